@@ -8,10 +8,17 @@ unicorn_sot.py:49) and is outside the timed region, as are H2D copies: frames ar
 Weights: synthetic (oracle/synth.py), data: synthetic clip.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f16x2|bf16|fp32] [--model ...] [--task sot|mot|vos]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the outputs of the last timed step if --dump-outputs
+is given, and prints one JSON line (`value` = frames/s, `ms_per_step` = milliseconds of one timed step).  Everything else
+(roofline / per-kernel-class leg, single-frame leg, CPU baseline + in-run parity, golden margin log, other precisions and
+configs, clock / power sensor, the N > 1 RLE gather check) runs only with --full; the --no-* / --with-* switches select
+within --full.
 
 HEADLINE = precision "f16x2" (fp32-equivalent split-f16 MFMA operands): the fastest mode that meets the parity bar of
-BASELINE.json:north_star (box/mask IoU >= 0.999, embedding cosine within 1e-4), checked IN THIS RUN against the CPU oracle
-("parity" key).  The bf16 mode (1 MFMA per product, misses box IoU with 8 operand bits) is reported next to it under
+BASELINE.json:north_star (box/mask IoU >= 0.999, embedding cosine within 1e-4), checked in a --full run against the CPU
+oracle ("parity" key).  The bf16 mode (1 MFMA per product, misses box IoU with 8 operand bits) is reported next to it under
 "modes", the other BASELINE configs under "configs".
 
 --gpus N > 1 without a torchrun environment re-launches itself as `python -m torch.distributed.run --nproc-per-node N`:
@@ -19,6 +26,7 @@ one process per GPU, one independent video stream per rank (stre
 collective; RCCL all_gather only for the result rows, external/lib/test/evaluation/running.py:111-120).
 """
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -69,7 +77,15 @@ def parse():
                     "`rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE` over a 3-step run of this script, ~70 s; N = 1 and without --no-extras only); "
                     "`roofline.traffic` then replays the committed passes under profiles/")
     ap.add_argument("--launch-check", action="store_true", help="only rendezvous (gloo on CPU, RCCL on GPUs) and report the world size")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline: roofline (+ HBM traffic passes), single-frame, CPU "
+                    "baseline + in-run parity (+ PyTorch-ROCm port), golden margin log, other precisions / configs, clock / power sensor, N > 1 RLE "
+                    "gather check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                    "(float32 / float64; rank 0; at most 64 MB: an output too large for its share is stored as a fixed seeded sample, <name>_sample.npy)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args):
@@ -158,7 +174,7 @@ def measure_pmc_traffic(args, H, W):
         for tag, ctr in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
             d = os.path.join(base, tag)
             cmd = ["rocprofv3", "--kernel-trace", "--pmc", ctr, "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1",
-                   "--no-cpu-baseline", "--no-extras", "--no-single-frame", "--no-pmc", "--model", args.model, "--height", str(H), "--width", str(W),
+                   "--full", "--no-cpu-baseline", "--no-extras", "--no-single-frame", "--no-pmc", "--model", args.model, "--height", str(H), "--width", str(W),
                    "--batch", str(args.batch), "--precision", args.precision, "--task", args.task]
             cp = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True,
                                 timeout=float(os.environ.get("UNI_BENCH_PMC_TIMEOUT", "240")))
@@ -415,6 +431,38 @@ def golden_sample(t, max_full=1 << 15):
     return a if a.size <= max_full else a[np.linspace(0, a.size - 1, max_full).astype(np.int64)]
 
 
+def dump_outputs(out_dir, outputs, budget_bytes=60 << 20):
+    """--dump-outputs: every tensor in `outputs` (nested dicts / tuples / lists; None skipped) -> out_dir/<name>.npy, float32 (float64
+    stays float64, integer and bool tensors become float64).  Smallest tensor first, each gets an even share of the budget still left
+    (60 MiB in all: the files stay under 64 MB); a tensor larger than its share is stored as a sample at sorted indices drawn from a
+    generator seeded with 0 (the same positions for the same shapes in every run and every build), named <name>_sample.npy.
+    -> {file name: stored shape}"""
+    import numpy as np
+    import torch
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            yield name, v
+        elif isinstance(v, (dict, tuple, list)):
+            for k, x in (v.items() if isinstance(v, dict) else enumerate(v)):
+                yield from walk("%s_%s" % (name, k) if name else str(k), x)
+    arrs = sorted(walk("", outputs), key=lambda a: a[1].numel())
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = budget_bytes, {}
+    for k, (name, t) in enumerate(arrs):
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        share = left // (len(arrs) - k) // (8 if dt == torch.float64 else 4)
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), share))
+            flat, name = flat[torch.from_numpy(idx).to(flat.device)], name + "_sample"
+        a = flat.to(dt).cpu().numpy().reshape(t.shape if flat.numel() == t.numel() else (-1,))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name + ".npy"] = list(a.shape)
+    return written
+
+
 class Stream:
     """One video stream on one GPU: model + resident frames + the per-step closure of a task."""
 
@@ -443,6 +491,8 @@ class Stream:
         self.results = torch.zeros((4096, 8), device=dev)
         self.last_rows = torch.zeros((0, 8), device=dev)
         self.pending_rows = []          # result rows of the steps since the last gather
+        self.keep_outputs = False       # --dump-outputs: step() keeps references to what it returned (no copy, no sync)
+        self.last_out = None
         self.seed = seed
         self._gen = None
         if task == "mot":     # evaluate_omni loop (mot_evaluator.py:991-1045) with the native QuasiDense association
@@ -507,6 +557,8 @@ class Stream:
                 self.last_rows = rows
                 self.pending_rows = (self.pending_rows + [rows])[-64:]
                 self.results[i % 4096] = rows[0]
+                if self.keep_outputs:
+                    self.last_out = dict(r, rows=rows)
             elif self.task == "mot":      # the evaluate_omni loop body over NB consecutive frames (unicorn_amd/tracker/omni.py)
                 img = self.batches[i % len(self.batches)]
                 if os.environ.get("UNI_BENCH_NO_PIPELINE"):
@@ -523,8 +575,12 @@ class Stream:
                             rows.append([0.0, float(i * img.shape[0] + bi), float(ids[k])] + [float(v) for v in bb[k, :5]])
                 self.last_rows = torch.tensor(rows, dtype=torch.float32).reshape(-1, 8).to(self.dev)
                 self.pending_rows = (self.pending_rows + [self.last_rows])[-64:]
+                if self.keep_outputs:
+                    self.last_out = {"rows": self.last_rows}
             else:                         # VOS: K = 3 objects, head per object, CondInst masks + postprocess (unicorn_vos.py:71-200)
                 res, _ = self.trk.step(self.frames[1 + i % (len(self.frames) - 1)])
+                if self.keep_outputs:
+                    self.last_out = {"obj": res}
                 d = res["1"][0]
                 if d is not None:
                     self.results[i % 4096, :7] = d
@@ -663,11 +719,17 @@ def main():
 
         def gather(streams):
             return gather_rows(streams if not errs else [_Empty])
-    sensor, win = GpuSensor(local_rank), []
-    with sensor:
+    if main_s is not None and args.dump_outputs and rank == 0:
+        main_s.keep_outputs = True
+    sensor, win = (GpuSensor(local_rank) if args.full else None), []
+    with sensor if sensor is not None else contextlib.nullcontext():
         dt, own_dt, _ = timed([main_s] if main_s is not None else [], args.steps, args.warmup, barrier, gather, max(1, args.gather_every), errs,
                               window=win)
-    clocks = sensor.summary(window=win or None)
+    clocks = sensor.summary(window=win or None) if sensor is not None else None
+    if main_s is not None and main_s.last_out is not None and not errs:      # before any other leg steps the stream again
+        written = dump_outputs(args.dump_outputs, main_s.last_out)
+        main_s.keep_outputs, main_s.last_out = False, None
+        print("[bench] outputs of the last timed step -> %s: %s" % (args.dump_outputs, written), file=sys.stderr, flush=True)
     fps_frames = args.steps * main_s.frames_per_step() if (main_s is not None and not errs) else 0
     per_rank, rank_errors = None, None
     if dist is not None:
@@ -695,38 +757,39 @@ def main():
         all_errs = [None] * world
         dist.all_gather_object(all_errs, list(errs))                    # a few short strings, control group
         rank_errors = {str(r_): e_ for r_, e_ in enumerate(all_errs) if e_} or None
-        # variable-length gather (mask RLE strings, unicorn_amd/parallel.py:gather_byte_strings): every rank encodes the box of its last
-        # result row as a mask with the device RLE kernel; rank 0 decodes every string and checks the round trip
-        hm, wm = 135, 240
-        strs, mk = [], None
-        try:
-            if errs:
-                raise RuntimeError("rank failed earlier")
-            from unicorn_amd.ops import rle_encode
-            rr = main_s.last_rows[:4] if main_s.last_rows.shape[0] else torch.zeros((1, 8), device=dev)
-            mk = torch.zeros((rr.shape[0], hm, wm), device=dev, dtype=torch.uint8)
-            bx = (rr[:, 3:7] / 8.0).clamp(min=0).long().cpu().tolist()
-            for k_, (x1, y1, x2, y2) in enumerate(bx):
-                mk[k_, min(y1, hm - 1):min(max(y2, y1 + 1), hm), min(x1, wm - 1):min(max(x2, x1 + 1), wm)] = 1
-            strs = rle_encode(mk)
-        except Exception as e:                      # noqa: BLE001
-            if not errs:
-                errs.append("rle: %r" % (e,))
-        allstr = gather_byte_strings(strs, group=dgroup)
-        gstat["rle_own_ok"] = bool(len(allstr) == world and allstr[rank] == strs)
-        if rank == 0:
-            from unicorn_amd.utils.masks import rle_string_to_mask
-            nstr, nbad = 0, 0
-            for r_ in range(world):
-                for b_ in allstr[r_]:
-                    try:
-                        rle_string_to_mask(b_, hm, wm)      # raises unless the runs cover the hm x wm mask exactly
-                    except ValueError:
-                        nbad += 1
-                    nstr += 1
-            gstat["rle_strings"], gstat["rle_undecodable"] = nstr, nbad
-            if strs and mk is not None:
-                gstat["rle_round_trip_ok"] = bool((torch.as_tensor(rle_string_to_mask(strs[0], hm, wm)) == mk[0].cpu()).all())
+        if args.full:
+            # variable-length gather (mask RLE strings, unicorn_amd/parallel.py:gather_byte_strings): every rank encodes the box of its last
+            # result row as a mask with the device RLE kernel; rank 0 decodes every string and checks the round trip
+            hm, wm = 135, 240
+            strs, mk = [], None
+            try:
+                if errs:
+                    raise RuntimeError("rank failed earlier")
+                from unicorn_amd.ops import rle_encode
+                rr = main_s.last_rows[:4] if main_s.last_rows.shape[0] else torch.zeros((1, 8), device=dev)
+                mk = torch.zeros((rr.shape[0], hm, wm), device=dev, dtype=torch.uint8)
+                bx = (rr[:, 3:7] / 8.0).clamp(min=0).long().cpu().tolist()
+                for k_, (x1, y1, x2, y2) in enumerate(bx):
+                    mk[k_, min(y1, hm - 1):min(max(y2, y1 + 1), hm), min(x1, wm - 1):min(max(x2, x1 + 1), wm)] = 1
+                strs = rle_encode(mk)
+            except Exception as e:                      # noqa: BLE001
+                if not errs:
+                    errs.append("rle: %r" % (e,))
+            allstr = gather_byte_strings(strs, group=dgroup)
+            gstat["rle_own_ok"] = bool(len(allstr) == world and allstr[rank] == strs)
+            if rank == 0:
+                from unicorn_amd.utils.masks import rle_string_to_mask
+                nstr, nbad = 0, 0
+                for r_ in range(world):
+                    for b_ in allstr[r_]:
+                        try:
+                            rle_string_to_mask(b_, hm, wm)      # raises unless the runs cover the hm x wm mask exactly
+                        except ValueError:
+                            nbad += 1
+                        nstr += 1
+                gstat["rle_strings"], gstat["rle_undecodable"] = nstr, nbad
+                if strs and mk is not None:
+                    gstat["rle_round_trip_ok"] = bool((torch.as_tensor(rle_string_to_mask(strs[0], hm, wm)) == mk[0].cpu()).all())
         gstat["dist"] = dinfo
     else:
         total_frames = float(fps_frames)
@@ -744,7 +807,7 @@ def main():
 
     # ---------------- roofline leg: per-kernel-class HIP-event timing on the launch stream (rank 0) ----------------
     roof, extra = None, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
         model = main_s.model
         prof_steps = 3
@@ -833,7 +896,7 @@ def main():
     # ---------------- single-frame leg: ONE (1,3,H,W) frame per call, host-synchronised per frame = the reference drivers' call pattern
     # (external/lib/test/tracker/unicorn_sot.py:57-76), with its own roofline block ----------------
     single = None
-    if rank == 0 and task == "sot" and not args.no_single_frame:
+    if rank == 0 and args.full and task == "sot" and not args.no_single_frame:
         import ctypes as C
         with torch.no_grad():
             for _ in range(3):
@@ -876,7 +939,7 @@ def main():
 
     # ---------------- CPU baseline (the oracle = port of the reference, host cores, bounded sample) + in-run parity ----------------
     cpu, parity = None, None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cores = min(os.cpu_count() or 1, 16)
         torch.set_num_threads(cores)
         P, cfg = main_s.P, main_s.cfg
@@ -995,7 +1058,7 @@ def main():
 
     # ---------------- sub-results: other precision modes, single-frame latency, the other BASELINE configs ----------------
     modes, configs = {}, {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and args.full and world == 1 and not args.no_extras:
         def quick(model_name, precision, task, nb, steps=4, warmup=1, P=None, keep=False):
             s = Stream(model_name, precision, task, H, W, nb, dev, seed=1, corr_prec=args.corr_precision, P=P)
             d = timed([s], steps, warmup, barrier)[0]

@@ -120,3 +120,34 @@ def test_gpu_sensor_summary_uses_only_the_timed_window():
     w = []
     dt, own, _ = bench.timed([_S()], 3, 1, lambda: None, window=w)
     assert len(w) == 2 and abs((w[1] - w[0]) - dt) < 1e-6
+
+
+def test_dump_outputs_names_dtypes_and_seeded_sample(tmp_path):
+    """--dump-outputs: nested step outputs -> <name>.npy in float32 / float64 (integers as float64, None skipped); smallest first, a tensor
+    over its share of the budget left is stored as a sample at the same sorted positions in every run (<name>_sample.npy)"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = {"head": torch.rand(2, 5, 6, generator=g), "fpn": (torch.rand(3, 4, generator=g), torch.rand(1000, generator=g)),
+            "rows": torch.arange(8), "obj": {"1": (None, torch.rand(4, dtype=torch.float64, generator=g))}}
+    budget = 2000          # 32 + 64 + 48 + 240 bytes stored whole, 1616 bytes = 404 float32 elements left for the largest
+    w1 = bench.dump_outputs(str(tmp_path / "a"), outs, budget_bytes=budget)
+    w2 = bench.dump_outputs(str(tmp_path / "b"), outs, budget_bytes=budget)
+    assert w1 == w2 == {"head.npy": [2, 5, 6], "fpn_0.npy": [3, 4], "fpn_1_sample.npy": [404], "rows.npy": [8], "obj_1_1.npy": [4]}
+    total = 0
+    for f in w1:
+        a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= budget
+    assert np.array_equal(np.load(str(tmp_path / "a" / "head.npy")), outs["head"].numpy())
+    assert np.load(str(tmp_path / "a" / "rows.npy")).dtype == np.float64 and np.load(str(tmp_path / "a" / "obj_1_1.npy")).dtype == np.float64
+    s = np.load(str(tmp_path / "a" / "fpn_1_sample.npy"))
+    assert np.isin(s, outs["fpn"][1].numpy()).all()
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps" in out.stderr, out.stderr[-500:]

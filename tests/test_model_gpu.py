@@ -1036,8 +1036,8 @@ def test_bench_two_ranks_shared_gpu_mix_plumbing():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(UNI_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--task", "mix", "--model", "unicorn_track_tiny", "--height", "320",
-                          "--width", "512", "--batch", "2", "--steps", "4", "--warmup", "1", "--gather-every", "2", "--no-cpu-baseline", "--no-extras",
-                          "--no-single-frame"], env=env, capture_output=True, text=True, timeout=900)
+                          "--width", "512", "--batch", "2", "--steps", "4", "--warmup", "1", "--gather-every", "2", "--full", "--no-cpu-baseline",
+                          "--no-extras", "--no-single-frame"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

@@ -1,4 +1,4 @@
-run() { env "$@" timeout 200 python bench.py --no-extras --no-cpu-baseline --no-single-frame --steps 12 2>/dev/null | python -c "
+run() { env "$@" timeout 200 python bench.py --full --no-extras --no-cpu-baseline --no-single-frame --steps 12 2>/dev/null | python -c "
 import json,sys;b=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('%-28s %.2f fps  gemm %.1f us/launch' % ('$*', b['value'], b['roofline']['avg_launch_us']))"; }
 run X=base
 run UNI_NO_H2D_192=1
