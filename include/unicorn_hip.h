@@ -1,4 +1,4 @@
-/* libunicorn_hip.so — C-ABI of the MI355X-native Unicorn inference hot path.
+/* libunicorn_hip.so — C-ABI of the MI355X-native Unicorn inference hot path (+ the gradient of its one native operator).
  *
  * This is the drop-in boundary: plain pointers and sizes, no torch types.  The caller
  * (Python/ctypes in unicorn_amd/, or any other host) owns every input/output buffer (device memory,
@@ -14,6 +14,13 @@
  *   uni_msda_fwd            MultiScaleDeformableAttention.ms_deform_attn_forward
  *                           (unicorn/models/ops/src/vision.cpp:13-16, ops/src/ms_deform_attn.h:19-38,
  *                            ops/src/cuda/ms_deform_attn_cuda.cu:20-80)
+ *   uni_msda_bwd            MultiScaleDeformableAttention.ms_deform_attn_backward
+ *                           (ops/src/vision.cpp:13-16, ops/src/ms_deform_attn.h:40-61,
+ *                            ops/src/cuda/ms_deform_attn_cuda.cu:83-153, ms_deform_im2col_cuda.cuh:87-234,301-920,956-1326)
+ *   uni_msda_fwd_f64 / uni_msda_bwd_f64   the double dispatch of the same two functions (AT_DISPATCH_FLOATING_TYPES,
+ *                            ms_deform_attn_cuda.cu:64,134).  Together the four are the whole native boundary of the reference's
+ *                            operator, forward and gradient (unicorn_amd.msda_ext offers them under the pybind module's name).
+ *                            The model-level entry points below stay inference only.
  *   uni_corr_softmax_pv     simi = E_ref^T E_cur; softmax(dim=0); values @ trans
  *                           (external/lib/test/tracker/unicorn_sot.py:95-100, unicorn_vos.py:166-181)
  *   uni_backbone_fpn        Unicorn.forward(mode="backbone") (unicorn/models/unicorn.py:231-258;
@@ -139,6 +146,31 @@ int uni_pos_embed(uni_ctx* ctx, int h, int w, float* out_nhwc, uni_stream_t stre
 int uni_msda_fwd(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
                  const float* sampling_loc, const float* attn_weight, float* out, int N, int S, int M, int D, int Lq,
                  int L, int P, uni_stream_t stream);
+int uni_msda_fwd_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                     const double* sampling_loc, const double* attn_weight, double* out, int N, int S, int M, int D,
+                     int Lq, int L, int P, uni_stream_t stream);
+/* Gradient of uni_msda_fwd (replaces ms_deform_attn_cuda_backward, ms_deform_attn_cuda.cu:83-153, and the col2im kernels
+ * ms_deform_im2col_cuda.cuh:301-920,956-1326): the inputs of the forward plus grad_output [N,Lq,M*D] ->
+ *   grad_value [N,S,M,D]              scatter-add of w_corner * attn * grad_output into the up-to-four corner rows,
+ *   grad_sampling_loc [N,Lq,M,L,P,2]  (W, H) * attn * sum_d grad_output_d * d(bilinear_d)/d(x, y),
+ *   grad_attn_weight [N,Lq,M,L,P]     sum_d grad_output_d * bilinear_d,
+ * with the forward's rules (pixel coordinates loc*(W,H) - 0.5; a sample outside -1 < x < W, -1 < y < H contributes nothing and gets
+ * zero gradients; corners outside the map contribute nothing).  Same limits as the forward (L <= 8, sum(H*W) == S); every level must
+ * lie inside [0, S).  All three outputs are written completely: the call zeroes grad_value itself on the stream (hipMemsetAsync) and
+ * accumulates into it with hardware float atomics (global_atomic_add_f32 / _f64).  Two consequences for the caller:
+ *   - grad_value MUST be ordinary device memory (a hipMalloc-class allocation; torch device tensors are) -- NOT fine-grained,
+ *     managed or host-mapped memory, where the hardware float atomic is not performed;
+ *   - grad_value depends on the arrival order of the adds in its last bits, run to run, exactly like the reference's atomicAdd;
+ *     grad_sampling_loc and grad_attn_weight have one writer per element and are bitwise reproducible.
+ * Lq == 0 or N == 0 returns at once with grad_value zeroed. */
+int uni_msda_bwd(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                 const float* sampling_loc, const float* attn_weight, const float* grad_output, float* grad_value,
+                 float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M, int D, int Lq, int L, int P,
+                 uni_stream_t stream);
+int uni_msda_bwd_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                     const double* sampling_loc, const double* attn_weight, const double* grad_output, double* grad_value,
+                     double* grad_sampling_loc, double* grad_attn_weight, int N, int S, int M, int D, int Lq, int L, int P,
+                     uni_stream_t stream);
 /* e_ref [R,128], e_cur [Q,128] fp32 row-major (NHWC embedding maps), values [K,R] -> out [K,Q].
  * precision 0 = exact fp32 MFMA, 1 = fp32-equivalent bf16x3 split (6 bf16 MFMAs per product), 2 = fp32-equivalent f16x2 split
  * (3 f16 MFMAs per product; operands must lie inside the f16 range, |x| < 65504 / log2 e), 3 = the reference DRIVER's arithmetic

@@ -39,6 +39,12 @@ PROTOS = {
     "uni_pos_embed": (c_i, [C.c_void_p, c_i, c_i, c_f, C.c_void_p]),
     "uni_msda_fwd": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                            C.c_void_p]),
+    "uni_msda_fwd_f64": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                               C.c_void_p]),
+    "uni_msda_bwd": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i,
+                           c_i, c_i, C.c_void_p]),
+    "uni_msda_bwd_f64": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
+                               c_i, c_i, c_i, C.c_void_p]),
     "uni_corr_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i]),
     "uni_corr_softmax_pv": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_corr_workspace_bytes_batched": (C.c_size_t, [c_i, c_i, c_i, c_i]),

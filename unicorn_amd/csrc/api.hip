@@ -188,7 +188,28 @@ int uni_pos_embed(uni_ctx* ctx, int h, int w, float* out_nhwc, uni_stream_t stre
 int uni_msda_fwd(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const float* sampling_loc,
                  const float* attn_weight, float* out, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {
     UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && out, "msda: NULL argument");
-    API(launch_msda(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, out, N, S_, M, D, Lq, L, P, S(stream)));
+    API(launch_msda<float>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, out, N, S_, M, D, Lq, L, P, S(stream)));
+}
+int uni_msda_fwd_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const double* sampling_loc,
+                     const double* attn_weight, double* out, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {
+    UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && out, "msda: NULL argument");
+    API(launch_msda<double>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, out, N, S_, M, D, Lq, L, P, S(stream)));
+}
+int uni_msda_bwd(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const float* sampling_loc,
+                 const float* attn_weight, const float* grad_output, float* grad_value, float* grad_sampling_loc,
+                 float* grad_attn_weight, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {
+    UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && grad_output && grad_value &&
+                grad_sampling_loc && grad_attn_weight, "msda_bwd: NULL argument");
+    API(launch_msda_bwd<float>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
+                               grad_sampling_loc, grad_attn_weight, N, S_, M, D, Lq, L, P, S(stream)));
+}
+int uni_msda_bwd_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const double* sampling_loc,
+                     const double* attn_weight, const double* grad_output, double* grad_value, double* grad_sampling_loc,
+                     double* grad_attn_weight, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {
+    UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && grad_output && grad_value &&
+                grad_sampling_loc && grad_attn_weight, "msda_bwd: NULL argument");
+    API(launch_msda_bwd<double>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
+                                grad_sampling_loc, grad_attn_weight, N, S_, M, D, Lq, L, P, S(stream)));
 }
 size_t uni_corr_workspace_bytes(int R, int Q, int K) { return corr_workspace_bytes(R, Q, K); }
 int uni_corr_softmax_pv(const float* e_ref, const float* e_cur, const float* values, float* out, int R, int Q, int D, int K,

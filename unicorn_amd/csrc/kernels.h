@@ -125,8 +125,16 @@ int launch_stem(const StemArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- msda.hip
 // reference-compatible op (ops/src/vision.cpp:13-16): value [N,S,M,D], loc [N,Lq,M,L,P,2], attn [N,Lq,M,L,P]
-int launch_msda(const float* value, const int64_t* shapes_host, const int64_t* lsi_host, const float* loc,
-                const float* attn, float* out, int N, int S, int M, int D, int Lq, int L, int P, hipStream_t s);
+// T = float | double (the reference dispatches both, ms_deform_attn_cuda.cu:64,134)
+template <typename T>
+int launch_msda(const T* value, const int64_t* shapes_host, const int64_t* lsi_host, const T* loc,
+                const T* attn, T* out, int N, int S, int M, int D, int Lq, int L, int P, hipStream_t s);
+// backward (ms_deform_attn_cuda.cu:83-153): zeroes grad_value on the stream, then scatter-adds into it with float atomics;
+// grad_loc [N,Lq,M,L,P,2] and grad_attn [N,Lq,M,L,P] are written by plain stores, every element
+template <typename T>
+int launch_msda_bwd(const T* value, const int64_t* shapes_host, const int64_t* lsi_host, const T* loc, const T* attn,
+                    const T* grad_out, T* grad_value, T* grad_loc, T* grad_attn, int N, int S, int M, int D, int Lq, int L, int P,
+                    hipStream_t s);
 // fused engine variant: raw offsets / attention logits -> softmax, loc = ref + off/(W,H), sample, bf16 out
 struct MsdaFusedArgs {
     const float* value = nullptr;             // [2*hw][256] fp32

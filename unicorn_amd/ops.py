@@ -22,22 +22,82 @@ def empty_nhwc(c, h, w, device, b=1):
     return torch.empty((b, c, h, w), device=device, dtype=torch.float32, memory_format=torch.channels_last)
 
 
-def msda_forward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step=64):
-    """Same signature as MultiScaleDeformableAttention.ms_deform_attn_forward (ops/src/vision.cpp:13-16)."""
-    _need_cuda(value, sampling_locations, attention_weights)
-    if value.dtype != torch.float32:
-        raise L.UnicornHipError("msda_forward: only fp32 is implemented (reference dispatches fp32/fp64)")
-    value, loc, attn = value.contiguous(), sampling_locations.contiguous(), attention_weights.contiguous()
-    N, S, M, D = value.shape
-    _, Lq, _, Ln, P, _ = loc.shape
+_MSDA_ENTRY = {torch.float32: ("uni_msda_fwd", "uni_msda_bwd"), torch.float64: ("uni_msda_fwd_f64", "uni_msda_bwd_f64")}
+
+
+def _msda_args(what, value, spatial_shapes, level_start_index, loc, attn, *more):
+    """Common argument handling of the two MultiScaleDeformableAttention functions: device + dtype checks (fp32 / fp64, no mixing, as
+    AT_DISPATCH_FLOATING_TYPES on value.type()), contiguous copies, the host int64 shape arrays and the sizes."""
+    ts = (value, loc, attn) + more
+    _need_cuda(*ts)
+    if value.dtype not in _MSDA_ENTRY:
+        raise L.UnicornHipError("%s: dtype %s unsupported (fp32 / fp64, like the reference's dispatch)" % (what, value.dtype))
+    if any(t.dtype != value.dtype for t in ts):
+        raise L.UnicornHipError("%s: mixed dtypes %s (every floating tensor must have value's dtype)" % (what, [str(t.dtype) for t in ts]))
+    if value.dim() != 4 or loc.dim() != 6 or attn.dim() != 5 or loc.shape[-1] != 2 or tuple(loc.shape[:5]) != tuple(attn.shape) \
+            or loc.shape[0] != value.shape[0] or loc.shape[2] != value.shape[2]:
+        raise L.UnicornHipError("%s: shapes value %s, sampling_locations %s, attention_weights %s do not fit (N,S,M,D), (N,Lq,M,L,P,2), "
+                                "(N,Lq,M,L,P)" % (what, tuple(value.shape), tuple(loc.shape), tuple(attn.shape)))
+    Ln = loc.shape[3]
+    if spatial_shapes.numel() != 2 * Ln or level_start_index.numel() != Ln:
+        raise L.UnicornHipError("%s: spatial_shapes / level_start_index do not describe %d levels" % (what, Ln))
     shp = (C.c_int64 * (2 * Ln))(*[int(v) for v in spatial_shapes.reshape(-1).tolist()])
     lsi = (C.c_int64 * Ln)(*[int(v) for v in level_start_index.reshape(-1).tolist()])
-    out = torch.empty((N, Lq, M * D), device=value.device, dtype=torch.float32)
+    return tuple(t.contiguous() for t in ts), shp, lsi
+
+
+def msda_forward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step=64):
+    """Same signature as MultiScaleDeformableAttention.ms_deform_attn_forward (ops/src/vision.cpp:13-16); fp32 or fp64."""
+    (value, loc, attn), shp, lsi = _msda_args("msda_forward", value, spatial_shapes, level_start_index, sampling_locations,
+                                              attention_weights)
+    N, S, M, D = value.shape
+    _, Lq, _, Ln, P, _ = loc.shape
+    out = torch.empty((N, Lq, M * D), device=value.device, dtype=value.dtype)
     if out.numel() == 0:
         return out
-    L.check(L.lib().uni_msda_fwd(L.ptr(value), shp, lsi, L.ptr(loc), L.ptr(attn), L.ptr(out), N, S, M, D, Lq, Ln, P,
-                                 L.stream_ptr()), "uni_msda_fwd")
+    name = _MSDA_ENTRY[value.dtype][0]
+    L.check(getattr(L.lib(), name)(L.ptr(value), shp, lsi, L.ptr(loc), L.ptr(attn), L.ptr(out), N, S, M, D, Lq, Ln, P,
+                                   L.stream_ptr()), name)
     return out
+
+
+def msda_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output, im2col_step=64):
+    """Same signature as MultiScaleDeformableAttention.ms_deform_attn_backward (ops/src/vision.cpp:13-16); fp32 or fp64.
+    Returns (grad_value, grad_sampling_loc, grad_attn_weight).  grad_value is summed with float atomics: its last bits depend on the
+    arrival order, like the reference's; the other two are bitwise reproducible."""
+    (value, loc, attn, gout), shp, lsi = _msda_args("msda_backward", value, spatial_shapes, level_start_index, sampling_locations,
+                                                    attention_weights, grad_output)
+    N, S, M, D = value.shape
+    _, Lq, _, Ln, P, _ = loc.shape
+    if gout.numel() != N * Lq * M * D:
+        raise L.UnicornHipError("msda_backward: grad_output %s is not (N, Lq, M*D) = (%d, %d, %d)" % (tuple(gout.shape), N, Lq, M * D))
+    gvalue, gloc, gattn = torch.empty_like(value), torch.empty_like(loc), torch.empty_like(attn)
+    if value.numel() == 0 or attn.numel() == 0:       # no query / empty batch: nothing to scatter (empty tensors have no device pointer)
+        return gvalue.zero_(), gloc, gattn
+    name = _MSDA_ENTRY[value.dtype][1]
+    L.check(getattr(L.lib(), name)(L.ptr(value), shp, lsi, L.ptr(loc), L.ptr(attn), L.ptr(gout), L.ptr(gvalue), L.ptr(gloc),
+                                   L.ptr(gattn), N, S, M, D, Lq, Ln, P, L.stream_ptr()), name)
+    return gvalue, gloc, gattn
+
+
+class MSDeformAttnFunction(torch.autograd.Function):
+    """The reference's autograd function (ops/functions/ms_deform_attn_func.py:21-38) on the two HIP operators:
+    apply(value, shapes, level_start_index, sampling_locations, attention_weights, im2col_step)."""
+
+    @staticmethod
+    def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights, im2col_step):
+        ctx.im2col_step = im2col_step
+        output = msda_forward(value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights, im2col_step)
+        ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights)
+        return output
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        value, shapes, lsi, loc, attn = ctx.saved_tensors
+        gv, gl, ga = msda_backward(value, shapes, lsi, loc, attn, grad_output.contiguous(), ctx.im2col_step)
+        need = ctx.needs_input_grad
+        return gv if need[0] else None, None, None, gl if need[3] else None, ga if need[4] else None, None
 
 
 _corr_ws = {}
