@@ -23,6 +23,8 @@
  *                            The model-level entry points below stay inference only.
  *   uni_corr_softmax_pv     simi = E_ref^T E_cur; softmax(dim=0); values @ trans
  *                           (external/lib/test/tracker/unicorn_sot.py:95-100, unicorn_vos.py:166-181)
+ *   uni_corr_softmax_pv_lse / uni_corr_softmax_pv_bwd (+ _f64)   the same three lines in the training losses, forward and gradient
+ *                           (unicorn/models/unicorn.py:321-326, :342-371)
  *   uni_backbone_fpn        Unicorn.forward(mode="backbone") (unicorn/models/unicorn.py:231-258;
  *                            backbone/convnext.py:141-154, backbone/yolo_pafpn_new.py:113-161)
  *   uni_interaction         Unicorn.forward(mode="interaction") (unicorn.py:260-276,
@@ -185,6 +187,32 @@ size_t uni_corr_workspace_bytes_batched(int B, int R, int Q, int K);
 int uni_corr_softmax_pv_batched(const float* e_ref, const float* e_cur, const float* values, float* out, int B, int R, int Q, int D,
                                 int K, int values_per_frame, int precision, void* workspace, size_t workspace_bytes,
                                 uni_stream_t stream);
+/* The same operator for TRAINING: the label propagation of the reference's losses (unicorn/models/unicorn.py:321-326, compute_loss_sot,
+ * and :342-371, compute_loss_vos):  simi_mat = bmm(embed_0^T, embed_1); trans_mat_01 = softmax(simi_mat, dim=1);
+ * pred_lbs1 = bmm(gt_lbs_0, trans_mat_01), whose R x Q matrices (1 GB each in fp32 at 800 x 1280, kept by autograd) never exist here.
+ *   uni_corr_softmax_pv_lse  = uni_corr_softmax_pv_batched (same kernels, `out` bitwise equal) that also stores
+ *                              lse[b,q] = log sum_r exp(S[r,q])   [B,Q]
+ *   uni_corr_softmax_pv_bwd  given grad_out = d loss / d out [B,K,Q] and the forward's out / lse, writes
+ *                              grad_e_ref [B,R,128], grad_e_cur [B,Q,128], grad_values [B,K,R] ([K,R], summed over the frames, when
+ *                              values_per_frame = 0).  Each of the three may be NULL: that gradient is not computed.  P is recomputed
+ *                              tile by tile; every output row has ONE writer (two recompute passes, no atomics), so the results are
+ *                              bitwise reproducible and completely written by the call.
+ * precision: 0 (exact fp32 MFMA) is the only backward arithmetic; any other value is refused by _bwd (the forward accepts 0..3).
+ * workspace >= uni_corr_bwd_workspace_bytes (covers both calls), 16-byte aligned like the embeddings.  The _f64 pair is a plain
+ * double-precision evaluation (FMA loops, one writer per element, no workspace) for gradcheck and fixtures on small problems. */
+size_t uni_corr_bwd_workspace_bytes(int B, int R, int Q, int K);
+int uni_corr_softmax_pv_lse(const float* e_ref, const float* e_cur, const float* values, float* out, float* lse, int B, int R, int Q,
+                            int D, int K, int values_per_frame, int precision, void* workspace, size_t workspace_bytes,
+                            uni_stream_t stream);
+int uni_corr_softmax_pv_bwd(const float* e_ref, const float* e_cur, const float* values, const float* out, const float* lse,
+                            const float* grad_out, float* grad_e_ref, float* grad_e_cur, float* grad_values, int B, int R, int Q,
+                            int D, int K, int values_per_frame, int precision, void* workspace, size_t workspace_bytes,
+                            uni_stream_t stream);
+int uni_corr_softmax_pv_lse_f64(const double* e_ref, const double* e_cur, const double* values, double* out, double* lse, int B, int R,
+                                int Q, int D, int K, int values_per_frame, uni_stream_t stream);
+int uni_corr_softmax_pv_bwd_f64(const double* e_ref, const double* e_cur, const double* values, const double* out, const double* lse,
+                                const double* grad_out, double* grad_e_ref, double* grad_e_cur, double* grad_values, int B, int R,
+                                int Q, int D, int K, int values_per_frame, uni_stream_t stream);
 int uni_prior_pyramid(const float* p8, float* p16, float* p32, int K, int H8, int W8, uni_stream_t stream);
 int uni_label_map_s8(const float* box_xyxy_dev, float* out, int H, int W, uni_stream_t stream);
 int uni_sample_embeddings(const float* embed_nhwc, int H8, int W8, int C, const float* boxes_xyxy, int ld_boxes, int n,

@@ -223,6 +223,33 @@ int uni_corr_softmax_pv_batched(const float* e_ref, const float* e_cur, const fl
     UNI_REQUIRE(e_ref && e_cur && values && out && workspace, "corr: NULL argument");
     API(launch_corr_batched(e_ref, e_cur, values, out, B, R, Q, D, K, values_per_frame, precision, workspace, workspace_bytes, S(stream)));
 }
+size_t uni_corr_bwd_workspace_bytes(int B, int R, int Q, int K) { return corr_bwd_workspace_bytes(B, R, Q, K); }
+int uni_corr_softmax_pv_lse(const float* e_ref, const float* e_cur, const float* values, float* out, float* lse, int B, int R, int Q, int D,
+                            int K, int values_per_frame, int precision, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(e_ref && e_cur && values && out && lse && workspace, "corr_lse: NULL argument");
+    UNI_REQUIRE(B > 0 && R > 0 && Q > 0 && K > 0, "corr_lse: empty problem B=%d R=%d Q=%d K=%d", B, R, Q, K);
+    UNI_REQUIRE(workspace_bytes >= corr_bwd_workspace_bytes(B, R, Q, K), "corr_lse: workspace too small (uni_corr_bwd_workspace_bytes)");
+    API(launch_corr_batched(e_ref, e_cur, values, out, B, R, Q, D, K, values_per_frame, precision, workspace, workspace_bytes, S(stream), lse));
+}
+int uni_corr_softmax_pv_bwd(const float* e_ref, const float* e_cur, const float* values, const float* out, const float* lse,
+                            const float* grad_out, float* grad_e_ref, float* grad_e_cur, float* grad_values, int B, int R, int Q, int D,
+                            int K, int values_per_frame, int precision, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(e_ref && e_cur && values && out && lse && grad_out && workspace, "corr_bwd: NULL argument");
+    API(launch_corr_bwd(e_ref, e_cur, values, out, lse, grad_out, grad_e_ref, grad_e_cur, grad_values, B, R, Q, D, K, values_per_frame,
+                        precision, workspace, workspace_bytes, S(stream)));
+}
+int uni_corr_softmax_pv_lse_f64(const double* e_ref, const double* e_cur, const double* values, double* out, double* lse, int B, int R,
+                                int Q, int D, int K, int values_per_frame, uni_stream_t stream) {
+    UNI_REQUIRE(e_ref && e_cur && values && out && lse, "corr_lse_f64: NULL argument");
+    API(launch_corr_f64(e_ref, e_cur, values, out, lse, B, R, Q, D, K, values_per_frame, S(stream)));
+}
+int uni_corr_softmax_pv_bwd_f64(const double* e_ref, const double* e_cur, const double* values, const double* out, const double* lse,
+                                const double* grad_out, double* grad_e_ref, double* grad_e_cur, double* grad_values, int B, int R,
+                                int Q, int D, int K, int values_per_frame, uni_stream_t stream) {
+    UNI_REQUIRE(e_ref && e_cur && values && out && lse && grad_out, "corr_bwd_f64: NULL argument");
+    API(launch_corr_bwd_f64(e_ref, e_cur, values, out, lse, grad_out, grad_e_ref, grad_e_cur, grad_values, B, R, Q, D, K, values_per_frame,
+                            S(stream)));
+}
 int uni_prior_pyramid(const float* p8, float* p16, float* p32, int K, int H8, int W8, uni_stream_t stream) {
     UNI_REQUIRE(p8 && p16 && p32, "prior_pyramid: NULL argument");
     API(launch_prior_pyramid(p8, p16, p32, K, H8, W8, S(stream)));

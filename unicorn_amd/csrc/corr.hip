@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256, 2) void corr_f32_kernel(const float* __restric
                                                           const float* __restrict__ ecur,
                                                           const float* __restrict__ v, float* __restrict__ out,
                                                           float* __restrict__ ws, int R, int Q, int K, int nsplit,
-                                                          int rows_per_split) {
+                                                          int rows_per_split, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                    // [2][TR*LDA]
     float* Vs = smem + 2 * TR * LDA;     // [2][KV*TR]
@@ -146,6 +146,7 @@ __global__ __launch_bounds__(256, 2) void corr_f32_kernel(const float* __restric
 #pragma unroll
             for (int k = 0; k < KV; ++k)
                 if (k < K) out[(size_t)k * Q + q] = o[k] / l;
+            if (lse) lse[q] = m + logf(l);
         } else {
             float* w = ws + ((size_t)split * Q + q) * (2 + KV);
             w[0] = m;
@@ -179,7 +180,7 @@ template <int KV, int NWV>
 __global__ __launch_bounds__(64 * NWV) void corr_split_kernel(const float* __restrict__ eref, const float* __restrict__ ecur,
                                                          const float* __restrict__ v, float* __restrict__ out,
                                                          float* __restrict__ ws, int R, int Q, int K, int nsplit,
-                                                         int rows_per_split) {
+                                                         int rows_per_split, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int PLANE = TR * CD;                       // bf16 elements per piece plane (32 x 128)
     bf16* As = reinterpret_cast<bf16*>(smem);            // [2 buffers][3 planes][TR][CD]
@@ -324,6 +325,7 @@ __global__ __launch_bounds__(64 * NWV) void corr_split_kernel(const float* __res
 #pragma unroll
             for (int k = 0; k < KV; ++k)
                 if (k < K) out[(size_t)k * Q + q] = o[k] / l;
+            if (lse) lse[q] = m + logf(l);
         } else {
             float* w = ws + ((size_t)split * Q + q) * (2 + KV);
             w[0] = m;
@@ -355,7 +357,7 @@ template <int KV, int NWV, bool H1 = false>
 __global__ __launch_bounds__(64 * NWV) void corr_h2_kernel(const float* __restrict__ eref, const float* __restrict__ ecur,
                                                       const float* __restrict__ v, float* __restrict__ out,
                                                       float* __restrict__ ws, int R, int Q, int K, int nsplit,
-                                                      int rows_per_split, long v_frame_stride) {
+                                                      int rows_per_split, long v_frame_stride, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     {   // blockIdx.z = frame of a batch: [B][R][128] / [B][Q][128] embeddings, [B][K][Q] outputs, value rows shared (stride 0) or per frame
         const size_t z = blockIdx.z;
@@ -364,6 +366,7 @@ __global__ __launch_bounds__(64 * NWV) void corr_h2_kernel(const float* __restri
         out += z * (size_t)K * Q;
         ws += z * (size_t)nsplit * Q * (2 + KV);
         v += z * (size_t)v_frame_stride;
+        if (lse) lse += z * (size_t)Q;
     }
     constexpr int PLANE = TR * CD;                       // f16 elements per piece plane (32 x 128)
     f16* As = reinterpret_cast<f16*>(smem);              // [2 buffers][2 planes][TR][CD]
@@ -499,6 +502,7 @@ __global__ __launch_bounds__(64 * NWV) void corr_h2_kernel(const float* __restri
 #pragma unroll
             for (int k = 0; k < KV; ++k)
                 if (k < K) out[(size_t)k * Q + q] = o[k] / l;
+            if (lse) lse[q] = m + logf(l);
         } else {
             float* w = ws + ((size_t)split * Q + q) * (2 + KV);
             w[0] = m;
@@ -510,7 +514,7 @@ __global__ __launch_bounds__(64 * NWV) void corr_h2_kernel(const float* __restri
 }
 
 template <int KV>
-__global__ void corr_merge_kernel(const float* __restrict__ ws, float* __restrict__ out, int Q, int K, int nsplit) {
+__global__ void corr_merge_kernel(const float* __restrict__ ws, float* __restrict__ out, int Q, int K, int nsplit, float* __restrict__ lse) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= Q) return;
     ws += (size_t)blockIdx.y * nsplit * Q * (2 + KV);          // blockIdx.y = frame of a batch
@@ -530,6 +534,7 @@ __global__ void corr_merge_kernel(const float* __restrict__ ws, float* __restric
 #pragma unroll
     for (int k = 0; k < KV; ++k)
         if (k < K) out[(size_t)k * Q + q] = O[k] / L;
+    if (lse) lse[(size_t)blockIdx.y * Q + q] = M + logf(L);
 }
 
 int corr_slots(int precision) {     // co-resident blocks on the device: 2 x 4-wave blocks (fp32) / 1 x 8-wave block (split) per CU
@@ -567,7 +572,7 @@ int pick_nsplit(int R, int Q, int precision = 0, int B = 1) {
 
 template <int KV>
 int run(const float* eref, const float* ecur, const float* v, float* out, int R, int Q, int K, float* ws, size_t ws_bytes, int precision,
-        hipStream_t s, int B = 1, long vfs = 0) {
+        hipStream_t s, int B = 1, long vfs = 0, float* lse = nullptr) {
     const int ns = pick_nsplit(R, Q, precision, B);
     int rps = cdiv(cdiv(R, ns), TR) * TR;
     const int ns_eff = cdiv(R, rps);   // every split non-empty
@@ -578,25 +583,25 @@ int run(const float* eref, const float* ecur, const float* v, float* out, int R,
     if (precision == 3) {
         size_t lds = (size_t)2 * 2 * TR * CD * sizeof(f16) + (size_t)2 * KV * TR * sizeof(float);
         hipLaunchKernelGGL((corr_h2_kernel<KV, 8, true>), dim3(cdiv(Q, QB2), ns_eff, B), dim3(512), lds, s, eref, ecur, v, out, ws, R,
-                           Q, K, ns_eff, rps, vfs);
+                           Q, K, ns_eff, rps, vfs, ns_eff == 1 ? lse : nullptr);
     } else if (precision == 2) {
         size_t lds = (size_t)2 * 2 * TR * CD * sizeof(f16) + (size_t)2 * KV * TR * sizeof(float);
         hipLaunchKernelGGL((corr_h2_kernel<KV, 8>), dim3(cdiv(Q, QB2), ns_eff, B), dim3(512), lds, s, eref, ecur, v, out, ws, R,
-                           Q, K, ns_eff, rps, vfs);
+                           Q, K, ns_eff, rps, vfs, ns_eff == 1 ? lse : nullptr);
     } else if constexpr (KV > 8) {
         uni_set_error("corr: 16 value rows per pass only in precision 2 / 3");
         return -1;
     } else if (precision) {
         size_t lds = (size_t)2 * 3 * TR * CD * sizeof(bf16) + (size_t)2 * KV * TR * sizeof(float);
         hipLaunchKernelGGL((corr_split_kernel<KV, 8>), dim3(cdiv(Q, QB2), ns_eff), dim3(512), lds, s, eref, ecur, v, out, ws, R,
-                           Q, K, ns_eff, rps);
+                           Q, K, ns_eff, rps, ns_eff == 1 ? lse : nullptr);
     } else {
         size_t lds = (size_t)(2 * TR * LDA + 2 * KV * TR) * sizeof(float);
         hipLaunchKernelGGL((corr_f32_kernel<KV>), dim3(cdiv(Q, QB), ns_eff), dim3(256), lds, s, eref, ecur, v, out, ws, R,
-                           Q, K, ns_eff, rps);
+                           Q, K, ns_eff, rps, ns_eff == 1 ? lse : nullptr);
     }
     if (ns_eff > 1)
-        hipLaunchKernelGGL((corr_merge_kernel<KV>), dim3(cdiv(Q, 256), B), dim3(256), 0, s, ws, out, Q, K, ns_eff);
+        hipLaunchKernelGGL((corr_merge_kernel<KV>), dim3(cdiv(Q, 256), B), dim3(256), 0, s, ws, out, Q, K, ns_eff, lse);
     return 0;
 }
 }  // namespace
@@ -623,14 +628,14 @@ size_t corr_workspace_bytes_batched(int B, int R, int Q, int K) {
 // -- 0.222 vs 0.236-0.243 ms per frame against 16 launches (tools/corr_batch_probe.py).  Precisions 0 / 1 and more than 16 value rows
 // run frame by frame.
 int launch_corr_batched(const float* eref, const float* ecur, const float* v, float* out, int B, int R, int Q, int D, int K,
-                        int values_per_frame, int precision, void* workspace, size_t ws_bytes, hipStream_t s) {
+                        int values_per_frame, int precision, void* workspace, size_t ws_bytes, hipStream_t s, float* lse) {
     UNI_REQUIRE(B > 0, "corr: empty batch");
     UNI_REQUIRE(ws_bytes >= corr_workspace_bytes_batched(B, R, Q, K), "corr: workspace too small");
     const long vfs = values_per_frame ? (long)K * R : 0;
     if (B == 1 || precision < 2 || K > 16) {
         for (int b = 0; b < B; ++b) {
             const int rc = launch_corr(eref + (size_t)b * R * D, ecur + (size_t)b * Q * D, v + (size_t)b * vfs, out + (size_t)b * K * Q, R, Q, D, K,
-                                       precision, workspace, ws_bytes, s);
+                                       precision, workspace, ws_bytes, s, lse ? lse + (size_t)b * Q : nullptr);
             if (rc) return rc;
         }
         return 0;
@@ -640,14 +645,14 @@ int launch_corr_batched(const float* eref, const float* ecur, const float* v, fl
     UNI_REQUIRE(precision <= 3, "corr: precision %d not implemented", precision);
     UNI_REQUIRE(((uintptr_t)eref & 15) == 0 && ((uintptr_t)ecur & 15) == 0, "corr: embeddings must be 16-B aligned");
     float* ws = reinterpret_cast<float*>(workspace);
-    if (K == 1) return run<1>(eref, ecur, v, out, R, Q, K, ws, ws_bytes, precision, s, B, vfs);
-    if (K <= 4) return run<4>(eref, ecur, v, out, R, Q, K, ws, ws_bytes, precision, s, B, vfs);
-    if (K <= 8) return run<8>(eref, ecur, v, out, R, Q, K, ws, ws_bytes, precision, s, B, vfs);
-    return run<16>(eref, ecur, v, out, R, Q, K, ws, ws_bytes, precision, s, B, vfs);
+    if (K == 1) return run<1>(eref, ecur, v, out, R, Q, K, ws, ws_bytes, precision, s, B, vfs, lse);
+    if (K <= 4) return run<4>(eref, ecur, v, out, R, Q, K, ws, ws_bytes, precision, s, B, vfs, lse);
+    if (K <= 8) return run<8>(eref, ecur, v, out, R, Q, K, ws, ws_bytes, precision, s, B, vfs, lse);
+    return run<16>(eref, ecur, v, out, R, Q, K, ws, ws_bytes, precision, s, B, vfs, lse);
 }
 
 int launch_corr(const float* eref, const float* ecur, const float* v, float* out, int R, int Q, int D, int K,
-                int precision, void* workspace, size_t ws_bytes, hipStream_t s) {
+                int precision, void* workspace, size_t ws_bytes, hipStream_t s, float* lse) {
     UNI_REQUIRE(D == CD, "corr: embedding dim %d unsupported (128)", D);
     UNI_REQUIRE(R > 0 && Q > 0 && K > 0, "corr: empty problem R=%d Q=%d K=%d", R, Q, K);
     UNI_REQUIRE(precision >= 0 && precision <= 3, "corr: precision %d not implemented (0 = fp32 MFMA, 1 = bf16x3 split, 2 = f16x2 split, 3 = fp16 single pass)", precision);
@@ -660,10 +665,10 @@ int launch_corr(const float* eref, const float* ecur, const float* v, float* out
     for (int k0 = 0; k0 < K; k0 += chunk) {
         const int kc = K - k0 < chunk ? K - k0 : chunk;
         int rc;
-        if (kc == 1) rc = run<1>(eref, ecur, v + (size_t)k0 * R, out + (size_t)k0 * Q, R, Q, kc, ws, ws_bytes, precision, s);
-        else if (kc <= 4) rc = run<4>(eref, ecur, v + (size_t)k0 * R, out + (size_t)k0 * Q, R, Q, kc, ws, ws_bytes, precision, s);
-        else if (kc <= 8) rc = run<8>(eref, ecur, v + (size_t)k0 * R, out + (size_t)k0 * Q, R, Q, kc, ws, ws_bytes, precision, s);
-        else rc = run<16>(eref, ecur, v + (size_t)k0 * R, out + (size_t)k0 * Q, R, Q, kc, ws, ws_bytes, precision, s);
+        if (kc == 1) rc = run<1>(eref, ecur, v + (size_t)k0 * R, out + (size_t)k0 * Q, R, Q, kc, ws, ws_bytes, precision, s, 1, 0, k0 ? nullptr : lse);
+        else if (kc <= 4) rc = run<4>(eref, ecur, v + (size_t)k0 * R, out + (size_t)k0 * Q, R, Q, kc, ws, ws_bytes, precision, s, 1, 0, k0 ? nullptr : lse);
+        else if (kc <= 8) rc = run<8>(eref, ecur, v + (size_t)k0 * R, out + (size_t)k0 * Q, R, Q, kc, ws, ws_bytes, precision, s, 1, 0, k0 ? nullptr : lse);
+        else rc = run<16>(eref, ecur, v + (size_t)k0 * R, out + (size_t)k0 * Q, R, Q, kc, ws, ws_bytes, precision, s, 1, 0, k0 ? nullptr : lse);
         if (rc) return rc;
     }
     return 0;

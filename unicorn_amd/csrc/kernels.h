@@ -148,12 +148,27 @@ int launch_msda_fused(const MsdaFusedArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- corr.hip
 // out[k][q] = sum_r V[k][r] softmax_r(<Eref[r], Ecur[q]>);  Eref [R][D], Ecur [Q][D] fp32 row-major, V [K][R]
+// lse (optional, [Q] / [B][Q]): the log-sum-exp over the reference axis the kernels hold anyway, lse[q] = m + log l; one more store,
+// `out` is bitwise what the call without it returns
 int launch_corr(const float* eref, const float* ecur, const float* v, float* out, int R, int Q, int D, int K,
-                int precision, void* workspace, size_t ws_bytes, hipStream_t s);
+                int precision, void* workspace, size_t ws_bytes, hipStream_t s, float* lse = nullptr);
 size_t corr_workspace_bytes(int R, int Q, int K);
 int launch_corr_batched(const float* eref, const float* ecur, const float* v, float* out, int B, int R, int Q, int D, int K,
-                        int values_per_frame, int precision, void* workspace, size_t ws_bytes, hipStream_t s);
+                        int values_per_frame, int precision, void* workspace, size_t ws_bytes, hipStream_t s, float* lse = nullptr);
 size_t corr_workspace_bytes_batched(int B, int R, int Q, int K);
+
+// ---------------------------------------------------------------- corr_bwd.hip
+// gradient of the operator above (unicorn/models/unicorn.py:321-326 under autograd), flash-style: P is recomputed tile by tile from the
+// embeddings and lse.  gref / gcur / gv may each be NULL (not computed); every non-NULL output is written completely, one writer per element.
+size_t corr_bwd_workspace_bytes(int B, int R, int Q, int K);      // >= corr_workspace_bytes_batched: one scratch serves forward and backward
+int launch_corr_bwd(const float* eref, const float* ecur, const float* v, const float* out, const float* lse, const float* gout,
+                    float* gref, float* gcur, float* gv, int B, int R, int Q, int D, int K, int values_per_frame, int precision,
+                    void* workspace, size_t ws_bytes, hipStream_t s);
+// plain double-precision pair (FMA loops, one wave per output row, one writer per element; small problems, no performance claim)
+int launch_corr_f64(const double* eref, const double* ecur, const double* v, double* out, double* lse, int B, int R, int Q, int D, int K,
+                    int values_per_frame, hipStream_t s);
+int launch_corr_bwd_f64(const double* eref, const double* ecur, const double* v, const double* out, const double* lse, const double* gout,
+                        double* gref, double* gcur, double* gv, int B, int R, int Q, int D, int K, int values_per_frame, hipStream_t s);
 
 // ---------------------------------------------------------------- misc.hip
 int launch_cast_operand(const float* x, int ldx, bf16* out, int ldo, int M, int C, hipStream_t s, int b32 = 0);

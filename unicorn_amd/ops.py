@@ -159,6 +159,123 @@ def corr_softmax_pv_batched(embed_ref, embed_cur, values, precision=2, values_pe
     return out
 
 
+def _corr_scratch(dev, need):
+    key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    ws = _corr_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), device=dev, dtype=torch.uint8)
+        _corr_ws[key] = ws
+    return ws
+
+
+def _corr_train_args(what, embed_ref, embed_cur, values, *more):
+    """Argument handling of the differentiable correlation: shapes (B,R,D), (B,Q,D), (B,K,R) [+ (B,K,Q) tensors], one dtype (fp32 / fp64),
+    device tensors; returns contiguous tensors."""
+    ts = (embed_ref, embed_cur, values) + more
+    if embed_ref.dim() != 3 or embed_cur.dim() != 3 or values.dim() != 3 or embed_ref.shape[0] != embed_cur.shape[0] \
+            or values.shape[0] != embed_ref.shape[0] or embed_ref.shape[2] != embed_cur.shape[2] or values.shape[2] != embed_ref.shape[1] \
+            or any(t.shape != (values.shape[0], values.shape[1], embed_cur.shape[1]) for t in more):
+        raise L.UnicornHipError("%s: shapes %s do not fit embed_ref (B,R,D), embed_cur (B,Q,D), values (B,K,R)%s"
+                                % (what, [tuple(t.shape) for t in ts], ", out / grad_out (B,K,Q)" if more else ""))
+    if embed_ref.dtype not in (torch.float32, torch.float64) or any(t.dtype != embed_ref.dtype for t in ts):
+        raise L.UnicornHipError("%s: dtypes %s unsupported (all fp32 or all fp64)" % (what, [str(t.dtype) for t in ts]))
+    if min(embed_ref.shape + embed_cur.shape + values.shape) == 0:
+        raise L.UnicornHipError("%s: empty problem %s" % (what, [tuple(t.shape) for t in ts]))
+    _need_cuda(*ts)
+    return tuple(t.contiguous() for t in ts)
+
+
+def corr_softmax_pv_lse(embed_ref, embed_cur, values, precision=0):
+    """The forward of the differentiable operator (`uni_corr_softmax_pv_lse`): embed_ref (B,R,128), embed_cur (B,Q,128) row-major, values (B,K,R)
+    (or (K,R): rows shared by the frames) -> (out (B,K,Q), lse (B,Q)) with lse[b,q] = logsumexp_r <embed_ref[b,r], embed_cur[b,q]>.
+    `out` is bitwise what corr_softmax_pv_batched returns for the same inputs and precision (the same kernels, one more store).
+    fp64 tensors take the plain double-precision path (precision is ignored there)."""
+    shared = values.dim() == 2
+    er, ec, v = _corr_train_args("corr_softmax_pv_lse", embed_ref, embed_cur,
+                                 values.unsqueeze(0).expand(embed_ref.shape[0], -1, -1) if shared and embed_ref.dim() == 3 else values)
+    if shared:
+        v = values.contiguous()
+    B, R, D = er.shape
+    Q, K = ec.shape[1], v.shape[-2]
+    out = torch.empty((B, K, Q), device=er.device, dtype=er.dtype)
+    lse = torch.empty((B, Q), device=er.device, dtype=er.dtype)
+    with torch.cuda.device(er.device):
+        if er.dtype == torch.float64:
+            L.check(L.lib().uni_corr_softmax_pv_lse_f64(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(out), L.ptr(lse), B, R, Q, D, K, 0 if shared else 1,
+                                                        L.stream_ptr()), "uni_corr_softmax_pv_lse_f64")
+        else:
+            ws = _corr_scratch(er.device, L.lib().uni_corr_bwd_workspace_bytes(B, R, Q, K))
+            L.check(L.lib().uni_corr_softmax_pv_lse(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(out), L.ptr(lse), B, R, Q, D, K, 0 if shared else 1,
+                                                    int(precision), L.ptr(ws), ws.numel(), L.stream_ptr()), "uni_corr_softmax_pv_lse")
+    return out, lse
+
+
+def corr_softmax_pv_backward(embed_ref, embed_cur, values, out, lse, grad_out, need=(True, True, True), precision=0):
+    """`uni_corr_softmax_pv_bwd`: (grad_embed_ref, grad_embed_cur, grad_values) for the tensors of corr_softmax_pv_lse; with shared (K,R)
+    values grad_values is (K,R), summed over the frames.  An entry of `need` that is False is not computed (None).  One writer per output
+    element: bitwise reproducible."""
+    shared = values.dim() == 2
+    er, ec, v, o, g = _corr_train_args("corr_softmax_pv_backward", embed_ref, embed_cur,
+                                       values.unsqueeze(0).expand(embed_ref.shape[0], -1, -1) if shared and embed_ref.dim() == 3 else values,
+                                       out, grad_out)
+    if shared:
+        v = values.contiguous()
+    B, R, D = er.shape
+    Q, K = ec.shape[1], v.shape[-2]
+    if lse.shape != (B, Q) or lse.dtype != er.dtype:
+        raise L.UnicornHipError("corr_softmax_pv_backward: lse %s %s is not (B,Q) = (%d, %d) %s" % (tuple(lse.shape), lse.dtype, B, Q, er.dtype))
+    _need_cuda(lse)
+    lse = lse.contiguous()
+    ger = torch.empty_like(er) if need[0] else None
+    gec = torch.empty_like(ec) if need[1] else None
+    gv = torch.empty_like(v) if need[2] else None
+    with torch.cuda.device(er.device):
+        if er.dtype == torch.float64:
+            L.check(L.lib().uni_corr_softmax_pv_bwd_f64(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(o), L.ptr(lse), L.ptr(g), L.ptr(ger), L.ptr(gec),
+                                                        L.ptr(gv), B, R, Q, D, K, 0 if shared else 1, L.stream_ptr()), "uni_corr_softmax_pv_bwd_f64")
+        else:
+            ws = _corr_scratch(er.device, L.lib().uni_corr_bwd_workspace_bytes(B, R, Q, K))
+            L.check(L.lib().uni_corr_softmax_pv_bwd(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(o), L.ptr(lse), L.ptr(g), L.ptr(ger), L.ptr(gec),
+                                                    L.ptr(gv), B, R, Q, D, K, 0 if shared else 1, int(precision), L.ptr(ws), ws.numel(), L.stream_ptr()),
+                    "uni_corr_softmax_pv_bwd")
+    return ger, gec, gv
+
+
+class CorrSoftmaxPVFunction(torch.autograd.Function):
+    """values @ softmax(embed_ref embed_cur^T, dim = reference axis) per frame, differentiable, in O(R + Q) memory:
+    apply(embed_ref (B,R,128), embed_cur (B,Q,128), values (B,K,R), precision=0) -> (B,K,Q); fp32 or fp64 device tensors.
+    The training form of unicorn/models/unicorn.py:321-326; saves `out` and `lse`, the backward recomputes the probabilities tile by tile."""
+
+    @staticmethod
+    def forward(ctx, embed_ref, embed_cur, values, precision=0):
+        er, ec, v = _corr_train_args("CorrSoftmaxPVFunction", embed_ref, embed_cur, values)
+        if precision != 0 and er.dtype == torch.float32 and any(ctx.needs_input_grad[:3]):
+            raise L.UnicornHipError("CorrSoftmaxPVFunction: the backward exists in precision 0 (exact fp32) only, got precision %r" % (precision,))
+        out, lse = corr_softmax_pv_lse(er, ec, v, precision)
+        ctx.save_for_backward(er, ec, v, out, lse)
+        ctx.precision = precision
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        er, ec, v, out, lse = ctx.saved_tensors
+        ger, gec, gv = corr_softmax_pv_backward(er, ec, v, out, lse, grad_out.contiguous(), ctx.needs_input_grad[:3], ctx.precision)
+        return ger, gec, gv, None
+
+
+def propagate_labels(embed_0, embed_1, labels, precision=0):
+    """The label propagation of the reference's training losses (unicorn/models/unicorn.py:321-326, 342-371) without the HW x HW matrices:
+    embed_* (B, C, H, W) or (B, C, HW) (any strides), labels (B, K, HW_0) -> (B, K, HW_1), equal in value and in gradient to
+        torch.bmm(labels, torch.softmax(torch.bmm(embed_0.flatten(-2).transpose(-1, -2), embed_1.flatten(-2)), dim=1)).
+    The layout changes are ordinary torch ops, so autograd carries the gradients back to the callers' layouts."""
+    if embed_0.dim() not in (3, 4) or embed_1.dim() not in (3, 4):
+        raise L.UnicornHipError("propagate_labels: embeddings must be (B, C, H, W) or (B, C, HW), got %s, %s" % (tuple(embed_0.shape), tuple(embed_1.shape)))
+    e0 = embed_0.flatten(2).transpose(1, 2)
+    e1 = embed_1.flatten(2).transpose(1, 2)
+    return CorrSoftmaxPVFunction.apply(e0, e1, labels, precision)
+
+
 def prior_pyramid(coarse):
     """(1,K,H8,W8) -> (coarse, 1/2, 1/4) like unicorn_sot.py:103-105"""
     _need_cuda(coarse)
