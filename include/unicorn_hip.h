@@ -222,6 +222,34 @@ int uni_sample_embeddings(const float* embed_nhwc, int H8, int W8, int C, const 
 int uni_condinst_masks(const float* mask_feats, const float* up_masks, const float* params, int ldp,
                        const float* inst_loc, const int32_t* inst_lvl, int n, int H8, int W8, int up_rate, int d_rate,
                        float* out, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+/* The CondInst mask loss for TRAINING (unicorn/models/condinst/dynamic_mask_head.py:247-278 with :138-170, :172-225 and dice_coefficient
+ * :50-58; called per image on the SimOTA foreground anchors by unicorn_head_mask.py:676-694): the arguments of uni_condinst_masks plus
+ * gt [n][r H8][r W8] (0 / 1 maps in the floating type) -> loss [n] = 1 - 2 I / U per instance, sums [n][3] = (I = sum s g, sum s^2,
+ * sum g^2), U = sum s^2 + sum g^2 + 1e-5, s = sigmoid of the x r convex-upsampled logits.  No n x rH8 x rW8 map is ever stored.
+ *   uni_condinst_loss_bwd  given grad_loss [n] and the forward's sums, recomputes s from the coarse logits and writes
+ *                            grad_mask_feats [H8][W8][8], grad_up_masks [H8][W8][9 r r], grad_params [n] rows of pitch ldp (169 columns
+ *                            written).  Each may be NULL: that gradient is not computed.  inst_loc / inst_lvl / gt carry no gradient.
+ *                            One writer per element, fixed summation orders, no atomics: bitwise reproducible, completely written.
+ * inst_lvl outside 0..4 is clamped to that range (the reference's index into sizes_of_interest would fail instead).
+ * up_rate 1..16, n <= 65535, H8 W8 r r < 2^30 (uni_condinst_loss_workspace_bytes returns 0 for shapes the calls refuse).
+ * workspace: device scratch of >= uni_condinst_loss_workspace_bytes bytes (fp32; the _f64 forms need twice that),
+ * 8-byte aligned, O(n H8 W8); nothing is kept in it between the two calls.  n must be > 0.  The _f64 pair is the same templated
+ * code in double precision, for gradcheck and fixtures. */
+size_t uni_condinst_loss_workspace_bytes(int n, int H8, int W8, int up_rate);
+int uni_condinst_loss_fwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const float* inst_loc,
+                          const int32_t* inst_lvl, const float* gt, int n, int H8, int W8, int up_rate, float* loss, float* sums,
+                          void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_condinst_loss_bwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const float* inst_loc,
+                          const int32_t* inst_lvl, const float* gt, const float* sums, const float* grad_loss, int n, int H8, int W8,
+                          int up_rate, float* grad_mask_feats, float* grad_up_masks, float* grad_params, void* workspace,
+                          size_t workspace_bytes, uni_stream_t stream);
+int uni_condinst_loss_fwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const double* inst_loc,
+                              const int32_t* inst_lvl, const double* gt, int n, int H8, int W8, int up_rate, double* loss, double* sums,
+                              void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_condinst_loss_bwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const double* inst_loc,
+                              const int32_t* inst_lvl, const double* gt, const double* sums, const double* grad_loss, int n, int H8,
+                              int W8, int up_rate, double* grad_mask_feats, double* grad_up_masks, double* grad_params, void* workspace,
+                              size_t workspace_bytes, uni_stream_t stream);
 
 /* Input letterbox on the device (row 0 / N1): PreprocessorX.process (external/lib/test/tracker/unicorn_sot.py:111-123,
  * swap_rb = 1) and preproc (unicorn/data/data_augment.py:194-214, swap_rb = 0).  img_hwc: (h, w, 3) uint8 DEVICE buffer;

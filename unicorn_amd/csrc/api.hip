@@ -301,6 +301,40 @@ int uni_condinst_masks(const float* mask_feats, const float* up_masks, const flo
     a.out = out;
     API(launch_condinst(a, S(stream)));
 }
+size_t uni_condinst_loss_workspace_bytes(int n, int H8, int W8, int up_rate) { return condinst_loss_workspace_bytes(n, H8, W8, up_rate); }
+int uni_condinst_loss_fwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const float* inst_loc,
+                          const int32_t* inst_lvl, const float* gt, int n, int H8, int W8, int up_rate, float* loss, float* sums,
+                          void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && loss && sums && workspace, "condinst_loss_fwd: NULL argument");
+    API(launch_condinst_loss_fwd(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, n, H8, W8, up_rate, loss, sums, workspace,
+                                 workspace_bytes, S(stream)));
+}
+int uni_condinst_loss_bwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const float* inst_loc,
+                          const int32_t* inst_lvl, const float* gt, const float* sums, const float* grad_loss, int n, int H8, int W8,
+                          int up_rate, float* grad_mask_feats, float* grad_up_masks, float* grad_params, void* workspace,
+                          size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && sums && grad_loss && workspace,
+                "condinst_loss_bwd: NULL argument");
+    API(launch_condinst_loss_bwd(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, sums, grad_loss, n, H8, W8, up_rate, grad_mask_feats,
+                                 grad_up_masks, grad_params, workspace, workspace_bytes, S(stream)));
+}
+int uni_condinst_loss_fwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const double* inst_loc,
+                              const int32_t* inst_lvl, const double* gt, int n, int H8, int W8, int up_rate, double* loss, double* sums,
+                              void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && loss && sums && workspace,
+                "condinst_loss_fwd_f64: NULL argument");
+    API(launch_condinst_loss_fwd_f64(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, n, H8, W8, up_rate, loss, sums, workspace,
+                                     workspace_bytes, S(stream)));
+}
+int uni_condinst_loss_bwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const double* inst_loc,
+                              const int32_t* inst_lvl, const double* gt, const double* sums, const double* grad_loss, int n, int H8, int W8,
+                              int up_rate, double* grad_mask_feats, double* grad_up_masks, double* grad_params, void* workspace,
+                              size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && sums && grad_loss && workspace,
+                "condinst_loss_bwd_f64: NULL argument");
+    API(launch_condinst_loss_bwd_f64(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, sums, grad_loss, n, H8, W8, up_rate,
+                                     grad_mask_feats, grad_up_masks, grad_params, workspace, workspace_bytes, S(stream)));
+}
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

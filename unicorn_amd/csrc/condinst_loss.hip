@@ -1,0 +1,504 @@
+// Fused CondInst mask loss for TRAINING (condinst/dynamic_mask_head.py:138-170 mask_heads_forward / upsample_preds, :172-225
+// mask_heads_forward_with_coords, :247-278 the dice loss of __call__; dice_coefficient :50-58), forward and a recomputing backward.
+//
+//   in = [rel_x, rel_y, mask_feats(8)]   h0 = relu(W0 in + b0)   h1 = relu(W1 h0 + b1)   L = W2 h1 + b2        (per instance, per coarse pixel)
+//   u[n, r y + i, r x + j] = sum_t w_t[y, x, i, j] Lpad[n, (y, x) + delta_t],  w = softmax_t(up_masks)           (convex upsample x r)
+//   s = sigmoid(u)   I = sum s g   U = sum s^2 + sum g^2 + 1e-5   loss_n = 1 - 2 I / U
+//
+// Nothing of size n x rH x rW is ever stored: the forward keeps three sums per instance, the backward recomputes s from the coarse logits.
+// Every output element has ONE writer and every sum a fixed order (no float atomics): results are bitwise reproducible.
+//
+//   forward   cl_mlp_kernel      logits[n][HW]                                         thread = (instance, coarse pixel)
+//             cl_dice_kernel     block partials of (sum s g, sum s^2, sum g^2)         thread = fine pixel x CL_IC instances (tap weights once)
+//             cl_dice_final      partials -> sums[n][3], loss[n]                       block = instance, fixed-order tree
+//   backward  cl_mlp_kernel      logits again (the workspace is scratch between calls)
+//             per chunk of CL_CH instances, in stream order:
+//               cl_du_kernel     du = gout (-2 g / U + 4 I s / U^2) s (1 - s) per fine pixel; d up_masks += du w_t (L_t - u) (the thread owns its
+//                                element over ALL instances: chunk c adds to what chunk c - 1 left); A[k][p][t] = sum_sub w_t du  (LDS, fixed order)
+//               cl_gather_kernel dL[n][q] = sum_t A[k][q - delta_t][t]                    the 9 x r r contributions that read q, one writer
+//             cl_dparams_kernel  recompute h0 / h1, one half of the 169 accumulators per thread over its pixels (blockIdx.z), wave + block
+//                                reduction -> partials
+//             cl_dparams_final   partials -> grad_params[n][169]
+//             cl_dfeat_kernel    thread = coarse pixel, loops the instances of a chunk -> partials;  cl_dfeat_final adds the chunks in order
+//
+// The chunked A buffer (CL_CH x HW x 9) keeps the workspace at O(n HW) with a small constant instead of 9 x the logits.
+#include "kernels.h"
+
+namespace {
+
+constexpr int CL_NP = 169;     // 80 | 64 | 8 | 8 | 8 | 1 (parse_dynamic_params)
+constexpr int CL_IC = 8;       // forward: instances per thread (the tap softmax does not depend on the instance, misc.hip CU_IC)
+constexpr int CL_CH = 16;      // backward: instances per chunk launch
+constexpr int CL_PPT = 4;      // cl_dparams_kernel: coarse pixels per thread
+constexpr int CL_FB = 128;     // cl_dfeat_kernel block
+
+template <typename T> __device__ __forceinline__ T cl_exp(T x);
+template <> __device__ __forceinline__ float cl_exp<float>(float x) { return expf(x); }        // accurate: this path is differentiated
+template <> __device__ __forceinline__ double cl_exp<double>(double x) { return exp(x); }
+
+// Thread mapping of the fine-pixel kernels: a block owns PX consecutive coarse pixels; tid = i (PX r) + xl r + j, so a wave reads contiguous
+// ground-truth rows (r = 4: 64 consecutive floats).
+__device__ __forceinline__ void cl_map(int r, int PX, int HWc, int& pix, int& i, int& j, int& xl, bool& valid) {
+    const int span = PX * r, tid = threadIdx.x;
+    i = tid / span;
+    const int rem = tid - i * span;
+    xl = rem / r;
+    j = rem - xl * r;
+    pix = blockIdx.x * PX + xl;
+    valid = tid < span * r && pix < HWc;
+}
+
+template <typename T>
+__device__ __forceinline__ void cl_inputs(const T* __restrict__ mask_feats, const T* __restrict__ inst_loc, const int* __restrict__ inst_lvl,
+                                          int inst, int pix, int W, T in[10]) {
+    const T soi_tab[5] = {(T)64, (T)128, (T)256, (T)512, (T)1024};
+    const T soi = soi_tab[min(max(inst_lvl[inst], 0), 4)];
+    const int y = pix / W, x = pix - y * W;
+    in[0] = (inst_loc[inst * 2] - (T)(x * 8 + 4)) / soi;       // comm.py:30-43 locations = arange * 8 + 4
+    in[1] = (inst_loc[inst * 2 + 1] - (T)(y * 8 + 4)) / soi;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in[2 + c] = mask_feats[(size_t)pix * 8 + c];
+}
+
+// condinst_mlp_kernel's arithmetic (misc.hip), keeping the hidden activations
+template <typename T>
+__device__ __forceinline__ T cl_mlp(const T* prm, const T in[10], T h0[8], T h1[8]) {
+    const T *w0 = prm, *w1 = prm + 80, *w2 = prm + 144, *b0 = prm + 152, *b1 = prm + 160, *b2 = prm + 168;
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        T s = b0[o];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) s += w0[o * 10 + i] * in[i];
+        h0[o] = s > (T)0 ? s : (T)0;
+    }
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        T s = b1[o];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += w1[o * 8 + i] * h0[i];
+        h1[o] = s > (T)0 ? s : (T)0;
+    }
+    T s = b2[0];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s += w2[i] * h1[i];
+    return s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cl_mlp_kernel(const T* __restrict__ mask_feats, const T* __restrict__ params, int ldp,
+                                                     const T* __restrict__ inst_loc, const int* __restrict__ inst_lvl, int HWc, int W,
+                                                     T* __restrict__ logits) {
+    __shared__ T prm[CL_NP];
+    const int inst = blockIdx.y;
+    for (int i = threadIdx.x; i < CL_NP; i += blockDim.x) prm[i] = params[(size_t)inst * ldp + i];
+    __syncthreads();
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= HWc) return;
+    T in[10], h0[8], h1[8];
+    cl_inputs(mask_feats, inst_loc, inst_lvl, inst, pix, W, in);
+    logits[(size_t)inst * HWc + pix] = cl_mlp(prm, in, h0, h1);
+}
+
+// normalised tap weights of one fine pixel and the (zero-padded) neighbour offsets of its coarse pixel
+template <typename T>
+__device__ __forceinline__ void cl_taps(const T* __restrict__ up_masks, int pix, int sub, int rr, int H, int W, bool valid, T wt[9], int off[9]) {
+    if (!valid) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t) { wt[t] = (T)0; off[t] = -1; }
+        return;
+    }
+    const T* um = up_masks + (size_t)pix * 9 * rr + sub;
+    const int y = pix / W, x = pix - y * W;
+    T mx = um[0];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) { wt[t] = um[t * rr]; mx = wt[t] > mx ? wt[t] : mx; }
+    T sum = (T)0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        wt[t] = cl_exp<T>(wt[t] - mx);
+        sum += wt[t];
+        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+        off[t] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? yy * W + xx : -1;
+    }
+    const T inv = (T)1 / sum;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) wt[t] *= inv;
+}
+
+template <typename T>
+__device__ __forceinline__ T cl_wave_sum(T v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cl_dice_kernel(const T* __restrict__ up_masks, const T* __restrict__ logits, const T* __restrict__ gt,
+                                                      T* __restrict__ part, int n, int H, int W, int r, int PX, int nblk) {
+    __shared__ T red[4][3 * CL_IC];
+    const int rr = r * r, HWc = H * W;
+    int pix, i, j, xl;
+    bool valid;
+    cl_map(r, PX, HWc, pix, i, j, xl, valid);
+    T wt[9];
+    int off[9];
+    cl_taps(up_masks, pix, i * r + j, rr, H, W, valid, wt, off);
+    const int y = pix / W, x = pix - y * W;
+    const size_t fine = (size_t)(r * y + i) * (r * W) + r * x + j, fsz = (size_t)HWc * rr;
+    const int i0 = blockIdx.y * CL_IC, cnt = min(n - i0, CL_IC);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = 0; k < cnt; ++k) {
+        T sg = (T)0, ss = (T)0, gg = (T)0;
+        if (valid) {
+            const T* L = logits + (size_t)(i0 + k) * HWc;
+            T u = (T)0;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) u += wt[t] * (off[t] >= 0 ? L[off[t]] : (T)0);
+            const T s = (T)1 / ((T)1 + cl_exp<T>(-u));
+            const T g = gt[(size_t)(i0 + k) * fsz + fine];
+            sg = s * g; ss = s * s; gg = g * g;
+        }
+        sg = cl_wave_sum(sg); ss = cl_wave_sum(ss); gg = cl_wave_sum(gg);
+        if (lane == 0) { red[wave][3 * k] = sg; red[wave][3 * k + 1] = ss; red[wave][3 * k + 2] = gg; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 3 * cnt) {
+        const int t = threadIdx.x;
+        part[((size_t)(i0 + t / 3) * nblk + blockIdx.x) * 3 + t % 3] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cl_dice_final(const T* __restrict__ part, int nblk, T* __restrict__ sums, T* __restrict__ loss) {
+    __shared__ T red[3][256];
+    const int inst = blockIdx.x, tid = threadIdx.x;
+    T a[3] = {(T)0, (T)0, (T)0};
+    for (int b = tid; b < nblk; b += 256) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a[c] += part[((size_t)inst * nblk + b) * 3 + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) red[c][tid] = a[c];
+    __syncthreads();
+    for (int d = 128; d >= 1; d >>= 1) {
+        if (tid < d) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) red[c][tid] += red[c][tid + d];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const T I = red[0][0], U = red[1][0] + red[2][0] + (T)1e-5;
+        sums[inst * 3] = I; sums[inst * 3 + 1] = red[1][0]; sums[inst * 3 + 2] = red[2][0];
+        loss[inst] = (T)1 - (T)2 * I / U;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cl_du_kernel(const T* __restrict__ up_masks, const T* __restrict__ logits, const T* __restrict__ gt,
+                                                    const T* __restrict__ sums, const T* __restrict__ gout, T* __restrict__ A,
+                                                    T* __restrict__ grad_um, int c0, int cnt, int H, int W, int r, int PX, int want_dl) {
+    __shared__ T cs[9][256];
+    const int rr = r * r, HWc = H * W;
+    int pix, i, j, xl;
+    bool valid;
+    cl_map(r, PX, HWc, pix, i, j, xl, valid);
+    T wt[9], acc[9];
+    int off[9];
+    cl_taps(up_masks, pix, i * r + j, rr, H, W, valid, wt, off);
+    const int y = pix / W, x = pix - y * W;
+    const size_t fine = (size_t)(r * y + i) * (r * W) + r * x + j, fsz = (size_t)HWc * rr;
+    T* gum = grad_um ? grad_um + (size_t)pix * 9 * rr + i * r + j : nullptr;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] = (gum && valid && c0 > 0) ? gum[t * rr] : (T)0;
+    const int span = PX * r, pix0 = blockIdx.x * PX;
+    for (int k = 0; k < cnt; ++k) {
+        const int inst = c0 + k;
+        const T I = sums[inst * 3], U = sums[inst * 3 + 1] + sums[inst * 3 + 2] + (T)1e-5, go = gout[inst];
+        const T ca = (T)-2 * go / U, cb = (T)4 * go * I / (U * U);
+        T c[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) c[t] = (T)0;
+        if (valid) {
+            const T* L = logits + (size_t)inst * HWc;
+            T Lt[9], u = (T)0;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) { Lt[t] = off[t] >= 0 ? L[off[t]] : (T)0; u += wt[t] * Lt[t]; }
+            const T s = (T)1 / ((T)1 + cl_exp<T>(-u));
+            const T g = gt[(size_t)inst * fsz + fine];
+            const T du = (ca * g + cb * s) * (s * ((T)1 - s));
+#pragma unroll
+            for (int t = 0; t < 9; ++t) { c[t] = wt[t] * du; acc[t] += c[t] * (Lt[t] - u); }
+        }
+        if (want_dl) {
+#pragma unroll
+            for (int t = 0; t < 9; ++t) cs[t][threadIdx.x] = c[t];
+            __syncthreads();
+            for (int o = threadIdx.x; o < PX * 9; o += 256) {
+                const int pl = o / 9, t = o - pl * 9;
+                if (pix0 + pl < HWc) {
+                    T s = (T)0;
+                    for (int ii = 0; ii < r; ++ii)
+                        for (int jj = 0; jj < r; ++jj) s += cs[t][ii * span + pl * r + jj];
+                    A[((size_t)k * HWc + pix0 + pl) * 9 + t] = s;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (gum && valid) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t) gum[t * rr] = acc[t];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cl_gather_kernel(const T* __restrict__ A, T* __restrict__ dL, int c0, int H, int W) {
+    const int HWc = H * W, q = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (q >= HWc) return;
+    const int y = q / W, x = q - y * W;
+    T s = (T)0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {      // the coarse pixel p whose tap t reads q: p + delta_t = q
+        const int yy = y - (t / 3 - 1), xx = x - (t % 3 - 1);
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) s += A[((size_t)k * HWc + yy * W + xx) * 9 + t];
+    }
+    dL[(size_t)(c0 + k) * HWc + q] = s;
+}
+
+// parameter columns of the two halves the parameter-gradient kernel is split into (169 accumulators per thread do not fit the register
+// file next to the recomputation): half 0 = W0 | b0 (88 columns), half 1 = W1 | W2 | b1 | b2 (81 columns)
+__device__ __forceinline__ constexpr bool cl_in_half(int half, int i) { return ((i < 80 || (i >= 152 && i < 160)) ? 0 : 1) == half; }
+
+// backward of the three layers at one pixel: accumulates the parameter gradients of one half (HALF 0 / 1; gp[169], the other half's entries
+// are never touched) or returns d in[2..9] (HALF < 0, dmf)
+template <typename T, int HALF>
+__device__ __forceinline__ void cl_mlp_bwd(const T* prm, const T in[10], T dLv, T* gp, T* dmf) {
+    const T *w0 = prm, *w1 = prm + 80, *w2 = prm + 144;
+    T h0[8], h1[8], dh1[8], dh0[8];
+    cl_mlp(prm, in, h0, h1);
+#pragma unroll
+    for (int o = 0; o < 8; ++o) dh1[o] = h1[o] > (T)0 ? dLv * w2[o] : (T)0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        T s = (T)0;
+#pragma unroll
+        for (int o = 0; o < 8; ++o) s += w1[o * 8 + i] * dh1[o];
+        dh0[i] = h0[i] > (T)0 ? s : (T)0;
+    }
+    if (HALF == 0) {
+#pragma unroll
+        for (int o = 0; o < 8; ++o) {
+#pragma unroll
+            for (int i = 0; i < 10; ++i) gp[o * 10 + i] += dh0[o] * in[i];
+            gp[152 + o] += dh0[o];
+        }
+    }
+    if (HALF == 1) {
+#pragma unroll
+        for (int o = 0; o < 8; ++o) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) gp[80 + o * 8 + i] += dh1[o] * h0[i];
+            gp[144 + o] += dLv * h1[o];
+            gp[160 + o] += dh1[o];
+        }
+        gp[168] += dLv;
+    }
+    if (HALF < 0) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            T s = (T)0;
+#pragma unroll
+            for (int o = 0; o < 8; ++o) s += w0[o * 10 + 2 + c] * dh0[o];
+            dmf[c] += s;
+        }
+    }
+}
+
+template <typename T, int HALF>
+__device__ __forceinline__ void cl_dparams_half(const T* prm, T (*red)[CL_NP], const T* __restrict__ mask_feats, const T* __restrict__ inst_loc,
+                                                const int* __restrict__ inst_lvl, const T* __restrict__ dL, int HWc, int W, T* __restrict__ part,
+                                                int nblk) {
+    const int inst = blockIdx.y, tid = threadIdx.x;
+    T gp[CL_NP];
+#pragma unroll
+    for (int i = 0; i < CL_NP; ++i) gp[i] = (T)0;
+    for (int k = 0; k < CL_PPT; ++k) {
+        const int pix = (blockIdx.x * CL_PPT + k) * 256 + tid;
+        if (pix < HWc) {
+            T in[10];
+            cl_inputs(mask_feats, inst_loc, inst_lvl, inst, pix, W, in);
+            cl_mlp_bwd<T, HALF>(prm, in, dL[(size_t)inst * HWc + pix], gp, nullptr);
+        }
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int i = 0; i < CL_NP; ++i) {
+        if (cl_in_half(HALF, i)) {
+            const T v = cl_wave_sum(gp[i]);
+            if (lane == 0) red[wave][i] = v;
+        }
+    }
+    __syncthreads();
+    if (tid < CL_NP && cl_in_half(HALF, tid))
+        part[((size_t)inst * nblk + blockIdx.x) * CL_NP + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cl_dparams_kernel(const T* __restrict__ mask_feats, const T* __restrict__ params, int ldp,
+                                                         const T* __restrict__ inst_loc, const int* __restrict__ inst_lvl,
+                                                         const T* __restrict__ dL, int HWc, int W, T* __restrict__ part, int nblk) {
+    __shared__ T prm[CL_NP];
+    __shared__ T red[4][CL_NP];
+    for (int i = threadIdx.x; i < CL_NP; i += 256) prm[i] = params[(size_t)blockIdx.y * ldp + i];
+    __syncthreads();
+    if (blockIdx.z == 0) cl_dparams_half<T, 0>(prm, red, mask_feats, inst_loc, inst_lvl, dL, HWc, W, part, nblk);
+    else cl_dparams_half<T, 1>(prm, red, mask_feats, inst_loc, inst_lvl, dL, HWc, W, part, nblk);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cl_dparams_final(const T* __restrict__ part, int nblk, T* __restrict__ grad_params, int ldp) {
+    const int inst = blockIdx.x, tid = threadIdx.x;
+    if (tid >= CL_NP) return;
+    T s = (T)0;
+    for (int b = 0; b < nblk; ++b) s += part[((size_t)inst * nblk + b) * CL_NP + tid];
+    grad_params[(size_t)inst * ldp + tid] = s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(CL_FB) void cl_dfeat_kernel(const T* __restrict__ mask_feats, const T* __restrict__ params, int ldp,
+                                                          const T* __restrict__ inst_loc, const int* __restrict__ inst_lvl,
+                                                          const T* __restrict__ dL, int n, int HWc, int W, T* __restrict__ part) {
+    __shared__ T prm[CL_NP];
+    const int pix = blockIdx.x * CL_FB + threadIdx.x, c0 = blockIdx.y * CL_CH, cnt = min(n - c0, CL_CH);
+    const bool valid = pix < HWc;
+    T dmf[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) dmf[c] = (T)0;
+    for (int k = 0; k < cnt; ++k) {
+        const int inst = c0 + k;
+        __syncthreads();
+        for (int i = threadIdx.x; i < CL_NP; i += CL_FB) prm[i] = params[(size_t)inst * ldp + i];
+        __syncthreads();
+        if (valid) {
+            T in[10];
+            cl_inputs(mask_feats, inst_loc, inst_lvl, inst, pix, W, in);
+            cl_mlp_bwd<T, -1>(prm, in, dL[(size_t)inst * HWc + pix], nullptr, dmf);
+        }
+    }
+    if (valid) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) part[((size_t)blockIdx.y * HWc + pix) * 8 + c] = dmf[c];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cl_dfeat_final(const T* __restrict__ part, int nchunk, int HWc, T* __restrict__ grad_mf) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= HWc * 8) return;
+    T s = (T)0;
+    for (int c = 0; c < nchunk; ++c) s += part[(size_t)c * HWc * 8 + e];
+    grad_mf[e] = s;
+}
+
+// workspace layout, in elements of T
+struct CLLayout {
+    size_t logits, dL, dice, A, pp, pf, total;
+    int PX, nblk_d, nblk_p, nchunk;
+};
+CLLayout cl_layout(int n, int H, int W, int r) {
+    CLLayout l;
+    const size_t hw = (size_t)H * W;
+    l.PX = 256 / (r * r);
+    l.nblk_d = cdiv(H * W, l.PX);
+    l.nblk_p = cdiv(H * W, 256 * CL_PPT);
+    l.nchunk = cdiv(n, CL_CH);
+    size_t o = 0;
+    l.logits = o; o += (size_t)n * hw;
+    l.dL = o;     o += (size_t)n * hw;
+    l.dice = o;   o += (size_t)n * l.nblk_d * 3;
+    l.A = o;      o += (size_t)(n < CL_CH ? n : CL_CH) * hw * 9;
+    l.pp = o;     o += (size_t)n * l.nblk_p * CL_NP;
+    l.pf = o;     o += (size_t)l.nchunk * hw * 8;
+    l.total = o;
+    return l;
+}
+
+int cl_check(const char* what, int n, int H, int W, int r, int ldp, const void* ws, size_t ws_bytes, size_t esize) {
+    UNI_REQUIRE(n > 0 && H > 0 && W > 0, "%s: empty problem n=%d H8=%d W8=%d", what, n, H, W);
+    UNI_REQUIRE(r >= 1 && r <= 16, "%s: up_rate %d unsupported (1..16)", what, r);
+    UNI_REQUIRE(ldp >= CL_NP, "%s: ldp %d < 169", what, ldp);
+    UNI_REQUIRE(n <= 65535, "%s: more than 65535 instances", what);
+    UNI_REQUIRE((size_t)H * W * r * r < (size_t)1 << 30, "%s: map too large", what);
+    const size_t need = cl_layout(n, H, W, r).total * esize;
+    UNI_REQUIRE(ws && ((uintptr_t)ws & 7) == 0 && ws_bytes >= need, "%s: workspace %zu < %zu bytes or misaligned", what, ws_bytes, need);
+    return 0;
+}
+
+template <typename T>
+int cl_fwd(const T* mf, const T* um, const T* params, int ldp, const T* loc, const int* lvl, const T* gt, int n, int H, int W, int r, T* loss,
+           T* sums, void* workspace, size_t ws_bytes, hipStream_t s) {
+    if (int rc = cl_check("condinst_loss_fwd", n, H, W, r, ldp, workspace, ws_bytes, sizeof(T))) return rc;
+    const CLLayout l = cl_layout(n, H, W, r);
+    T* ws = reinterpret_cast<T*>(workspace);
+    const int hw = H * W;
+    hipLaunchKernelGGL(cl_mlp_kernel<T>, dim3(cdiv(hw, 256), n), dim3(256), 0, s, mf, params, ldp, loc, lvl, hw, W, ws + l.logits);
+    hipLaunchKernelGGL(cl_dice_kernel<T>, dim3(l.nblk_d, cdiv(n, CL_IC)), dim3(256), 0, s, um, ws + l.logits, gt, ws + l.dice, n, H, W, r, l.PX,
+                       l.nblk_d);
+    hipLaunchKernelGGL(cl_dice_final<T>, dim3(n), dim3(256), 0, s, ws + l.dice, l.nblk_d, sums, loss);
+    return 0;
+}
+
+template <typename T>
+int cl_bwd(const T* mf, const T* um, const T* params, int ldp, const T* loc, const int* lvl, const T* gt, const T* sums, const T* gout, int n,
+           int H, int W, int r, T* gmf, T* gum, T* gpar, void* workspace, size_t ws_bytes, hipStream_t s) {
+    if (int rc = cl_check("condinst_loss_bwd", n, H, W, r, ldp, workspace, ws_bytes, sizeof(T))) return rc;
+    if (!gmf && !gum && !gpar) return 0;
+    const CLLayout l = cl_layout(n, H, W, r);
+    T* ws = reinterpret_cast<T*>(workspace);
+    const int hw = H * W, want_dl = (gmf || gpar) ? 1 : 0;
+    hipLaunchKernelGGL(cl_mlp_kernel<T>, dim3(cdiv(hw, 256), n), dim3(256), 0, s, mf, params, ldp, loc, lvl, hw, W, ws + l.logits);
+    for (int c0 = 0; c0 < n; c0 += CL_CH) {
+        const int cnt = n - c0 < CL_CH ? n - c0 : CL_CH;
+        hipLaunchKernelGGL(cl_du_kernel<T>, dim3(l.nblk_d), dim3(256), 0, s, um, ws + l.logits, gt, sums, gout, ws + l.A, gum, c0, cnt, H, W, r, l.PX,
+                           want_dl);
+        if (want_dl) hipLaunchKernelGGL(cl_gather_kernel<T>, dim3(cdiv(hw, 256), cnt), dim3(256), 0, s, ws + l.A, ws + l.dL, c0, H, W);
+    }
+    if (gpar) {
+        hipLaunchKernelGGL(cl_dparams_kernel<T>, dim3(l.nblk_p, n, 2), dim3(256), 0, s, mf, params, ldp, loc, lvl, ws + l.dL, hw, W, ws + l.pp, l.nblk_p);
+        hipLaunchKernelGGL(cl_dparams_final<T>, dim3(n), dim3(256), 0, s, ws + l.pp, l.nblk_p, gpar, ldp);
+    }
+    if (gmf) {
+        hipLaunchKernelGGL(cl_dfeat_kernel<T>, dim3(cdiv(hw, CL_FB), l.nchunk), dim3(CL_FB), 0, s, mf, params, ldp, loc, lvl, ws + l.dL, n, hw, W,
+                           ws + l.pf);
+        hipLaunchKernelGGL(cl_dfeat_final<T>, dim3(cdiv(hw * 8, 256)), dim3(256), 0, s, ws + l.pf, l.nchunk, hw, gmf);
+    }
+    return 0;
+}
+
+}  // namespace
+
+size_t condinst_loss_workspace_bytes(int n, int H, int W, int r) {
+    if (n <= 0 || H <= 0 || W <= 0 || r < 1 || r > 16 || n > 65535) return 0;
+    if ((size_t)H * W * r * r >= (size_t)1 << 30) return 0;          // the shapes cl_check refuses: H * W stays inside int below
+    return cl_layout(n, H, W, r).total * sizeof(float);
+}
+int launch_condinst_loss_fwd(const float* mf, const float* um, const float* params, int ldp, const float* loc, const int* lvl, const float* gt,
+                             int n, int H, int W, int r, float* loss, float* sums, void* ws, size_t ws_bytes, hipStream_t s) {
+    return cl_fwd<float>(mf, um, params, ldp, loc, lvl, gt, n, H, W, r, loss, sums, ws, ws_bytes, s);
+}
+int launch_condinst_loss_bwd(const float* mf, const float* um, const float* params, int ldp, const float* loc, const int* lvl, const float* gt,
+                             const float* sums, const float* gout, int n, int H, int W, int r, float* gmf, float* gum, float* gpar, void* ws,
+                             size_t ws_bytes, hipStream_t s) {
+    return cl_bwd<float>(mf, um, params, ldp, loc, lvl, gt, sums, gout, n, H, W, r, gmf, gum, gpar, ws, ws_bytes, s);
+}
+int launch_condinst_loss_fwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
+                                 const double* gt, int n, int H, int W, int r, double* loss, double* sums, void* ws, size_t ws_bytes,
+                                 hipStream_t s) {
+    return cl_fwd<double>(mf, um, params, ldp, loc, lvl, gt, n, H, W, r, loss, sums, ws, ws_bytes, s);
+}
+int launch_condinst_loss_bwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
+                                 const double* gt, const double* sums, const double* gout, int n, int H, int W, int r, double* gmf, double* gum,
+                                 double* gpar, void* ws, size_t ws_bytes, hipStream_t s) {
+    return cl_bwd<double>(mf, um, params, ldp, loc, lvl, gt, sums, gout, n, H, W, r, gmf, gum, gpar, ws, ws_bytes, s);
+}

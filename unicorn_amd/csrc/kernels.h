@@ -194,6 +194,22 @@ struct CondInstArgs {
 };
 int launch_condinst(const CondInstArgs& a, hipStream_t s);
 int launch_label_map_s8(const float* box_xyxy, float* out, int H, int W, hipStream_t s);
+// condinst_loss.hip: the CondInst dice loss for training (dynamic_mask_head.py:247-278), forward + recomputing backward, fp32 and fp64.
+// mf [H][W][8], um [H][W][9 r r], params [n][ldp >= 169], loc [n][2], lvl [n], gt [n][rH][rW] -> loss [n], sums [n][3] = (sum s g, sum s^2,
+// sum g^2).  The backward writes gmf [H][W][8], gum [H][W][9 r r], gpar [n][ldp] (169 columns); each may be NULL (not computed).
+// Workspace: condinst_loss_workspace_bytes for fp32, twice that for fp64; scratch between calls (the backward recomputes the logits).
+size_t condinst_loss_workspace_bytes(int n, int H, int W, int r);
+int launch_condinst_loss_fwd(const float* mf, const float* um, const float* params, int ldp, const float* loc, const int* lvl, const float* gt,
+                             int n, int H, int W, int r, float* loss, float* sums, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_condinst_loss_bwd(const float* mf, const float* um, const float* params, int ldp, const float* loc, const int* lvl, const float* gt,
+                             const float* sums, const float* gout, int n, int H, int W, int r, float* gmf, float* gum, float* gpar, void* ws,
+                             size_t ws_bytes, hipStream_t s);
+int launch_condinst_loss_fwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
+                                 const double* gt, int n, int H, int W, int r, double* loss, double* sums, void* ws, size_t ws_bytes,
+                                 hipStream_t s);
+int launch_condinst_loss_bwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
+                                 const double* gt, const double* sums, const double* gout, int n, int H, int W, int r, double* gmf, double* gum,
+                                 double* gpar, void* ws, size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

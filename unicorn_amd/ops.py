@@ -326,6 +326,90 @@ def condinst_masks(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate, d_
     return out
 
 
+_CL_ENTRY = {torch.float32: ("uni_condinst_loss_fwd", "uni_condinst_loss_bwd", 1),
+             torch.float64: ("uni_condinst_loss_fwd_f64", "uni_condinst_loss_bwd_f64", 2)}
+
+
+def _condinst_loss_ws(dev, dtype, n, H8, W8, r):
+    need = L.lib().uni_condinst_loss_workspace_bytes(n, H8, W8, r) * _CL_ENTRY[dtype][2]        # the fp64 forms need twice the fp32 size
+    return torch.empty(max(need, 8), device=dev, dtype=torch.uint8)
+
+
+class CondInstDiceFunction(torch.autograd.Function):
+    """The CondInst mask loss per instance (dynamic_mask_head.py:247-278) on the kernels' layouts, differentiable, in O(N H8 W8) memory:
+    apply(mask_feats (H8,W8,8), up_masks (H8,W8,9 r r), params (N,169), inst_loc (N,2), inst_lvl (N,) int32, gt (N,r H8,r W8), up_rate)
+    -> loss (N,); fp32 or fp64 contiguous device tensors (condinst_dice_loss checks and converts).  Saves the inputs and three sums per
+    instance; the backward recomputes the sigmoid scores from the coarse logits.  One writer per gradient element: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, mask_feats, up_masks, params, inst_loc, inst_lvl, gt, up_rate):
+        H8, W8, _ = mask_feats.shape
+        n, r = params.shape[0], int(up_rate)
+        fwd = _CL_ENTRY[params.dtype][0]
+        loss = torch.empty((n,), device=params.device, dtype=params.dtype)
+        sums = torch.empty((n, 3), device=params.device, dtype=params.dtype)
+        with torch.cuda.device(params.device):
+            ws = _condinst_loss_ws(params.device, params.dtype, n, H8, W8, r)
+            L.check(getattr(L.lib(), fwd)(L.ptr(mask_feats), L.ptr(up_masks), L.ptr(params), params.stride(0), L.ptr(inst_loc), L.ptr(inst_lvl),
+                                          L.ptr(gt), n, H8, W8, r, L.ptr(loss), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
+        ctx.save_for_backward(mask_feats, up_masks, params, inst_loc, inst_lvl, gt, sums)
+        ctx.up_rate = r
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        mf, um, p, loc, lvl, gt, sums = ctx.saved_tensors
+        H8, W8, _ = mf.shape
+        n, r = p.shape[0], ctx.up_rate
+        bwd = _CL_ENTRY[p.dtype][1]
+        g = grad_loss.contiguous()
+        gmf = torch.empty_like(mf) if ctx.needs_input_grad[0] else None
+        gum = torch.empty_like(um) if ctx.needs_input_grad[1] else None
+        gp = torch.empty((n, p.stride(0)), device=p.device, dtype=p.dtype)[:, :169] if ctx.needs_input_grad[2] else None      # rows of pitch ldp, like params
+        if gmf is not None or gum is not None or gp is not None:
+            with torch.cuda.device(p.device):
+                ws = _condinst_loss_ws(p.device, p.dtype, n, H8, W8, r)
+                L.check(getattr(L.lib(), bwd)(L.ptr(mf), L.ptr(um), L.ptr(p), p.stride(0), L.ptr(loc), L.ptr(lvl), L.ptr(gt), L.ptr(sums), L.ptr(g),
+                                              n, H8, W8, r, L.ptr(gmf), L.ptr(gum), L.ptr(gp), L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
+        return gmf, gum, gp, None, None, None, None
+
+
+def condinst_dice_loss(mask_feats, up_masks, params, inst_loc, inst_lvl, gt_bitmasks, up_rate):
+    """The training half of DynamicMaskHead.__call__ (dynamic_mask_head.py:247-278, fully supervised branch) in one call:
+    mask_feats (1,8,H8,W8), up_masks (1,9 r r,H8,W8), params (N,169), inst_loc (N,2), inst_lvl (N,), gt_bitmasks (N,1,r H8,r W8) or
+    (N,r H8,r W8) -> the (N,) per-instance dice losses; the reference's `loss_mask` is `.mean()` of it.  Equal in value and in gradient
+    (mask_feats, up_masks, params) to dice_coefficient(mask_heads_forward_with_coords(...).sigmoid(), gt_bitmasks), without any
+    (N, r H8, r W8) tensor.  All floating tensors fp32 or all fp64; the NCHW -> NHWC layout changes are ordinary torch ops, so autograd
+    carries the gradients back to the callers' layouts."""
+    ts = (mask_feats, up_masks, params, inst_loc, gt_bitmasks)
+    r = int(up_rate)
+    if mask_feats.dim() != 4 or up_masks.dim() != 4 or params.dim() != 2 or mask_feats.shape[0] != 1 or mask_feats.shape[1] != 8 \
+            or r < 1 or r > 16 or tuple(up_masks.shape) != (1, 9 * r * r) + tuple(mask_feats.shape[2:]) or params.shape[1] != 169 \
+            or tuple(inst_loc.shape) != (params.shape[0], 2) or tuple(inst_lvl.shape) != (params.shape[0],):
+        raise L.UnicornHipError("condinst_dice_loss: shapes %s, inst_lvl %s, up_rate %r do not fit mask_feats (1,8,H8,W8), up_masks (1,9 r r,H8,W8), "
+                                "params (N,169), inst_loc (N,2), inst_lvl (N,), up_rate 1..16"
+                                % ([tuple(t.shape) for t in ts], tuple(inst_lvl.shape), up_rate))
+    n, H8, W8 = params.shape[0], mask_feats.shape[2], mask_feats.shape[3]
+    if tuple(gt_bitmasks.shape) not in ((n, 1, r * H8, r * W8), (n, r * H8, r * W8)):
+        raise L.UnicornHipError("condinst_dice_loss: gt_bitmasks %s do not fit (N,1,r H8,r W8) = (%d, 1, %d, %d): the ground truth must be exactly "
+                                "up_rate x the feature map" % (tuple(gt_bitmasks.shape), n, r * H8, r * W8))
+    if params.dtype not in _CL_ENTRY or any(t.dtype != params.dtype for t in ts):
+        raise L.UnicornHipError("condinst_dice_loss: dtypes %s unsupported (all fp32 or all fp64)" % [str(t.dtype) for t in ts])
+    if inst_lvl.dtype.is_floating_point or inst_lvl.dtype == torch.bool:
+        raise L.UnicornHipError("condinst_dice_loss: inst_lvl must be an integer tensor, got %s" % inst_lvl.dtype)
+    _need_cuda(*ts, inst_lvl)
+    if n == 0:
+        return params.new_zeros((0,))
+    if H8 == 0 or W8 == 0:
+        raise L.UnicornHipError("condinst_dice_loss: empty feature map %s" % (tuple(mask_feats.shape),))
+    mf = mask_feats[0].permute(1, 2, 0).contiguous()
+    um = up_masks[0].permute(1, 2, 0).contiguous()
+    p = params if params.stride(1) == 1 and params.stride(0) >= 169 else params.contiguous()      # a row pitch (ldp) is passed through
+    return CondInstDiceFunction.apply(mf, um, p, inst_loc.detach().contiguous(), inst_lvl.to(torch.int32).contiguous(),
+                                      gt_bitmasks.detach().reshape(n, r * H8, r * W8).contiguous(), r)
+
+
 def condinst_masks_resized(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate, d_rate, r, H, W, thr=None):
     """condinst_masks + mask_resize in ONE call (uni_condinst_masks_u8): the CondInst scores of `params` resized by 1/r and pasted into
     (N, H, W) maps -- `> thr` bytes (mot_evaluator.py:804-805) or, with thr=None, fp32 probabilities (unicorn_vos.py:141-152) -- without the
