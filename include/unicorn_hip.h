@@ -250,6 +250,29 @@ int uni_condinst_loss_bwd_f64(const double* mask_feats, const double* up_masks, 
                               const int32_t* inst_lvl, const double* gt, const double* sums, const double* grad_loss, int n, int H8,
                               int W8, int up_rate, double* grad_mask_feats, double* grad_up_masks, double* grad_params, void* workspace,
                               size_t workspace_bytes, uni_stream_t stream);
+/* SimOTA label assignment of the head loss for a whole BATCH (unicorn/models/unicorn_head_mask.py:754-983: get_assignments,
+ * get_in_boxes_info, dynamic_k_matching, with bboxes_iou of unicorn/utils/boxes.py:154-177), fp32, in four launches whatever the number of
+ * boxes or images, without a host synchronisation and without any tensor of size boxes x anchors x classes.
+ *   outputs  [B][A] rows of pitch ld_out >= 5 + C: decoded cx, cy, w, h, then the objectness logit and C class logits
+ *   labels   [B][M][5]: class, cx, cy, w, h; image b uses its first num_gt[b] rows (num_gt [B] int32 on the DEVICE, clamped to 0..M)
+ *   x_shifts, y_shifts, strides [A]: the anchor centre is shift * stride + 0.5 * stride;  img_h, img_w clip the box centres
+ *   -> fg_mask [B][A] (1 = anchor matched), matched_gt [B][A] (box index, -1 for background), matched_iou [B][A] (IoU with the matched
+ *      box, 0 for background), num_fg [B] (matches per image).  Every output is completely written, also for images with num_gt == 0.
+ * An anchor is a candidate when its centre lies strictly inside some box or inside the 2.5-stride square around some (clipped) box centre;
+ * cost = sum_c BCE(sqrt(sigmoid(cls) sigmoid(obj)), onehot(class)) + 3 (-log(iou + 1e-8)) + 1e5 (not inside box AND square); box g takes
+ * its k_g = max(1, int(sum of its 10 largest IoUs)) cheapest candidates; an anchor taken by several boxes goes to the cheapest of ALL boxes.
+ * Ties, which PyTorch leaves open: the lower anchor index wins in both top-k passes, the lower box index in the arg-min.  Only integer
+ * atomics are used: two calls give the same bits.  A class outside 0..C-1 is clamped (the reference's one_hot would fail instead).
+ * Limits: 1 <= B <= 65535, 1 <= A < 2^24, 0 <= M <= 1024, 1 <= C <= 256; other shapes are refused with an error string and
+ * uni_simota_workspace_bytes returns 0 for them.
+ * workspace: 4-byte aligned device scratch of >= uni_simota_workspace_bytes(B, A, M, C) bytes, which is at most
+ * 3 * B * M * A * 4 bytes (two B x M x A fp32 planes are used: cost and IoU) plus 4 * B * A * (C + 4) bytes plus 2 KiB of alignment;
+ * it has no term with M * A * C. */
+size_t uni_simota_workspace_bytes(int B, int A, int Gmax, int C);
+int uni_simota_assign(const float* outputs, int ld_out, const float* labels, const int32_t* num_gt, int M, const float* x_shifts,
+                      const float* y_shifts, const float* strides, int B, int A, int C, int img_h, int img_w, uint8_t* fg_mask,
+                      int32_t* matched_gt, float* matched_iou, int32_t* num_fg, void* workspace, size_t workspace_bytes,
+                      uni_stream_t stream);
 
 /* Input letterbox on the device (row 0 / N1): PreprocessorX.process (external/lib/test/tracker/unicorn_sot.py:111-123,
  * swap_rb = 1) and preproc (unicorn/data/data_augment.py:194-214, swap_rb = 0).  img_hwc: (h, w, 3) uint8 DEVICE buffer;

@@ -335,6 +335,16 @@ int uni_condinst_loss_bwd_f64(const double* mask_feats, const double* up_masks, 
     API(launch_condinst_loss_bwd_f64(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, sums, grad_loss, n, H8, W8, up_rate,
                                      grad_mask_feats, grad_up_masks, grad_params, workspace, workspace_bytes, S(stream)));
 }
+size_t uni_simota_workspace_bytes(int B, int A, int Gmax, int C) { return simota_workspace_bytes(B, A, Gmax, C); }
+int uni_simota_assign(const float* outputs, int ld_out, const float* labels, const int32_t* num_gt, int M, const float* x_shifts,
+                      const float* y_shifts, const float* strides, int B, int A, int C, int img_h, int img_w, uint8_t* fg_mask,
+                      int32_t* matched_gt, float* matched_iou, int32_t* num_fg, void* workspace, size_t workspace_bytes,
+                      uni_stream_t stream) {
+    UNI_REQUIRE(outputs && (labels || M == 0) && num_gt && x_shifts && y_shifts && strides && fg_mask && matched_gt && matched_iou && num_fg &&
+                workspace, "simota_assign: NULL argument");
+    API(launch_simota_assign(outputs, ld_out, labels, num_gt, M, x_shifts, y_shifts, strides, B, A, C, img_h, img_w, fg_mask, matched_gt,
+                             matched_iou, num_fg, workspace, workspace_bytes, S(stream)));
+}
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

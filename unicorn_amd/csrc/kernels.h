@@ -210,6 +210,13 @@ int launch_condinst_loss_fwd_f64(const double* mf, const double* um, const doubl
 int launch_condinst_loss_bwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
                                  const double* gt, const double* sums, const double* gout, int n, int H, int W, int r, double* gmf, double* gum,
                                  double* gpar, void* ws, size_t ws_bytes, hipStream_t s);
+// simota.hip: SimOTA label assignment of the head loss (unicorn_head_mask.py:754-983) for a batch, four launches, no host read-back.
+// outputs [B][A][ld >= 5 + C] (cx, cy, w, h, obj, cls logits), labels [B][M][5] (class, cx, cy, w, h), num_gt [B] device,
+// xs / ys / st [A] -> fg_mask [B][A], matched_gt [B][A] (-1 = background), matched_iou [B][A], num_fg [B], all completely written.
+size_t simota_workspace_bytes(int B, int A, int M, int C);
+int launch_simota_assign(const float* outputs, int ld, const float* labels, const int* num_gt, int M, const float* xs, const float* ys,
+                         const float* st, int B, int A, int C, int img_h, int img_w, unsigned char* fg_mask, int* matched_gt,
+                         float* matched_iou, int* num_fg, void* ws, size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

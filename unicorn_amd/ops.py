@@ -410,6 +410,133 @@ def condinst_dice_loss(mask_feats, up_masks, params, inst_loc, inst_lvl, gt_bitm
                                       gt_bitmasks.detach().reshape(n, r * H8, r * W8).contiguous(), r)
 
 
+def _simota_1d(name, t, A):
+    if t.dim() == 2 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 1 or t.shape[0] != A:
+        raise ValueError("simota_assign: %s %s does not fit (1, A) or (A,) with A = %d" % (name, tuple(t.shape), A))
+    return t
+
+
+def _simota_check(ts, names):
+    for n, t in zip(names, ts):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("simota_assign: %s is not a tensor" % n)
+    for n, t in zip(names, ts):
+        if t.dtype != torch.float32:
+            raise ValueError("simota_assign: %s is %s; only fp32 is supported (no fp16 / autocast inputs)" % (n, t.dtype))
+
+
+def _simota_dev(ts, names):
+    for n, t in zip(names, ts):
+        if not t.is_cuda:
+            raise ValueError("simota_assign: %s is a CPU tensor; the operator needs HIP device tensors (there is no CPU fallback)" % n)
+    if len({t.device for t in ts}) != 1:
+        raise ValueError("simota_assign: tensors on different devices %s" % sorted({str(t.device) for t in ts}))
+
+
+def _simota_img(img_size):
+    try:
+        h, w = int(img_size[0]), int(img_size[1])
+    except (TypeError, IndexError, ValueError):
+        raise ValueError("simota_assign: img_size %r is not (height, width)" % (img_size,))
+    if h <= 0 or w <= 0:
+        raise ValueError("simota_assign: img_size %r is not positive" % (img_size,))
+    return h, w
+
+
+def _simota_call(outputs, labels, num_gt, xs, ys, st, h, w, C):
+    """outputs (B, A, >= 5 + C) with unit column stride, labels (B, M, 5) contiguous, num_gt (B,) int32 on the device, xs / ys / st (A,)
+    contiguous -> fg (B, A) uint8, matched (B, A) int32, iou (B, A) fp32, num_fg (B,) int32.  No host synchronisation."""
+    B, A, M, dev = outputs.shape[0], outputs.shape[1], labels.shape[1], outputs.device
+    lib = L.lib()
+    need = lib.uni_simota_workspace_bytes(B, A, M, C)
+    if need == 0:
+        raise ValueError("simota_assign: shape B=%d A=%d M=%d C=%d is outside the limits of uni_simota_assign (include/unicorn_hip.h)"
+                         % (B, A, M, C))
+    fg = torch.empty((B, A), device=dev, dtype=torch.uint8)
+    matched = torch.empty((B, A), device=dev, dtype=torch.int32)
+    iou = torch.empty((B, A), device=dev, dtype=torch.float32)
+    num_fg = torch.empty((B,), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        L.check(lib.uni_simota_assign(L.ptr(outputs), outputs.stride(1), L.ptr(labels), L.ptr(num_gt), M, L.ptr(xs), L.ptr(ys), L.ptr(st), B, A, C,
+                                      h, w, L.ptr(fg), L.ptr(matched), L.ptr(iou), L.ptr(num_fg), L.ptr(ws), need, L.stream_ptr()),
+                "uni_simota_assign")
+    return fg, matched, iou, num_fg
+
+
+def simota_assign_batch(outputs, labels, x_shifts, y_shifts, expanded_strides, img_size, num_classes):
+    """The SimOTA label assignment of get_losses (unicorn_head_mask.py:571-645 with :754-983) for the WHOLE batch in one call and without a
+    host synchronisation: outputs (B, A, 5 + C) = decoded cx, cy, w, h, objectness logit, class logits; labels (B, M, 5) = class, cx, cy, w, h,
+    padded with zero rows (the number of boxes per image is (labels.sum(2) > 0).sum(1), computed on the device as the reference does);
+    x_shifts / y_shifts / expanded_strides (1, A) or (A,); img_size (height, width); all tensors fp32 on one HIP device.
+    -> fg_masks (B, A) bool, matched_gt_inds (B, A) int64 (-1 = background), matched_ious (B, A), num_fg (B,) int64 on the device.
+    Ties, which PyTorch leaves open: the lower anchor index wins in both top-k passes, the lower box index in the arg-min."""
+    names = ("outputs", "labels", "x_shifts", "y_shifts", "expanded_strides")
+    ts = (outputs, labels, x_shifts, y_shifts, expanded_strides)
+    _simota_check(ts, names)
+    C = int(num_classes)
+    if outputs.dim() != 3 or labels.dim() != 3 or C < 1 or outputs.shape[2] != 5 + C or labels.shape[2] != 5 or labels.shape[0] != outputs.shape[0]:
+        raise ValueError("simota_assign_batch: outputs %s, labels %s do not fit (B, A, 5 + num_classes) and (B, M, 5) with num_classes = %r"
+                         % (tuple(outputs.shape), tuple(labels.shape), num_classes))
+    B, A, _ = outputs.shape
+    xs, ys, st = (_simota_1d(n, t, A).contiguous() for n, t in zip(names[2:], ts[2:]))
+    h, w = _simota_img(img_size)
+    if B == 0 or A == 0:
+        raise ValueError("simota_assign_batch: empty batch or no anchors, outputs %s" % (tuple(outputs.shape),))
+    _simota_dev(ts, names)
+    with torch.no_grad():
+        out = outputs.detach()
+        out = out if out.stride(2) == 1 and out.stride(0) == A * out.stride(1) and out.stride(1) >= 5 + C else out.contiguous()
+        lab = labels.detach().contiguous()
+        num_gt = (lab.sum(dim=2) > 0).sum(dim=1).to(torch.int32)
+        fg, matched, iou, num_fg = _simota_call(out, lab, num_gt, xs, ys, st, h, w, C)
+        return fg.bool(), matched.long(), iou, num_fg.long()
+
+
+def simota_assign(bboxes_preds_per_image, obj_preds_b, cls_preds_b, gt_bboxes_per_image, gt_classes, x_shifts, y_shifts, expanded_strides,
+                  img_size, num_classes):
+    """Drop-in for the get_assignments call of one image (unicorn_head_mask.py:592-613): bboxes_preds_per_image (A, 4) decoded cx, cy, w, h,
+    obj_preds_b (A, 1) and cls_preds_b (A, C) logits, gt_bboxes_per_image (G, 4) cx, cy, w, h, gt_classes (G,), shifts and strides (1, A) or
+    (A,), img_size (height, width); all fp32 on one HIP device.  -> the reference's tuple (gt_matched_classes (num_fg,), fg_mask (A,) bool,
+    pred_ious_this_matching (num_fg,), matched_gt_inds (num_fg,) int64 in ascending anchor order, num_fg int).  The one host synchronisation
+    is the read of num_fg.  Ties: the lower anchor index wins in both top-k passes, the lower box index in the arg-min."""
+    names = ("bboxes_preds_per_image", "obj_preds_b", "cls_preds_b", "gt_bboxes_per_image", "gt_classes", "x_shifts", "y_shifts",
+             "expanded_strides")
+    ts = (bboxes_preds_per_image, obj_preds_b, cls_preds_b, gt_bboxes_per_image, gt_classes, x_shifts, y_shifts, expanded_strides)
+    _simota_check(ts, names)
+    C = int(num_classes)
+    box, obj, cls, gtb, gtc = ts[:5]
+    if box.dim() != 2 or box.shape[1] != 4 or C < 1 or tuple(cls.shape) != (box.shape[0], C) or gtb.dim() != 2 or gtb.shape[1] != 4 \
+            or tuple(gtc.shape) != (gtb.shape[0],) or obj.numel() != box.shape[0] or obj.dim() not in (1, 2):
+        raise ValueError("simota_assign: shapes %s do not fit bboxes (A, 4), obj (A, 1), cls (A, num_classes = %r), gt boxes (G, 4), gt classes (G,)"
+                         % ([tuple(t.shape) for t in ts[:5]], num_classes))
+    A, G, dev = box.shape[0], gtb.shape[0], box.device
+    xs, ys, st = (_simota_1d(n, t, A).contiguous() for n, t in zip(names[5:], ts[5:]))
+    h, w = _simota_img(img_size)
+    if A == 0:
+        raise ValueError("simota_assign: no anchors")
+    _simota_dev(ts, names)
+    if G == 0:
+        return (gtc.new_zeros((0,)), torch.zeros((A,), device=dev, dtype=torch.bool), box.new_zeros((0,)),
+                torch.zeros((0,), device=dev, dtype=torch.int64), 0)
+    with torch.no_grad():
+        out = torch.cat([box.detach(), obj.detach().reshape(A, 1), cls.detach()], dim=1)[None]
+        lab = torch.cat([gtc.detach()[:, None], gtb.detach()], dim=1)[None].contiguous()
+        num_gt = torch.full((1,), G, device=dev, dtype=torch.int32)
+        fg, matched, iou, num_fg = _simota_call(out, lab, num_gt, xs, ys, st, h, w, C)
+        n = int(num_fg.item())                                     # the one host synchronisation
+        fg = fg[0].bool()
+        # compaction in ascending anchor order without a second synchronisation (a boolean index would read the count back again):
+        # matched anchor a goes to slot (number of matched anchors before it); the others share a dump slot that is cut off.
+        # scatter_ with duplicate indices is non-deterministic, but the duplicates all land in that discarded slot: slots < n have one writer
+        slot = torch.where(fg, torch.cumsum(fg, 0) - 1, torch.full((), n, device=dev, dtype=torch.int64))
+        anchors = torch.zeros((n + 1,), device=dev, dtype=torch.int64).scatter_(0, slot, torch.arange(A, device=dev))[:n]
+        inds = matched[0].long()[anchors]
+        return gtc[inds], fg, iou[0][anchors], inds, n
+
+
 def condinst_masks_resized(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate, d_rate, r, H, W, thr=None):
     """condinst_masks + mask_resize in ONE call (uni_condinst_masks_u8): the CondInst scores of `params` resized by 1/r and pasted into
     (N, H, W) maps -- `> thr` bytes (mot_evaluator.py:804-805) or, with thr=None, fp32 probabilities (unicorn_vos.py:141-152) -- without the
