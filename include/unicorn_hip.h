@@ -273,6 +273,48 @@ int uni_simota_assign(const float* outputs, int ld_out, const float* labels, con
                       const float* y_shifts, const float* strides, int B, int A, int C, int img_h, int img_w, uint8_t* fg_mask,
                       int32_t* matched_gt, float* matched_iou, int32_t* num_fg, void* workspace, size_t workspace_bytes,
                       uni_stream_t stream);
+/* The MOT instance-contrastive loss for TRAINING (unicorn/models/unicorn.py:407-466, compute_loss_mot_corr) for a whole BATCH, forward and
+ * backward, in a constant number of launches (5 forward, 8 backward) whatever B, M and the instance counts, without a host
+ * synchronisation, a read-back or an allocation.
+ *   embed_0, embed_1  (B, C, H, W) maps of the two frames, read through ELEMENT strides strides_f[4] = (batch, channel, row, column) given
+ *                     as host arrays: NCHW and NHWC (channels-last) memory both work without a copy.  Strides are >= 0.
+ *   targets           [B][2][M][6] fp32, contiguous: rows (class, cx, cy, w, h, track id) of frame 0 and frame 1; fp32 in the _f64 forms too
+ *   stride            the reference's `s` (8): input pixels per map pixel;  flags: UNI_MOT_BIDIRECT | UNI_MOT_GRID_SAMPLE
+ *   -> loss [B], one value per sample (the reference returns their mean).
+ * Per sample: n_f = number of rows of frame f with id != 0, and the instances are the FIRST n_f rows whatever their ids (the reference's
+ * range(n_f)); row[i] = smallest j < n1 with id1[j] == id0[i] (fp32 compare), col[j] = LARGEST i < n0 with row[i] == j (the
+ * reference's overwrite order), -1 where there is none; E_f[i] = the embedding at the centre of instance i, with GRID_SAMPLE by
+ * g = (clamp(c / stride - 0.5, 0, size-1) / (size-1) - 0.5) * 2 (fp32 in both precisions) handed to grid_sample(bilinear, border,
+ * align_corners=False), i.e. x = clip(((g + 1) size - 1) / 2, 0, size-1) in the map's precision; without it the one pixel
+ * rint(clamp(c / stride, 0, size-1)) (half to even).  S = E_0 E_1^T; loss = 0.5 (CE(S, row) + CE(S^T, col)) with BIDIRECT, else
+ * CE(S, row); CE is the mean over the labelled rows (ignore_index = -1) with max-subtracted log-sum-exps.
+ * A sample without a matched pair gives NaN and a gradient of exactly zero (as torch's cross_entropy does).  A sample with n0 == 0 or
+ * n1 == 0 -- where the reference raises -- gives NaN and a zero gradient as well; other samples are not affected.
+ *   uni_mot_corr_loss_bwd  given grad_loss [B], writes the dense gradients grad_embed_f (B, C, H, W) COMPLETELY through grad_strides_f (all
+ *                          >= 1 and non-overlapping: refused otherwise): zeros, plus every instance's dE spread over its one to four source pixels with the
+ *                          forward's weights.  Either may be NULL: that gradient is not computed.  Targets carry no gradient.
+ * One writer per element and fixed summation orders, no float atomics: two calls give the same bits.
+ * Limits: 1 <= B <= 65535, 1 <= M <= 1024, 1 <= C <= 1024, C H W < 2^31; other shapes are refused with an error string and
+ * uni_mot_corr_workspace_bytes returns 0 for them.
+ * workspace: 8-byte aligned device scratch of >= uni_mot_corr_workspace_bytes(B, M, C) bytes (fp32; the _f64 forms need twice that),
+ * 4 B M (4 C + M + 14) + 16 B bytes plus at most 9 x 256 of alignment; nothing is kept in it between the two calls (the backward recomputes from the inputs). */
+#define UNI_MOT_BIDIRECT 1
+#define UNI_MOT_GRID_SAMPLE 2
+size_t uni_mot_corr_workspace_bytes(int B, int M, int C);
+int uni_mot_corr_loss_fwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
+                          int B, int C, int H, int W, int M, float stride, int flags, float* loss, void* workspace, size_t workspace_bytes,
+                          uni_stream_t stream);
+int uni_mot_corr_loss_bwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
+                          const float* grad_loss, int B, int C, int H, int W, int M, float stride, int flags, float* grad_embed_0,
+                          const int64_t* grad_strides_0, float* grad_embed_1, const int64_t* grad_strides_1, void* workspace,
+                          size_t workspace_bytes, uni_stream_t stream);
+int uni_mot_corr_loss_fwd_f64(const double* embed_0, const int64_t* strides_0, const double* embed_1, const int64_t* strides_1,
+                              const float* targets, int B, int C, int H, int W, int M, float stride, int flags, double* loss, void* workspace,
+                              size_t workspace_bytes, uni_stream_t stream);
+int uni_mot_corr_loss_bwd_f64(const double* embed_0, const int64_t* strides_0, const double* embed_1, const int64_t* strides_1,
+                              const float* targets, const double* grad_loss, int B, int C, int H, int W, int M, float stride, int flags,
+                              double* grad_embed_0, const int64_t* grad_strides_0, double* grad_embed_1, const int64_t* grad_strides_1,
+                              void* workspace, size_t workspace_bytes, uni_stream_t stream);
 
 /* Input letterbox on the device (row 0 / N1): PreprocessorX.process (external/lib/test/tracker/unicorn_sot.py:111-123,
  * swap_rb = 1) and preproc (unicorn/data/data_augment.py:194-214, swap_rb = 0).  img_hwc: (h, w, 3) uint8 DEVICE buffer;

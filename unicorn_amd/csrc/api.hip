@@ -345,6 +345,43 @@ int uni_simota_assign(const float* outputs, int ld_out, const float* labels, con
     API(launch_simota_assign(outputs, ld_out, labels, num_gt, M, x_shifts, y_shifts, strides, B, A, C, img_h, img_w, fg_mask, matched_gt,
                              matched_iou, num_fg, workspace, workspace_bytes, S(stream)));
 }
+static inline McStride mc_stride(const int64_t* s) { return McStride{s[0], s[1], s[2], s[3]}; }
+static const int64_t mc_no_stride[4] = {0, 0, 0, 0};
+size_t uni_mot_corr_workspace_bytes(int B, int M, int C) { return mot_corr_workspace_bytes(B, M, C); }
+int uni_mot_corr_loss_fwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
+                          int B, int C, int H, int W, int M, float stride, int flags, float* loss, void* workspace, size_t workspace_bytes,
+                          uni_stream_t stream) {
+    UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && loss && workspace, "mot_corr_loss_fwd: NULL argument");
+    API(launch_mot_corr_fwd(embed_0, mc_stride(strides_0), embed_1, mc_stride(strides_1), targets, B, C, H, W, M, stride, flags, loss, workspace,
+                            workspace_bytes, S(stream)));
+}
+int uni_mot_corr_loss_bwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
+                          const float* grad_loss, int B, int C, int H, int W, int M, float stride, int flags, float* grad_embed_0,
+                          const int64_t* grad_strides_0, float* grad_embed_1, const int64_t* grad_strides_1, void* workspace,
+                          size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && grad_loss && workspace && (!grad_embed_0 || grad_strides_0) &&
+                (!grad_embed_1 || grad_strides_1), "mot_corr_loss_bwd: NULL argument");
+    API(launch_mot_corr_bwd(embed_0, mc_stride(strides_0), embed_1, mc_stride(strides_1), targets, grad_loss, B, C, H, W, M, stride, flags,
+                            grad_embed_0, mc_stride(grad_embed_0 ? grad_strides_0 : mc_no_stride), grad_embed_1,
+                            mc_stride(grad_embed_1 ? grad_strides_1 : mc_no_stride), workspace, workspace_bytes, S(stream)));
+}
+int uni_mot_corr_loss_fwd_f64(const double* embed_0, const int64_t* strides_0, const double* embed_1, const int64_t* strides_1,
+                              const float* targets, int B, int C, int H, int W, int M, float stride, int flags, double* loss, void* workspace,
+                              size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && loss && workspace, "mot_corr_loss_fwd_f64: NULL argument");
+    API(launch_mot_corr_fwd_f64(embed_0, mc_stride(strides_0), embed_1, mc_stride(strides_1), targets, B, C, H, W, M, stride, flags, loss,
+                                workspace, workspace_bytes, S(stream)));
+}
+int uni_mot_corr_loss_bwd_f64(const double* embed_0, const int64_t* strides_0, const double* embed_1, const int64_t* strides_1,
+                              const float* targets, const double* grad_loss, int B, int C, int H, int W, int M, float stride, int flags,
+                              double* grad_embed_0, const int64_t* grad_strides_0, double* grad_embed_1, const int64_t* grad_strides_1,
+                              void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && grad_loss && workspace && (!grad_embed_0 || grad_strides_0) &&
+                (!grad_embed_1 || grad_strides_1), "mot_corr_loss_bwd_f64: NULL argument");
+    API(launch_mot_corr_bwd_f64(embed_0, mc_stride(strides_0), embed_1, mc_stride(strides_1), targets, grad_loss, B, C, H, W, M, stride, flags,
+                                grad_embed_0, mc_stride(grad_embed_0 ? grad_strides_0 : mc_no_stride), grad_embed_1,
+                                mc_stride(grad_embed_1 ? grad_strides_1 : mc_no_stride), workspace, workspace_bytes, S(stream)));
+}
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

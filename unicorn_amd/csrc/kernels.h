@@ -217,6 +217,22 @@ size_t simota_workspace_bytes(int B, int A, int M, int C);
 int launch_simota_assign(const float* outputs, int ld, const float* labels, const int* num_gt, int M, const float* xs, const float* ys,
                          const float* st, int B, int A, int C, int img_h, int img_w, unsigned char* fg_mask, int* matched_gt,
                          float* matched_iou, int* num_fg, void* ws, size_t ws_bytes, hipStream_t s);
+// mot_corr.hip: the MOT instance-contrastive loss of training (unicorn.py:407-466) for a batch, forward + backward, fp32 and fp64, a constant
+// number of launches and no host read-back.  e0 / e1 (B, C, H, W) through element strides, targets [B][2][M][6] fp32 -> loss [B]; the backward
+// writes the dense g0 / g1 completely through their own strides (NULL: not computed).  Workspace: mot_corr_workspace_bytes for fp32, twice
+// that for fp64; scratch between the calls (the backward recomputes).  flags: 1 = bidirect, 2 = grid_sample.
+struct McStride { long long b, c, y, x; };      // element strides of a (B, C, H, W) map
+size_t mot_corr_workspace_bytes(int B, int M, int C);
+int launch_mot_corr_fwd(const float* e0, McStride s0, const float* e1, McStride s1, const float* targets, int B, int C, int H, int W, int M,
+                        float stride, int flags, float* loss, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_mot_corr_bwd(const float* e0, McStride s0, const float* e1, McStride s1, const float* targets, const float* gout, int B, int C, int H,
+                        int W, int M, float stride, int flags, float* g0, McStride gs0, float* g1, McStride gs1, void* ws, size_t ws_bytes,
+                        hipStream_t s);
+int launch_mot_corr_fwd_f64(const double* e0, McStride s0, const double* e1, McStride s1, const float* targets, int B, int C, int H, int W, int M,
+                            float stride, int flags, double* loss, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_mot_corr_bwd_f64(const double* e0, McStride s0, const double* e1, McStride s1, const float* targets, const double* gout, int B, int C,
+                            int H, int W, int M, float stride, int flags, double* g0, McStride gs0, double* g1, McStride gs1, void* ws,
+                            size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

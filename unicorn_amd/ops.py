@@ -537,6 +537,99 @@ def simota_assign(bboxes_preds_per_image, obj_preds_b, cls_preds_b, gt_bboxes_pe
         return gtc[inds], fg, iou[0][anchors], inds, n
 
 
+_MC_ENTRY = {torch.float32: ("uni_mot_corr_loss_fwd", "uni_mot_corr_loss_bwd", 1),
+             torch.float64: ("uni_mot_corr_loss_fwd_f64", "uni_mot_corr_loss_bwd_f64", 2)}
+
+
+def _mc_strides(t):
+    return (C.c_int64 * 4)(*t.stride())
+
+
+def _mc_ws(dev, dtype, B, M, Cc):
+    need = L.lib().uni_mot_corr_workspace_bytes(B, M, Cc)
+    if need == 0:
+        raise L.UnicornHipError("mot_corr_loss: shape B=%d M=%d C=%d is outside the limits of uni_mot_corr_loss_fwd (include/unicorn_hip.h)"
+                                % (B, M, Cc))
+    return torch.empty(need * _MC_ENTRY[dtype][2], device=dev, dtype=torch.uint8)      # the fp64 forms need twice the fp32 size
+
+
+class MotCorrLossFunction(torch.autograd.Function):
+    """The MOT instance-contrastive loss per sample (unicorn.py:407-466), differentiable in the two embedding maps:
+    apply(embed_0 (B,C,H,W), embed_1 (B,C,H,W), targets (B,2,M,6) fp32 contiguous, s, flags) -> loss (B,); fp32 or fp64 device maps of any
+    strides (mot_corr_loss checks).  Saves the inputs only; the backward recomputes.  No host synchronisation in either direction; one writer
+    per gradient element: bitwise reproducible.  B == 0 or M == 0: no library call (NaN losses, zero gradients)."""
+
+    @staticmethod
+    def forward(ctx, embed_0, embed_1, targets, s, flags):
+        B, Cc, H, W = embed_0.shape
+        M = targets.shape[2]
+        ctx.save_for_backward(embed_0, embed_1, targets)
+        ctx.s, ctx.flags = float(s), int(flags)
+        loss = torch.empty((B,), device=embed_0.device, dtype=embed_0.dtype)
+        if B == 0 or M == 0:
+            return loss.fill_(float("nan"))
+        fwd = _MC_ENTRY[embed_0.dtype][0]
+        with torch.cuda.device(embed_0.device):
+            ws = _mc_ws(embed_0.device, embed_0.dtype, B, M, Cc)
+            L.check(getattr(L.lib(), fwd)(L.ptr(embed_0), _mc_strides(embed_0), L.ptr(embed_1), _mc_strides(embed_1), L.ptr(targets), B, Cc, H, W, M,
+                                          ctx.s, ctx.flags, L.ptr(loss), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        e0, e1, targets = ctx.saved_tensors
+        B, Cc, H, W = e0.shape
+        M = targets.shape[2]
+        if B == 0 or M == 0:
+            return (torch.zeros_like(e0) if ctx.needs_input_grad[0] else None, torch.zeros_like(e1) if ctx.needs_input_grad[1] else None, None,
+                    None, None)
+        # empty_like: a dense tensor in the map's own dimension order (NCHW, channels-last); the call writes it completely
+        g0 = torch.empty_like(e0) if ctx.needs_input_grad[0] else None
+        g1 = torch.empty_like(e1) if ctx.needs_input_grad[1] else None
+        if g0 is not None or g1 is not None:
+            bwd = _MC_ENTRY[e0.dtype][1]
+            g = grad_loss.contiguous()
+            with torch.cuda.device(e0.device):
+                ws = _mc_ws(e0.device, e0.dtype, B, M, Cc)
+                L.check(getattr(L.lib(), bwd)(L.ptr(e0), _mc_strides(e0), L.ptr(e1), _mc_strides(e1), L.ptr(targets), L.ptr(g), B, Cc, H, W, M,
+                                              ctx.s, ctx.flags, L.ptr(g0), None if g0 is None else _mc_strides(g0), L.ptr(g1),
+                                              None if g1 is None else _mc_strides(g1), L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
+        return g0, g1, None, None, None
+
+
+def mot_corr_loss(embed_0, embed_1, targets, s=8, bidirect=True, grid_sample=True):
+    """Unicorn.compute_loss_mot_corr (unicorn.py:407-466) for the whole batch in one call without a host synchronisation:
+    embed_0, embed_1 (B, C, H_d, W_d) fp32 (or both fp64), NCHW or channels-last memory, read in place; targets (B, 2, M, 6) rows
+    [cls, cx, cy, w, h, trackid], converted with .float() as the reference does -> the (B,) per-sample losses; the reference's value is
+    `.mean()` of it.  Equal in value and in gradient (embed_0, embed_1) to the reference's loop, with its quirks: the first n rows of a frame
+    are its instances (n = number of non-zero ids), a repeated id keeps the reference's overwrite order, the align_corners=True style grid is
+    sampled with align_corners=False.  A sample without a matched pair gives NaN and a zero gradient like the reference; so does a sample
+    without instances, where the reference raises.  fp16 / bf16 maps are refused: the reference computes them under autocast(enabled=False)."""
+    for n, t in (("embed_0", embed_0), ("embed_1", embed_1), ("targets", targets)):
+        if not isinstance(t, torch.Tensor):
+            raise L.UnicornHipError("mot_corr_loss: %s is not a tensor" % n)
+    if embed_0.dim() != 4 or embed_1.shape != embed_0.shape or targets.dim() != 4 or targets.shape[0] != embed_0.shape[0] \
+            or targets.shape[1] != 2 or targets.shape[3] != 6:
+        raise L.UnicornHipError("mot_corr_loss: shapes %s, %s, %s do not fit embed_0 (B,C,H,W), embed_1 (B,C,H,W), targets (B,2,M,6)"
+                                % (tuple(embed_0.shape), tuple(embed_1.shape), tuple(targets.shape)))
+    if embed_0.dtype not in _MC_ENTRY or embed_1.dtype != embed_0.dtype:
+        raise L.UnicornHipError("mot_corr_loss: embedding dtypes %s / %s unsupported (both fp32 or both fp64; no fp16 / autocast input: the "
+                                "reference computes the embeddings under autocast(enabled=False))" % (embed_0.dtype, embed_1.dtype))
+    _need_cuda(embed_0, embed_1, targets)
+    if len({t.device for t in (embed_0, embed_1, targets)}) != 1:
+        raise L.UnicornHipError("mot_corr_loss: tensors on different devices")
+    B, Cc, H, W = embed_0.shape
+    M = targets.shape[2]
+    if not float(s) > 0:
+        raise L.UnicornHipError("mot_corr_loss: stride s = %r is not positive" % (s,))
+    if B and M and (B > 65535 or H == 0 or W == 0 or not 1 <= Cc <= 1024 or M > 1024 or Cc * H * W >= 1 << 31):
+        raise L.UnicornHipError("mot_corr_loss: shape B=%d C=%d H=%d W=%d M=%d is outside B <= 65535, 1 <= C <= 1024, M <= 1024, a non-empty map "
+                                "with C H W < 2^31" % (B, Cc, H, W, M))
+    flags = (1 if bidirect else 0) | (2 if grid_sample else 0)
+    return MotCorrLossFunction.apply(embed_0, embed_1, targets.detach().float().contiguous(), float(s), flags)
+
+
 def condinst_masks_resized(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate, d_rate, r, H, W, thr=None):
     """condinst_masks + mask_resize in ONE call (uni_condinst_masks_u8): the CondInst scores of `params` resized by 1/r and pasted into
     (N, H, W) maps -- `> thr` bytes (mot_evaluator.py:804-805) or, with thr=None, fp32 probabilities (unicorn_vos.py:141-152) -- without the
