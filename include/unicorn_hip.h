@@ -273,6 +273,59 @@ int uni_simota_assign(const float* outputs, int ld_out, const float* labels, con
                       const float* y_shifts, const float* strides, int B, int A, int C, int img_h, int img_w, uint8_t* fg_mask,
                       int32_t* matched_gt, float* matched_iou, int32_t* num_fg, void* workspace, size_t workspace_bytes,
                       uni_stream_t stream);
+/* The four detection losses of the head for a whole BATCH (the rest of get_losses, unicorn/models/unicorn_head_mask.py:646-745, identically
+ * unicorn_head.py:484-681, with IOUloss of unicorn/models/losses.py:15-36, loss_type "iou"), forward and backward, fed by the device-side
+ * results of uni_simota_assign: two launches forward and two backward whatever B, A, M, C and the foreground counts, without a host
+ * synchronisation, a read-back or an allocation.
+ *   outputs      [B][A] rows of pitch ld_out >= 5 + C: decoded cx, cy, w, h, then the objectness logit and C class logits
+ *   origin_preds [B][A] rows of pitch ld_org >= 4: the raw regression outputs; NULL = use_l1 False (the L1 loss is 0)
+ *   labels       [B][M][5]: class, cx, cy, w, h (may be NULL when M == 0; with M == 0 every anchor is background)
+ *   fg_mask [B][A] uint8, matched_gt [B][A] int32, matched_iou [B][A]: what uni_simota_assign wrote
+ *   num_fg, num_gt [B] int32 on the DEVICE (clamped to 0..A and 0..M);  x_shifts, y_shifts, strides [A]
+ *   -> out[5] = reg_weight x loss_iou, loss_obj, loss_cls, loss_l1, n / max(sum num_gt, 1) (the reference's quirk: its ratio divides the
+ *      clamped count, so it is 1.0 with no box at all), every loss divided by n = max(sum_b num_fg[b], 1) read from device memory:
+ *      obj  sum over ALL anchors of bce(obj_logit, fg);   iou  sum over foreground anchors of 1 - iou(pred, gt[matched])^2;
+ *      cls  sum over foreground anchors and classes of bce(cls_logit_c, c == class ? matched_iou : 0);
+ *      l1   sum over foreground anchors and 4 components of |origin - t|, t = (gx / s - x_shift, gy / s - y_shift, log(gw / s + 1e-8),
+ *           log(gh / s + 1e-8)) (:747-752);   bce(x, t) = max(x, 0) - x t + log1p(exp(-|x|)).
+ *      IoU as losses.py:15-36: edges = centre -+ size / 2, tl = max, br = min, en = (tl < br) strictly on both axes,
+ *      area_i = (br - tl).prod * en, iou = area_i / (area_p + area_g - area_i + 1e-16).
+ *   uni_head_loss_bwd  given grad_out[4] on the device (the weights of out[0..3]) writes grad_outputs [B][A] rows of pitch
+ *      ld_grad >= 5 + C, columns 0 .. 4 + C (the pitch padding is not touched), and grad_origin [B][A][4] COMPLETELY, one writer per
+ *      element: the objectness column of every anchor (sigmoid(x) - fg) g_obj / n; box and class columns and grad_origin of background
+ *      anchors exact zeros; class columns of foreground anchors (sigmoid(x_c) - t_c) g_cls / n; grad_origin sign(origin - t) g_l1 / n
+ *      with sign(0) = 0; box columns -2 iou d iou / d (cx, cy, w, h) reg_weight g_iou / n through the max / min of the edges, exactly zero
+ *      where en == 0.  Tie rule: where a predicted edge equals the ground-truth edge it is compared with, the gradient is split half and
+ *      half, as torch's maximum / minimum do.  Either gradient pointer may be NULL: not computed (grad_origin needs origin_preds).
+ *      The backward recomputes from the inputs; nothing is kept in the workspace between the two calls.
+ * The kernels never index labels with a matched_gt outside 0..M-1 on a foreground anchor: such a value is clamped; a class outside
+ * 0..C-1 is clamped as the assignment does.  The sums are accumulated in double in both precisions, in a fixed order, and the box, IoU and
+ * L1 lines of a foreground anchor are evaluated in double in the fp32 form as well (the foreground is sparse); there is no atomic: two
+ * calls give the same bits.
+ * Limits: 1 <= B <= 65535, 1 <= A < 2^24, 0 <= M <= 1024, 1 <= C <= 256; other shapes are refused with an error string and
+ * uni_head_loss_workspace_bytes returns 0 for them.
+ * workspace: 8-byte aligned device scratch of >= uni_head_loss_workspace_bytes(B, A, C) = B * ceil(A / 256) * 32 bytes rounded up to a
+ * multiple of 256 (four double partial sums per block of 256 anchors), the same in both precisions.
+ * The _f64 forms are the same templated code in double precision, for gradcheck and fixtures: every floating-point array is double there
+ * (matched_iou included, so that the fp64 run of the reference can be fed exactly); fg_mask, matched_gt, num_fg and num_gt stay as above. */
+size_t uni_head_loss_workspace_bytes(int B, int A, int C);
+int uni_head_loss_fwd(const float* outputs, int ld_out, const float* origin_preds, int ld_org, const float* labels, int M, const uint8_t* fg_mask,
+                      const int32_t* matched_gt, const float* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const float* x_shifts,
+                      const float* y_shifts, const float* strides, int B, int A, int C, double reg_weight, float* out, void* workspace,
+                      size_t workspace_bytes, uni_stream_t stream);
+int uni_head_loss_bwd(const float* outputs, int ld_out, const float* origin_preds, int ld_org, const float* labels, int M, const uint8_t* fg_mask,
+                      const int32_t* matched_gt, const float* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const float* x_shifts,
+                      const float* y_shifts, const float* strides, const float* grad_out, int B, int A, int C, double reg_weight,
+                      float* grad_outputs, int ld_grad, float* grad_origin, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_head_loss_fwd_f64(const double* outputs, int ld_out, const double* origin_preds, int ld_org, const double* labels, int M,
+                          const uint8_t* fg_mask, const int32_t* matched_gt, const double* matched_iou, const int32_t* num_fg,
+                          const int32_t* num_gt, const double* x_shifts, const double* y_shifts, const double* strides, int B, int A, int C,
+                          double reg_weight, double* out, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_head_loss_bwd_f64(const double* outputs, int ld_out, const double* origin_preds, int ld_org, const double* labels, int M,
+                          const uint8_t* fg_mask, const int32_t* matched_gt, const double* matched_iou, const int32_t* num_fg,
+                          const int32_t* num_gt, const double* x_shifts, const double* y_shifts, const double* strides, const double* grad_out,
+                          int B, int A, int C, double reg_weight, double* grad_outputs, int ld_grad, double* grad_origin, void* workspace,
+                          size_t workspace_bytes, uni_stream_t stream);
 /* The MOT instance-contrastive loss for TRAINING (unicorn/models/unicorn.py:407-466, compute_loss_mot_corr) for a whole BATCH, forward and
  * backward, in a constant number of launches (5 forward, 8 backward) whatever B, M and the instance counts, without a host
  * synchronisation, a read-back or an allocation.

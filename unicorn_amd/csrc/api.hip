@@ -382,6 +382,45 @@ int uni_mot_corr_loss_bwd_f64(const double* embed_0, const int64_t* strides_0, c
                                 grad_embed_0, mc_stride(grad_embed_0 ? grad_strides_0 : mc_no_stride), grad_embed_1,
                                 mc_stride(grad_embed_1 ? grad_strides_1 : mc_no_stride), workspace, workspace_bytes, S(stream)));
 }
+size_t uni_head_loss_workspace_bytes(int B, int A, int C) { return head_loss_workspace_bytes(B, A, C); }
+int uni_head_loss_fwd(const float* outputs, int ld_out, const float* origin_preds, int ld_org, const float* labels, int M, const uint8_t* fg_mask,
+                      const int32_t* matched_gt, const float* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const float* x_shifts,
+                      const float* y_shifts, const float* strides, int B, int A, int C, double reg_weight, float* out, void* workspace,
+                      size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts && strides &&
+                out && workspace, "head_loss_fwd: NULL argument");
+    API(launch_head_loss_fwd(outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, num_fg, num_gt, x_shifts,
+                             y_shifts, strides, B, A, C, reg_weight, out, workspace, workspace_bytes, S(stream)));
+}
+int uni_head_loss_bwd(const float* outputs, int ld_out, const float* origin_preds, int ld_org, const float* labels, int M, const uint8_t* fg_mask,
+                      const int32_t* matched_gt, const float* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const float* x_shifts,
+                      const float* y_shifts, const float* strides, const float* grad_out, int B, int A, int C, double reg_weight,
+                      float* grad_outputs, int ld_grad, float* grad_origin, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts && strides &&
+                grad_out && workspace, "head_loss_bwd: NULL argument");
+    API(launch_head_loss_bwd(outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, num_fg, num_gt, x_shifts,
+                             y_shifts, strides, grad_out, B, A, C, reg_weight, grad_outputs, ld_grad, grad_origin, workspace, workspace_bytes,
+                             S(stream)));
+}
+int uni_head_loss_fwd_f64(const double* outputs, int ld_out, const double* origin_preds, int ld_org, const double* labels, int M, const uint8_t* fg_mask,
+                      const int32_t* matched_gt, const double* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const double* x_shifts,
+                      const double* y_shifts, const double* strides, int B, int A, int C, double reg_weight, double* out, void* workspace,
+                      size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts && strides &&
+                out && workspace, "head_loss_fwd_f64: NULL argument");
+    API(launch_head_loss_fwd_f64(outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, num_fg, num_gt, x_shifts,
+                             y_shifts, strides, B, A, C, reg_weight, out, workspace, workspace_bytes, S(stream)));
+}
+int uni_head_loss_bwd_f64(const double* outputs, int ld_out, const double* origin_preds, int ld_org, const double* labels, int M, const uint8_t* fg_mask,
+                      const int32_t* matched_gt, const double* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const double* x_shifts,
+                      const double* y_shifts, const double* strides, const double* grad_out, int B, int A, int C, double reg_weight,
+                      double* grad_outputs, int ld_grad, double* grad_origin, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts && strides &&
+                grad_out && workspace, "head_loss_bwd_f64: NULL argument");
+    API(launch_head_loss_bwd_f64(outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, num_fg, num_gt, x_shifts,
+                             y_shifts, strides, grad_out, B, A, C, reg_weight, grad_outputs, ld_grad, grad_origin, workspace, workspace_bytes,
+                             S(stream)));
+}
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

@@ -233,6 +233,26 @@ int launch_mot_corr_fwd_f64(const double* e0, McStride s0, const double* e1, McS
 int launch_mot_corr_bwd_f64(const double* e0, McStride s0, const double* e1, McStride s1, const float* targets, const double* gout, int B, int C,
                             int H, int W, int M, float stride, int flags, double* g0, McStride gs0, double* g1, McStride gs1, void* ws,
                             size_t ws_bytes, hipStream_t s);
+// head_loss.hip: the four detection losses of get_losses (unicorn_head_mask.py:646-745) for a batch from the device-side results of
+// launch_simota_assign, forward + backward, fp32 and fp64, two launches each way and no host read-back.  outputs [B][A][ld >= 5 + C],
+// origin [B][A][ldo >= 4] or NULL, labels [B][M][5], fg / mg / miou [B][A], num_fg / num_gt [B] device, xs / ys / st [A] ->
+// out[5] = reg_weight x iou, obj, cls, l1 losses and max(sum num_fg, 1) / max(sum num_gt, 1); the backward writes g_out [B][A][ldg >= 5 + C]
+// (columns 0 .. 4 + C) and g_org [B][A][4] completely (NULL: not computed).  Workspace: head_loss_workspace_bytes in both precisions.
+size_t head_loss_workspace_bytes(int B, int A, int C);
+int launch_head_loss_fwd(const float* outputs, int ld, const float* origin, int ldo, const float* labels, int M, const unsigned char* fg,
+                         const int* mg, const float* miou, const int* num_fg, const int* num_gt, const float* xs, const float* ys,
+                         const float* st, int B, int A, int C, double reg_weight, float* out, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_head_loss_bwd(const float* outputs, int ld, const float* origin, int ldo, const float* labels, int M, const unsigned char* fg,
+                         const int* mg, const float* miou, const int* num_fg, const int* num_gt, const float* xs, const float* ys,
+                         const float* st, const float* gout, int B, int A, int C, double reg_weight, float* g_out, int ldg, float* g_org,
+                         void* ws, size_t ws_bytes, hipStream_t s);
+int launch_head_loss_fwd_f64(const double* outputs, int ld, const double* origin, int ldo, const double* labels, int M, const unsigned char* fg,
+                             const int* mg, const double* miou, const int* num_fg, const int* num_gt, const double* xs, const double* ys,
+                             const double* st, int B, int A, int C, double reg_weight, double* out, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_head_loss_bwd_f64(const double* outputs, int ld, const double* origin, int ldo, const double* labels, int M, const unsigned char* fg,
+                             const int* mg, const double* miou, const int* num_fg, const int* num_gt, const double* xs, const double* ys,
+                             const double* st, const double* gout, int B, int A, int C, double reg_weight, double* g_out, int ldg,
+                             double* g_org, void* ws, size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

@@ -537,6 +537,133 @@ def simota_assign(bboxes_preds_per_image, obj_preds_b, cls_preds_b, gt_bboxes_pe
         return gtc[inds], fg, iou[0][anchors], inds, n
 
 
+_HL_ENTRY = {torch.float32: ("uni_head_loss_fwd", "uni_head_loss_bwd"), torch.float64: ("uni_head_loss_fwd_f64", "uni_head_loss_bwd_f64")}
+
+
+def _hl_ws(dev, B, A, Cn):
+    need = L.lib().uni_head_loss_workspace_bytes(B, A, Cn)
+    if need == 0:
+        raise ValueError("head_det_loss: shape B=%d A=%d C=%d is outside the limits of uni_head_loss_fwd (include/unicorn_hip.h)" % (B, A, Cn))
+    return torch.empty(need, device=dev, dtype=torch.uint8)
+
+
+def _hl_rows(t, cols):
+    """(B, A, cols) with unit column stride and one row pitch >= cols over the whole batch is passed through; anything else is copied"""
+    return t if t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1) and t.stride(1) >= cols else t.contiguous()
+
+
+class HeadLossFunction(torch.autograd.Function):
+    """The four detection losses of get_losses (unicorn_head_mask.py:646-745) from the device-side assignment, differentiable in `outputs`
+    and `origin_preds`: apply(outputs (B, A, 5 + C), origin_preds (B, A, 4) or None, labels (B, M, 5), fg (B, A) uint8, matched (B, A) int32,
+    iou (B, A), num_fg (B,) int32, num_gt (B,) int32, xs, ys, st (A,), reg_weight) -> (5,) = reg_weight x iou, obj, cls, l1 losses and
+    max(sum num_fg, 1) / max(sum num_gt, 1).  All floating-point tensors fp32, or all fp64; `outputs` may carry a row pitch (a view of a wider
+    buffer).  Saves the inputs only; the backward recomputes.  No host synchronisation in either direction; one writer per gradient
+    element and no atomic: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, outputs, origin_preds, labels, fg, matched, iou, num_fg, num_gt, xs, ys, st, reg_weight):
+        B, A, Cn = outputs.shape[0], outputs.shape[1], outputs.shape[2] - 5
+        M, dev = labels.shape[1], outputs.device
+        out_ = _hl_rows(outputs.detach(), 5 + Cn)
+        org_ = None if origin_preds is None else _hl_rows(origin_preds.detach(), 4)
+        ins = (out_, org_, labels.contiguous(), fg.contiguous(), matched.contiguous(), iou.contiguous(), num_fg.contiguous(), num_gt.contiguous(),
+               xs.contiguous(), ys.contiguous(), st.contiguous())
+        ctx.save_for_backward(*ins)
+        ctx.reg_weight, ctx.dims = float(reg_weight), (B, A, Cn, M)
+        res = torch.empty((5,), device=dev, dtype=outputs.dtype)
+        fwd = _HL_ENTRY[outputs.dtype][0]
+        with torch.cuda.device(dev):
+            ws = _hl_ws(dev, B, A, Cn)
+            L.check(getattr(L.lib(), fwd)(L.ptr(out_), out_.stride(1), L.ptr(org_), 0 if org_ is None else org_.stride(1), L.ptr(ins[2]), M,
+                                          *map(L.ptr, ins[3:]), B, A, Cn, ctx.reg_weight, L.ptr(res), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_res):
+        ins = ctx.saved_tensors
+        out_, org_ = ins[:2]
+        B, A, Cn, M = ctx.dims
+        # both are written completely by the call
+        g_out = torch.empty((B, A, 5 + Cn), device=out_.device, dtype=out_.dtype) if ctx.needs_input_grad[0] else None
+        g_org = torch.empty((B, A, 4), device=out_.device, dtype=out_.dtype) if org_ is not None and ctx.needs_input_grad[1] else None
+        if g_out is not None or g_org is not None:
+            bwd = _HL_ENTRY[out_.dtype][1]
+            g = grad_res[:4].contiguous()
+            with torch.cuda.device(out_.device):
+                ws = _hl_ws(out_.device, B, A, Cn)
+                L.check(getattr(L.lib(), bwd)(L.ptr(out_), out_.stride(1), L.ptr(org_), 0 if org_ is None else org_.stride(1), L.ptr(ins[2]), M,
+                                              *map(L.ptr, ins[3:]), L.ptr(g), B, A, Cn, ctx.reg_weight, L.ptr(g_out), 5 + Cn, L.ptr(g_org),
+                                              L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
+        return (g_out, g_org) + (None,) * 10
+
+
+def head_det_loss(outputs, origin_preds, labels, x_shifts, y_shifts, expanded_strides, img_size, num_classes, reg_weight=5.0, assignment=None):
+    """The detection part of get_losses (unicorn_head_mask.py:571-745 without the CondInst lines :675-694; identically unicorn_head.py) for
+    the WHOLE batch without a host synchronisation: the SimOTA assignment (simota_assign_batch's kernels, under no_grad) and then the four
+    losses in one fused forward and one fused backward.  outputs (B, A, 5 + C) = decoded cx, cy, w, h, objectness logit, class logits;
+    origin_preds (B, A, 4), a list of per-level (B, A_l, 4) tensors (concatenated as the reference does) or None (use_l1 False: l1_loss is an
+    exact zero and carries no gradient); labels (B, M, 5) = class, cx, cy, w, h padded with zero rows; x_shifts / y_shifts /
+    expanded_strides (1, A) or (A,); img_size (height, width); all tensors fp32 on one HIP device.  assignment: the 4-tuple that
+    simota_assign_batch returned for these inputs (it is not computed again).
+    -> (losses, assignment): losses = dict of 0-d device tensors iou_loss (already times reg_weight), conf_loss, cls_loss, l1_loss, num_fg
+    (max(sum num_fg, 1) / max(sum num_gt, 1), the ratio the reference logs: 1.0 with no box at all) and total_loss = the sum of the four losses; assignment = (fg_masks bool,
+    matched_gt_inds int64, matched_ious, num_fg int64) for the mask loss."""
+    if isinstance(origin_preds, (list, tuple)):
+        for k, t in enumerate(origin_preds):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("head_det_loss: origin_preds[%d] is not a tensor" % k)
+            if t.dim() != 3 or t.shape[2] != 4 or t.shape[0] != origin_preds[0].shape[0] or t.dtype != origin_preds[0].dtype \
+                    or t.device != origin_preds[0].device:
+                raise ValueError("head_det_loss: origin_preds[%d] %s %s does not fit a list of (B, A_level, 4) tensors of one dtype and device"
+                                 % (k, tuple(t.shape), t.dtype))
+        if len(origin_preds) == 0:
+            raise ValueError("head_det_loss: origin_preds is an empty list (pass None for use_l1 = False)")
+        origin_preds = torch.cat(list(origin_preds), 1)
+    names = ("outputs", "labels", "x_shifts", "y_shifts", "expanded_strides") + (() if origin_preds is None else ("origin_preds",))
+    ts = (outputs, labels, x_shifts, y_shifts, expanded_strides) + (() if origin_preds is None else (origin_preds,))
+    for n, t in zip(names, ts):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("head_det_loss: %s is not a tensor" % n)
+    for n, t in zip(names, ts):
+        if t.dtype != torch.float32:
+            raise ValueError("head_det_loss: %s is %s; only fp32 is supported (no fp16 / bf16 / autocast inputs)" % (n, t.dtype))
+    Cn = int(num_classes)
+    if outputs.dim() != 3 or labels.dim() != 3 or Cn < 1 or outputs.shape[2] != 5 + Cn or labels.shape[2] != 5 or labels.shape[0] != outputs.shape[0]:
+        raise ValueError("head_det_loss: outputs %s, labels %s do not fit (B, A, 5 + num_classes) and (B, M, 5) with num_classes = %r"
+                         % (tuple(outputs.shape), tuple(labels.shape), num_classes))
+    B, A, _ = outputs.shape
+    if origin_preds is not None and tuple(origin_preds.shape) != (B, A, 4):
+        raise ValueError("head_det_loss: origin_preds %s do not fit (B, A, 4) = (%d, %d, 4)" % (tuple(origin_preds.shape), B, A))
+    xs, ys, st = (_simota_1d(n, t, A).contiguous() for n, t in zip(names[2:5], ts[2:5]))
+    h, w = _simota_img(img_size)
+    if B == 0 or A == 0:
+        raise ValueError("head_det_loss: empty batch or no anchors, outputs %s" % (tuple(outputs.shape),))
+    if assignment is not None:
+        if not isinstance(assignment, (tuple, list)) or len(assignment) != 4 or not all(isinstance(t, torch.Tensor) for t in assignment) \
+                or any(tuple(t.shape) != (B, A) for t in assignment[:3]) or tuple(assignment[3].shape) != (B,) \
+                or assignment[2].dtype != torch.float32:
+            raise ValueError("head_det_loss: assignment is not the (fg_masks (B, A), matched_gt_inds (B, A), matched_ious (B, A) fp32, num_fg (B,)) "
+                             "tuple of simota_assign_batch")
+        names, ts = names + ("assignment",) * 4, ts + tuple(assignment)
+    _simota_dev(ts, names)
+    with torch.no_grad():
+        lab = labels.detach().contiguous()
+        num_gt = (lab.sum(dim=2) > 0).sum(dim=1).to(torch.int32)
+        if assignment is None:
+            fg, matched, iou, num_fg = _simota_call(_hl_rows(outputs.detach(), 5 + Cn), lab, num_gt, xs, ys, st, h, w, Cn)
+            assignment = (fg.bool(), matched.long(), iou, num_fg.long())
+        else:
+            fg, matched, iou, num_fg = (assignment[0].to(torch.uint8), assignment[1].to(torch.int32), assignment[2].detach(),
+                                        assignment[3].to(torch.int32))
+            assignment = tuple(assignment)
+    res = HeadLossFunction.apply(outputs, origin_preds, lab, fg, matched, iou, num_fg, num_gt, xs, ys, st, float(reg_weight))
+    l1 = res[3] if origin_preds is not None else res.new_zeros(())
+    losses = {"total_loss": res[0] + res[1] + res[2] + l1, "iou_loss": res[0], "conf_loss": res[1], "cls_loss": res[2], "l1_loss": l1,
+              "num_fg": res[4].detach()}
+    return losses, assignment
+
+
 _MC_ENTRY = {torch.float32: ("uni_mot_corr_loss_fwd", "uni_mot_corr_loss_bwd", 1),
              torch.float64: ("uni_mot_corr_loss_fwd_f64", "uni_mot_corr_loss_bwd_f64", 2)}
 
