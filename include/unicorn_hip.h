@@ -326,6 +326,47 @@ int uni_head_loss_bwd_f64(const double* outputs, int ld_out, const double* origi
                           const int32_t* num_gt, const double* x_shifts, const double* y_shifts, const double* strides, const double* grad_out,
                           int B, int A, int C, double reg_weight, double* grad_outputs, int ld_grad, double* grad_origin, void* workspace,
                           size_t workspace_bytes, uni_stream_t stream);
+/* The CondInst mask loss of the head for a whole BATCH (unicorn/models/unicorn_head_mask.py:568-569, :675-694, :731-732 with
+ * dynamic_mask_head.py:247-278), forward and backward, fed by the device-side results of uni_simota_assign: 5 launches forward and at most 22
+ * backward whatever the data, B, A, M and capacity, without a host synchronisation, a read-back or an allocation.
+ *   mask_feats [B][H8][W8][8], up_masks [B][H8][W8][9 r r] NHWC;  params [B][A] rows of pitch ldp >= 169;  fpn_levels [B][A] int32
+ *   masks [B][M][r H8][r W8] (0 / 1 maps in the floating type, M >= 1), READ IN PLACE: no per-instance copy of a ground-truth map exists
+ *   fg_mask [B][A] uint8, matched_gt [B][A] int32: what uni_simota_assign wrote (a matched_gt outside 0..M-1 is clamped)
+ *   x_shifts, y_shifts, strides [A]: the instance of anchor a is located at stride (shift + 0.5)
+ *   -> out[1 + B]: out[1 + b] = loss_mask[b] = the mean of uni_condinst_loss_fwd's per-instance loss over the foreground anchors of image b
+ *      in ascending anchor order (an exact 0 without foreground), out[0] = sum_b loss_mask[b] / max(number of images with foreground, 1);
+ *      sums [capacity][3]: the three dice sums per instance slot, for the backward.
+ * The instance table (slot -> image, anchor, mask row; per-image counts and offsets; the number of valid images) is built on the device by
+ * a scan in ascending (image, anchor) order; grids are sized from the geometry and from `capacity`, the number of instance slots the
+ * workspace holds, and blocks loop over the counts they read from the table.  If the batch has MORE foreground anchors than capacity,
+ * nothing is indexed by a slot: out[0 .. B] are NaN and the backward writes exact zeros (visible in the logged loss; never a silent
+ * truncation).  B * min(A, 10 M) can never overflow after uni_simota_assign (a box takes at most 10 anchors).
+ *   uni_head_mask_loss_bwd  given grad_out[1] on the device (the weight of out[0]) and the forward's sums, recomputes the logits and
+ *      writes grad_mask_feats [B][H8][W8][8], grad_up_masks [B][H8][W8][9 r r] and the DENSE grad_params [B][A] rows of pitch
+ *      ld_grad >= 169 (169 columns; background rows and images without foreground: exact zeros) COMPLETELY.  Each may be NULL: that
+ *      gradient is not computed.  One writer per element, fixed summation orders, no atomics: bitwise reproducible.
+ * Limits: 1 <= B <= 65535, A >= 1, B A <= 2^28, M >= 1, up_rate 1..16, H8 W8 r r < 2^30, 1 <= capacity <= 2^24; other shapes are
+ * refused with an error string and uni_head_mask_loss_workspace_bytes returns 0 for them.
+ * workspace: 8-byte aligned device scratch of >= uni_head_mask_loss_workspace_bytes bytes (fp32; the _f64 forms need twice that) =
+ * 4 (4 + 2 B + 4 capacity + B A) for the table, rounded up to 8, plus 4 bytes x [capacity (2 H8 W8 + 3 ceil(H8 W8 / floor(256 / r^2)) +
+ * 169 ceil(H8 W8 / 1024) + 3) + 9 ceil(capacity / 8) H8 W8 + 64 B H8 W8]: O(capacity H8 W8), about 3.5 coarse maps per slot at up_rate 4
+ * (the backward stages its 9 tap sums per pixel in 8 passes over the instance range, which is where the launch count comes from).  Nothing
+ * is kept in it between the two calls.  The _f64 pair is the same templated code in double precision, for gradcheck and fixtures. */
+size_t uni_head_mask_loss_workspace_bytes(int B, int A, int H8, int W8, int up_rate, int capacity);
+int uni_head_mask_loss_fwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const int32_t* fpn_levels, const float* masks, int M,
+    const uint8_t* fg_mask, const int32_t* matched_gt, const float* x_shifts, const float* y_shifts, const float* strides, int B, int A, int H8, int W8,
+    int up_rate, int capacity, float* out, float* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_head_mask_loss_bwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const int32_t* fpn_levels, const float* masks, int M,
+    const uint8_t* fg_mask, const int32_t* matched_gt, const float* x_shifts, const float* y_shifts, const float* strides, int B, int A, int H8, int W8,
+    int up_rate, int capacity, const float* sums, const float* grad_out, float* grad_mask_feats, float* grad_up_masks,
+    float* grad_params, int ld_grad, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_head_mask_loss_fwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const int32_t* fpn_levels, const double* masks, int M,
+    const uint8_t* fg_mask, const int32_t* matched_gt, const double* x_shifts, const double* y_shifts, const double* strides, int B, int A, int H8, int W8,
+    int up_rate, int capacity, double* out, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_head_mask_loss_bwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const int32_t* fpn_levels, const double* masks, int M,
+    const uint8_t* fg_mask, const int32_t* matched_gt, const double* x_shifts, const double* y_shifts, const double* strides, int B, int A, int H8, int W8,
+    int up_rate, int capacity, const double* sums, const double* grad_out, double* grad_mask_feats, double* grad_up_masks,
+    double* grad_params, int ld_grad, void* workspace, size_t workspace_bytes, uni_stream_t stream);
 /* The MOT instance-contrastive loss for TRAINING (unicorn/models/unicorn.py:407-466, compute_loss_mot_corr) for a whole BATCH, forward and
  * backward, in a constant number of launches (5 forward, 8 backward) whatever B, M and the instance counts, without a host
  * synchronisation, a read-back or an allocation.

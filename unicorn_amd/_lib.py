@@ -86,6 +86,15 @@ PROTOS = {
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_head_loss_bwd_f64": (c_i, [c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, C.c_double, c_f, c_i,
                                     c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uni_head_mask_loss_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "uni_head_mask_loss_fwd": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
+    "uni_head_mask_loss_bwd": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f,
+                                     c_i, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uni_head_mask_loss_fwd_f64": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]),
+    "uni_head_mask_loss_bwd_f64": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f,
+                                         c_f, c_i, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_mot_corr_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i]),
     "uni_mot_corr_loss_fwd": (c_i, [c_f, C.POINTER(C.c_int64), c_f, C.POINTER(C.c_int64), c_f, c_i, c_i, c_i, c_i, c_i, C.c_float, c_i, c_f,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -347,6 +347,37 @@ int uni_simota_assign(const float* outputs, int ld_out, const float* labels, con
 }
 static inline McStride mc_stride(const int64_t* s) { return McStride{s[0], s[1], s[2], s[3]}; }
 static const int64_t mc_no_stride[4] = {0, 0, 0, 0};
+size_t uni_head_mask_loss_workspace_bytes(int B, int A, int H8, int W8, int up_rate, int capacity) {
+    return head_mask_loss_workspace_bytes(B, A, H8, W8, up_rate, capacity);
+}
+int uni_head_mask_loss_fwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const int32_t* fpn_levels, const float* masks, int M,
+    const uint8_t* fg_mask, const int32_t* matched_gt, const float* x_shifts, const float* y_shifts, const float* strides, int B, int A, int H8, int W8,
+    int up_rate, int capacity, float* out, float* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides && workspace && out && sums, "head_mask_loss_fwd: NULL argument");
+    API(launch_head_mask_loss_fwd(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, out, sums, workspace, workspace_bytes, S(stream)));
+}
+int uni_head_mask_loss_bwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const int32_t* fpn_levels, const float* masks, int M,
+    const uint8_t* fg_mask, const int32_t* matched_gt, const float* x_shifts, const float* y_shifts, const float* strides, int B, int A, int H8, int W8,
+    int up_rate, int capacity, const float* sums, const float* grad_out, float* grad_mask_feats, float* grad_up_masks,
+    float* grad_params, int ld_grad, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides && workspace && sums && grad_out, "head_mask_loss_bwd: NULL argument");
+    API(launch_head_mask_loss_bwd(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, sums, grad_out, grad_mask_feats, grad_up_masks, grad_params, ld_grad, workspace,
+                                  workspace_bytes, S(stream)));
+}
+int uni_head_mask_loss_fwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const int32_t* fpn_levels, const double* masks, int M,
+    const uint8_t* fg_mask, const int32_t* matched_gt, const double* x_shifts, const double* y_shifts, const double* strides, int B, int A, int H8, int W8,
+    int up_rate, int capacity, double* out, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides && workspace && out && sums, "head_mask_loss_fwd_f64: NULL argument");
+    API(launch_head_mask_loss_fwd_f64(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, out, sums, workspace, workspace_bytes, S(stream)));
+}
+int uni_head_mask_loss_bwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const int32_t* fpn_levels, const double* masks, int M,
+    const uint8_t* fg_mask, const int32_t* matched_gt, const double* x_shifts, const double* y_shifts, const double* strides, int B, int A, int H8, int W8,
+    int up_rate, int capacity, const double* sums, const double* grad_out, double* grad_mask_feats, double* grad_up_masks,
+    double* grad_params, int ld_grad, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides && workspace && sums && grad_out, "head_mask_loss_bwd_f64: NULL argument");
+    API(launch_head_mask_loss_bwd_f64(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, sums, grad_out, grad_mask_feats, grad_up_masks, grad_params, ld_grad, workspace,
+                                  workspace_bytes, S(stream)));
+}
 size_t uni_mot_corr_workspace_bytes(int B, int M, int C) { return mot_corr_workspace_bytes(B, M, C); }
 int uni_mot_corr_loss_fwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
                           int B, int C, int H, int W, int M, float stride, int flags, float* loss, void* workspace, size_t workspace_bytes,

@@ -253,6 +253,27 @@ int launch_head_loss_bwd_f64(const double* outputs, int ld, const double* origin
                              const int* mg, const double* miou, const int* num_fg, const int* num_gt, const double* xs, const double* ys,
                              const double* st, const double* gout, int B, int A, int C, double reg_weight, double* g_out, int ldg,
                              double* g_org, void* ws, size_t ws_bytes, hipStream_t s);
+// head_mask_loss.hip: the CondInst mask loss of get_losses (unicorn_head_mask.py:568-569, :675-694, :731-732) for a batch from the device-side
+// results of launch_simota_assign, forward + recomputing backward, fp32 and fp64, 5 launches forward and at most 22 backward, no host read-back.
+// mf [B][H][W][8], um [B][H][W][9 r r], params [B][A][ldp >= 169], lvl [B][A], masks [B][M][rH][rW] (read in place through mg), fg / mg [B][A],
+// xs / ys / st [A] -> out[1 + B] = loss_condinst, loss_mask[B]; sums [cap][3] for the backward.  The backward writes gmf [B][H][W][8],
+// gum [B][H][W][9 r r], gpar [B][A][ldg >= 169] (169 columns) completely; each may be NULL.  More foreground anchors than cap: NaN losses, zero
+// gradients.  Workspace: head_mask_loss_workspace_bytes for fp32, twice that for fp64; scratch between calls.
+size_t head_mask_loss_workspace_bytes(int B, int A, int H, int W, int r, int cap);
+int launch_head_mask_loss_fwd(const float* mf, const float* um, const float* params, int ldp, const int* lvl, const float* masks, int M,
+                              const unsigned char* fg, const int* mg, const float* xs, const float* ys, const float* st, int B, int A, int H,
+                              int W, int r, int cap, float* out, float* sums, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_head_mask_loss_bwd(const float* mf, const float* um, const float* params, int ldp, const int* lvl, const float* masks, int M,
+                              const unsigned char* fg, const int* mg, const float* xs, const float* ys, const float* st, int B, int A, int H,
+                              int W, int r, int cap, const float* sums, const float* gout, float* gmf, float* gum, float* gpar, int ldg,
+                              void* ws, size_t ws_bytes, hipStream_t s);
+int launch_head_mask_loss_fwd_f64(const double* mf, const double* um, const double* params, int ldp, const int* lvl, const double* masks, int M,
+                                  const unsigned char* fg, const int* mg, const double* xs, const double* ys, const double* st, int B, int A,
+                                  int H, int W, int r, int cap, double* out, double* sums, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_head_mask_loss_bwd_f64(const double* mf, const double* um, const double* params, int ldp, const int* lvl, const double* masks, int M,
+                                  const unsigned char* fg, const int* mg, const double* xs, const double* ys, const double* st, int B, int A,
+                                  int H, int W, int r, int cap, const double* sums, const double* gout, double* gmf, double* gum,
+                                  double* gpar, int ldg, void* ws, size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

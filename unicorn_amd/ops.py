@@ -664,6 +664,137 @@ def head_det_loss(outputs, origin_preds, labels, x_shifts, y_shifts, expanded_st
     return losses, assignment
 
 
+_HM_ENTRY = {torch.float32: ("uni_head_mask_loss_fwd", "uni_head_mask_loss_bwd", 1),
+             torch.float64: ("uni_head_mask_loss_fwd_f64", "uni_head_mask_loss_bwd_f64", 2)}
+
+
+def _hm_ws(dev, dtype, B, A, H8, W8, r, cap):
+    need = L.lib().uni_head_mask_loss_workspace_bytes(B, A, H8, W8, r, cap)
+    if need == 0:
+        raise L.UnicornHipError("head_mask_loss: shape B=%d A=%d H8=%d W8=%d up_rate=%d capacity=%d is outside the limits of "
+                                "uni_head_mask_loss_fwd (include/unicorn_hip.h)" % (B, A, H8, W8, r, cap))
+    return torch.empty(need * _HM_ENTRY[dtype][2], device=dev, dtype=torch.uint8)      # the fp64 forms need twice the fp32 size
+
+
+class HeadMaskLossFunction(torch.autograd.Function):
+    """The CondInst mask loss of get_losses (unicorn_head_mask.py:568-569, :675-694, :731-732) for the whole batch from the device-side
+    assignment, differentiable in the two maps and the parameters: apply(mask_feats (B, H8, W8, 8), up_masks (B, H8, W8, 9 r r),
+    params (B, A, 169) rows of any pitch >= 169, fpn_levels (B, A) int32, masks (B, M, r H8, r W8), fg (B, A) uint8, matched (B, A) int32,
+    xs, ys, st (A,), up_rate, capacity) -> (1 + B,) = loss_condinst, loss_mask per image.  All floating-point tensors fp32, or all fp64,
+    contiguous (head_mask_loss checks and converts).  Saves the inputs and three sums per instance slot; the backward recomputes.  No host
+    synchronisation in either direction: the instance table is built on the device, `capacity` only sizes the workspace and the grids.  One
+    writer per gradient element: bitwise reproducible.  More foreground anchors than capacity: NaN losses and zero gradients."""
+
+    @staticmethod
+    def forward(ctx, mask_feats, up_masks, params, fpn_levels, masks, fg, matched, xs, ys, st, up_rate, capacity):
+        B, H8, W8, _ = mask_feats.shape
+        A, M, r, cap = params.shape[1], masks.shape[1], int(up_rate), int(capacity)
+        dev, dt = params.device, params.dtype
+        fwd = _HM_ENTRY[dt][0]
+        out = torch.empty((1 + B,), device=dev, dtype=dt)
+        sums = torch.empty((cap, 3), device=dev, dtype=dt)
+        with torch.cuda.device(dev):
+            ws = _hm_ws(dev, dt, B, A, H8, W8, r, cap)
+            L.check(getattr(L.lib(), fwd)(L.ptr(mask_feats), L.ptr(up_masks), L.ptr(params), params.stride(1), L.ptr(fpn_levels), L.ptr(masks), M,
+                                          L.ptr(fg), L.ptr(matched), L.ptr(xs), L.ptr(ys), L.ptr(st), B, A, H8, W8, r, cap, L.ptr(out),
+                                          L.ptr(sums), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
+        ctx.save_for_backward(mask_feats, up_masks, params, fpn_levels, masks, fg, matched, xs, ys, st, sums)
+        ctx.up_rate, ctx.capacity = r, cap
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        mf, um, p, lvl, masks, fg, matched, xs, ys, st, sums = ctx.saved_tensors
+        B, H8, W8, _ = mf.shape
+        A, M, r, cap = p.shape[1], masks.shape[1], ctx.up_rate, ctx.capacity
+        bwd = _HM_ENTRY[p.dtype][1]
+        # all three are written completely by the call
+        gmf = torch.empty_like(mf) if ctx.needs_input_grad[0] else None
+        gum = torch.empty_like(um) if ctx.needs_input_grad[1] else None
+        gp = torch.empty((B, A, 169), device=p.device, dtype=p.dtype) if ctx.needs_input_grad[2] else None
+        if gmf is not None or gum is not None or gp is not None:
+            g = grad_out[:1].contiguous()                    # the per-image losses are returned detached
+            with torch.cuda.device(p.device):
+                ws = _hm_ws(p.device, p.dtype, B, A, H8, W8, r, cap)
+                L.check(getattr(L.lib(), bwd)(L.ptr(mf), L.ptr(um), L.ptr(p), p.stride(1), L.ptr(lvl), L.ptr(masks), M, L.ptr(fg), L.ptr(matched),
+                                              L.ptr(xs), L.ptr(ys), L.ptr(st), B, A, H8, W8, r, cap, L.ptr(sums), L.ptr(g), L.ptr(gmf), L.ptr(gum),
+                                              L.ptr(gp), 169, L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
+        return (gmf, gum, gp) + (None,) * 9
+
+
+def head_mask_loss(mask_feats, up_masks, dynamic_params, fpn_levels, masks, assignment, x_shifts, y_shifts, expanded_strides, up_rate,
+                   capacity=None):
+    """The CondInst lines of get_losses (unicorn_head_mask.py:568-569, :675-694, :731-732) for the WHOLE batch without a host
+    synchronisation, fed by what simota_assign_batch / head_det_loss leave on the device: mask_feats (B, 8, H8, W8), up_masks
+    (B, 9 r r, H8, W8), dynamic_params (B, A, 169) (a view of wider rows is read in place), fpn_levels (B, A) integer, masks
+    (B, M, r H8, r W8) floating 0 / 1 maps read in place through matched_gt_inds (no per-instance copy), assignment = (fg_masks,
+    matched_gt_inds, matched_ious, num_fgs), x_shifts / y_shifts / expanded_strides (1, A) or (A,).  All floating tensors fp32, or all fp64.
+    -> (loss_condinst, per_image): loss_condinst = sum_b loss_mask[b] / max(number of images with foreground, 1), differentiable in
+    mask_feats, up_masks and dynamic_params (dense gradients; background rows and images without foreground get exact zeros); per_image =
+    the detached (B,) loss_mask.  `masks is None` is the caller's business (no call, loss 0).
+    capacity: the number of instance slots the workspace (O(capacity H8 W8), include/unicorn_hip.h) and the grids are sized for; default
+    B * min(A, 10 M), which SimOTA cannot exceed.  A caller who knows the data passes less.  More foreground anchors than capacity: both
+    results are NaN and the gradients zero -- visible in the logged loss, never a silent truncation, and no read-back to raise."""
+    names = ("mask_feats", "up_masks", "dynamic_params", "masks", "x_shifts", "y_shifts", "expanded_strides", "fpn_levels")
+    ts = (mask_feats, up_masks, dynamic_params, masks, x_shifts, y_shifts, expanded_strides, fpn_levels)
+    for n, t in zip(names, ts):
+        if not isinstance(t, torch.Tensor):
+            raise L.UnicornHipError("head_mask_loss: %s is not a tensor" % n)
+    if not isinstance(assignment, (tuple, list)) or len(assignment) != 4 or not all(isinstance(t, torch.Tensor) for t in assignment):
+        raise L.UnicornHipError("head_mask_loss: assignment is not the (fg_masks, matched_gt_inds, matched_ious, num_fgs) tuple of "
+                                "simota_assign_batch / head_det_loss")
+    fg, matched = assignment[0], assignment[1]
+    r = int(up_rate)
+    if mask_feats.dim() != 4 or mask_feats.shape[1] != 8 or dynamic_params.dim() != 3 or dynamic_params.shape[2] != 169 or r < 1 or r > 16 \
+            or dynamic_params.shape[0] != mask_feats.shape[0] or tuple(up_masks.shape) != (mask_feats.shape[0], 9 * r * r) + tuple(mask_feats.shape[2:]):
+        raise L.UnicornHipError("head_mask_loss: shapes %s, up_rate %r do not fit mask_feats (B,8,H8,W8), up_masks (B,9 r r,H8,W8), "
+                                "dynamic_params (B,A,169), up_rate 1..16" % ([tuple(t.shape) for t in ts[:3]], up_rate))
+    B, _, H8, W8 = mask_feats.shape
+    A = dynamic_params.shape[1]
+    if masks.dim() != 4 or masks.shape[0] != B or tuple(masks.shape[2:]) != (r * H8, r * W8):
+        raise L.UnicornHipError("head_mask_loss: masks %s do not fit (B, M, r H8, r W8) = (%d, M, %d, %d): the ground truth must be exactly "
+                                "up_rate x the feature map" % (tuple(masks.shape), B, r * H8, r * W8))
+    if tuple(fpn_levels.shape) != (B, A) or tuple(fg.shape) != (B, A) or tuple(matched.shape) != (B, A):
+        raise L.UnicornHipError("head_mask_loss: fpn_levels %s, fg_masks %s, matched_gt_inds %s do not fit (B, A) = (%d, %d)"
+                                % (tuple(fpn_levels.shape), tuple(fg.shape), tuple(matched.shape), B, A))
+    dt = dynamic_params.dtype
+    if dt not in _HM_ENTRY or any(t.dtype != dt for t in ts[:7]):
+        raise L.UnicornHipError("head_mask_loss: dtypes %s unsupported (all fp32 or all fp64; no fp16 / bf16)" % [str(t.dtype) for t in ts[:7]])
+    if fpn_levels.dtype.is_floating_point or fpn_levels.dtype == torch.bool or matched.dtype.is_floating_point or matched.dtype == torch.bool \
+            or fg.dtype.is_floating_point:
+        raise L.UnicornHipError("head_mask_loss: fpn_levels %s / matched_gt_inds %s must be integer tensors and fg_masks %s bool or integer"
+                                % (fpn_levels.dtype, matched.dtype, fg.dtype))
+    try:
+        xs, ys, st = (_simota_1d(n, t, A) for n, t in zip(names[4:7], ts[4:7]))
+    except ValueError as e:
+        raise L.UnicornHipError(str(e).replace("simota_assign", "head_mask_loss"))
+    M = masks.shape[1]
+    if capacity is None:
+        cap = max(B * min(A, 10 * M), 1)
+    else:
+        cap = int(capacity)
+        if cap < 1:
+            raise L.UnicornHipError("head_mask_loss: capacity %r must be a positive number of instance slots" % (capacity,))
+    _need_cuda(*ts, fg, matched)
+    if len({t.device for t in ts + (fg, matched)}) != 1:
+        raise L.UnicornHipError("head_mask_loss: tensors on different devices")
+    if B == 0 or A == 0:
+        zero = (mask_feats.sum() + up_masks.sum() + dynamic_params.sum()) * 0.0
+        return zero, dynamic_params.new_zeros((B,))
+    if H8 == 0 or W8 == 0 or M == 0:
+        raise L.UnicornHipError("head_mask_loss: empty feature map or no ground-truth rows, mask_feats %s, masks %s"
+                                % (tuple(mask_feats.shape), tuple(masks.shape)))
+    mf = mask_feats.permute(0, 2, 3, 1).contiguous()
+    um = up_masks.permute(0, 2, 3, 1).contiguous()
+    p = dynamic_params if dynamic_params.stride(2) == 1 and dynamic_params.stride(1) >= 169 \
+        and dynamic_params.stride(0) == A * dynamic_params.stride(1) else dynamic_params.contiguous()      # a row pitch (ldp) is passed through
+    out = HeadMaskLossFunction.apply(mf, um, p, fpn_levels.to(torch.int32).contiguous(), masks.detach().contiguous(),
+                                     fg.to(torch.uint8).contiguous(), matched.to(torch.int32).contiguous(), xs.detach().contiguous(),
+                                     ys.detach().contiguous(), st.detach().contiguous(), r, cap)
+    return out[0], out[1:].detach()
+
+
 _MC_ENTRY = {torch.float32: ("uni_mot_corr_loss_fwd", "uni_mot_corr_loss_bwd", 1),
              torch.float64: ("uni_mot_corr_loss_fwd_f64", "uni_mot_corr_loss_bwd_f64", 2)}
 
