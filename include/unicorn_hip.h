@@ -74,6 +74,15 @@ typedef struct uni_model_cfg {
 
 const char* uni_last_error(void);
 int uni_version(void);
+/* Variant trace (tests / tools): which kernel instantiation did a call run?  Every launcher of the library reports the launch it is about
+ * to make as a short tag: launcher, kernel and template arguments, operand format and every launch-uniform switch that changes the
+ * index arithmetic or the store path inside the kernel (the tag does not depend on HOW the variant was chosen: heuristic, force_cfg or an
+ * environment switch).  Process-global, off by default (then a launch pays one relaxed atomic load), safe to use from several threads.
+ * uni_variant_trace(1) clears the recorded tags and starts recording, uni_variant_trace(0) stops (the tags stay readable); returns 0. */
+int uni_variant_trace(int on);
+/* Writes the recorded tags as "tag\tcount\n" lines, sorted by tag, NUL-terminated and truncated to cap bytes (buf may be NULL);
+ * returns the bytes needed for the whole text including the NUL. */
+size_t uni_variant_trace_read(char* buf, size_t cap);
 
 /* ---- context / weights ------------------------------------------------------------------------- */
 uni_ctx* uni_ctx_create(int device_id, const uni_model_cfg* cfg);
@@ -501,6 +510,15 @@ int uni_mlp_fused(const void* a_h2, int lda, const void* blob_dev, const float* 
                   uni_stream_t stream);
 int uni_layernorm(const float* x, int ldx, const float* gamma, const float* beta, float eps, int M, int C, float* outF,
                   uint16_t* outB, uni_stream_t stream);
+/* Every mode of the row LayerNorm the engine uses, without a context (fmt: 0 = bf16, 1 = fp32, 2 = f16x2 operand rows in out_op).
+ *   out_f32 (optional, ld ldf): fp32 rows.  pair_hw > 0: the rows are tokens [B][2 frames][pair_hw] and the fp32 rows of frame 0 go to
+ *     out_f32, those of frame 1 to out_f32_2, both as [B][pair_hw] maps (M a multiple of 2 pair_hw); otherwise out_f32_2 = NULL.
+ *   out_op (optional, ld ldb): operand rows in fmt.  ps_h, ps_w > 0: the rows are the pixels of a map ps_w wide and out_op receives
+ *     PixelShuffle(2) of it, a dense (2 M / ps_w, 2 ps_w, C / 4) map (ldb unused; unicorn.py:41).  Only ps_w enters the addressing: the
+ *     output row is 2 (row / ps_w), so stacked (ps_h, ps_w) maps simply extend the height; ps_h switches the mode on and M must be a
+ *     multiple of ps_h * ps_w. */
+int uni_layernorm_ex(const float* x, int ldx, const float* gamma, const float* beta, float eps, int M, int C, float* out_f32, int ldf,
+                     float* out_f32_2, int pair_hw, void* out_op, int ldb, int ps_h, int ps_w, int fmt, uni_stream_t stream);
 int uni_dwconv7_ln(const float* x_nhwc, const float* w49c, const float* bias, const float* gamma, const float* beta,
                    float eps, int H, int W, int C, uint16_t* out_bf16, uni_stream_t stream);
 /* The same for B stacked (H,W,C) maps and any operand format (what the engine calls per ConvNeXt block): fmt 0 = bf16 rows, 1 = fp32
@@ -515,8 +533,28 @@ int uni_dwconv7_ln_ex(const float* x_nhwc, const float* w49c, const float* bias,
 int uni_msda_tokens(const float* value, const float* offaw, int ldo, int B, int h, int w, float* out, uni_stream_t stream);
 int uni_groupnorm_act(const float* x, const double* stats, const float* gamma, const float* beta, float eps, int M,
                       int C, int G, int act, float* outF, uint16_t* outB, uni_stream_t stream);
+/* Every mode of the GroupNorm apply the engine uses, without a context: B samples of M rows each (x, outputs: [B * M] rows), the group
+ * sums (sum, sum of squares per group, G <= 32) of sample b at stats + 64 b.  y = act(GroupNorm(x)) (+ prior[row] * prior_beta[c] when
+ * both are given, unicorn_head.py:272-277) -> out_f32 (fp32, ld ldf) and / or out_op (operand rows in fmt, ld ldb) and / or out_up: the
+ * 2x nearest-neighbour copy of every sample's (M / W, W) map into a (2 M / W, 2 W) map of operand rows (ld ldu).  fmt as above; the
+ * bf16 / f16x2 formats use the reciprocal-based activations of the GEMM epilogues, fp32 the exact ones. */
+int uni_groupnorm_act_ex(const float* x, int ldx, const double* stats, const float* gamma, const float* beta, float eps, int B, int M,
+                         int C, int G, int act, const float* prior, const float* prior_beta, float* out_f32, int ldf, void* out_op,
+                         int ldb, void* out_up, int ldu, int W, int fmt, uni_stream_t stream);
 int uni_stem(const float* img, int H, int W, const float* w48c, const float* bias, const float* gamma,
              const float* beta, int C, float* out_nhwc, uni_stream_t stream);
+/* The same for a batch: img (B, 3, H, W) -> out (B, H / 4, W / 4, C) (what the engine calls for B frames). */
+int uni_stem_ex(const float* img, int B, int H, int W, const float* w48c, const float* bias, const float* gamma, const float* beta, int C,
+                float* out_nhwc, uni_stream_t stream);
+/* uni_gemm_bf16 / uni_gemm_h2 for any operand format, plus the activation window the engine uses on the head outputs: fmt 0 = bf16,
+ * 1 = exact fp32 (a, out_op: fp32 rows; w_packed: [ceil(N / 256) * 256][ceil(K / 64) * 64] fp32, zero padded, k = (ky * KW + kx) * Cin + c;
+ * wscale unused), 2 = f16x2 (uni_cast_h2 / uni_pack_weight_h2).  act applies to the columns >= act_col0 only (0: every column).
+ * force_cfg: 0 or a tile configuration (no ablation bits, no split-K: those stay with uni_gemm_h2).  Other arguments as uni_gemm_bf16.
+ * uni_cast_f32: the operand cast in the fp32 format (a strided copy). */
+int uni_gemm_ex(const void* a, int lda, const void* w_packed, float wscale, int fmt, int M, int N, int Hin, int Win, int Cin, int KH, int KW,
+                int stride, int pad, const float* bias, int act, int act_col0, const float* residual, int ldr, float* out_f32, int ldf,
+                void* out_op, int ldb, double* gn_stats, int cpg, int force_cfg, uni_stream_t stream);
+int uni_cast_f32(const float* x, int ldx, float* out, int ldo, int M, int C, uni_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -489,6 +489,104 @@ def test_groupnorm_act(L, C_, Gn, act):
     G.record("uni_groupnorm_act", "act %d, fp32 + bf16 outputs" % act, "M=%d C=%d G=%d" % (M, C_, Gn), {}, [gx, gs, gg, gb, oF, oB])
 
 
+def _op_dtype(fmt):
+    return torch.bfloat16 if fmt == 0 else (torch.int32 if fmt == 2 else torch.float32)
+
+
+def _op_decode(buf, fmt):
+    return h2_decode(buf, buf.shape[0], buf.shape[1]).double() if fmt == 2 else buf.double()
+
+
+@pytest.mark.parametrize("mode,C_,fmt", [("ps", 192, 2), ("ps", 768, 0), ("pair", 256, 2), ("pair", 256, 1)])
+def test_layernorm_ex(L, mode, C_, fmt):
+    """uni_layernorm_ex: the PixelShuffle scatter of the operand rows (three stacked (7, 5) maps -> a dense (42, 10, C / 4) map) and the
+    frame-pair remap of the fp32 rows (tokens [3][2][35]: even frames -> out_f32, odd frames -> out_f32_2, operand rows unremapped), padded
+    pitches on every strided buffer; bounds of test_layernorm (fp32 2e-5, bf16 8e-3) and format 2 of test_dwconv7_ln_batched_all_formats"""
+    B, h, w, hw = 3, 7, 5, 35
+    M = B * h * w if mode == "ps" else B * 2 * hw
+    g = torch.Generator().manual_seed(C_ + fmt)
+    ldx, ldf, ldb = C_ + 4, C_ + 4, C_ + 8
+    x = torch.randn(M, C_, generator=g) * 3 + 1.5
+    ga, be = torch.randn(C_, generator=g), torch.randn(C_, generator=g)
+    exp = F.layer_norm(x.double(), (C_,), ga.double(), be.double(), 1e-6)
+    big = exp.abs().max().item()
+    xd, gd, bd = x.cuda(), ga.cuda(), be.cuda()
+    dt = _op_dtype(fmt)
+    rows_f = B * hw
+    rows_b, cols_b = (4 * M, C_ // 4) if mode == "ps" else (M, C_)
+
+    def call(x_, ldx_, g_, b_, oF, ldf_, oF2, oB, ldb_):
+        return L.lib().uni_layernorm_ex(P(x_), ldx_, P(g_), P(b_), 1e-6, M, C_, P(oF), ldf_, P(oF2), hw if mode == "pair" else 0, P(oB), ldb_,
+                                        h if mode == "ps" else 0, w if mode == "ps" else 0, fmt, L.stream_ptr())
+    pF = torch.zeros((rows_f, C_), device=DEV) if mode == "pair" else None
+    pF2 = torch.zeros((rows_f, C_), device=DEV) if mode == "pair" else None
+    pB = torch.zeros((rows_b, cols_b), device=DEV, dtype=dt)
+    L.check(call(xd, C_, gd, bd, pF, C_, pF2, pB, C_), "layernorm_ex")
+    gx, gg, gb = gin("x", xd, ld=ldx), gin("gamma", gd), gin("beta", bd)
+    oF = gout("out_f32", rows_f, C_, torch.float32, ld=ldf) if mode == "pair" else None
+    oF2 = gout("out_f32_2", rows_f, C_, torch.float32, ld=ldf) if mode == "pair" else None
+    oB = gout("out_op", rows_b, cols_b, dt) if mode == "ps" else gout("out_op", rows_b, cols_b, dt, ld=ldb)      # the shuffled map is dense
+    L.check(call(gx, ldx, gg, gb, oF, ldf, oF2, oB, ldb), "layernorm_ex")
+    sync_check(gx, gg, gb, oF, oF2, oB)
+    oB.check_equal(pB)
+    if mode == "pair":
+        oF.check_equal(pF)
+        oF2.check_equal(pF2)
+        e = exp.reshape(B, 2, hw, C_)
+        assert (oF.payload().cpu().double() - e[:, 0].reshape(rows_f, C_)).abs().max() < 2e-5 * big
+        assert (oF2.payload().cpu().double() - e[:, 1].reshape(rows_f, C_)).abs().max() < 2e-5 * big
+        eb = exp
+    else:
+        eb = F.pixel_shuffle(exp.reshape(1, B * h, w, C_).permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1).reshape(rows_b, cols_b)
+    tol = 8e-3 * big if fmt == 0 else 2e-5 * max(1.0, big)
+    assert (_op_decode(oB.payload(), fmt).cpu() - eb).abs().max() < tol
+    G.record("uni_layernorm_ex", "%s, fmt %d" % (mode, fmt), "M=%d C=%d" % (M, C_), {"ldx": ldx, "ldf": ldf, "ldb": ldb}, [gx, gg, gb, oF, oF2, oB])
+
+
+@pytest.mark.parametrize("fmt", [2, 0])
+def test_groupnorm_act_ex_upsampled_copy(L, fmt):
+    """uni_groupnorm_act_ex: three samples with their own statistics slots, the prior fusion, fp32 + operand rows + the 2x nearest copy of
+    every (47, 13) map into a (94, 26) map whose pitch is wider than C; bounds of test_groupnorm_act (fp32 1e-4), test_layernorm (bf16 8e-3)
+    and format 2 of test_dwconv7_ln_batched_all_formats"""
+    C_, Gn, act, B, W, H = 96, 16, 3, 3, 13, 47
+    M, eps = H * W, 1e-3
+    g = torch.Generator().manual_seed(C_ + fmt)
+    x = torch.randn(B, M, C_, generator=g) * (1.0 + torch.arange(B).float().reshape(B, 1, 1)) + 0.5
+    ga, be = torch.randn(C_, generator=g), torch.randn(C_, generator=g)
+    prior, pbeta = torch.rand(B * M, generator=g), torch.randn(C_, generator=g)
+    xs = x.double()
+    grp = xs.reshape(B, M, Gn, C_ // Gn)
+    stats = torch.zeros(B, 64, dtype=torch.float64)
+    stats[:, 0:2 * Gn:2], stats[:, 1:2 * Gn:2] = grp.sum((1, 3)), (grp ** 2).sum((1, 3))
+    exp = ACTS[act](F.group_norm(xs.permute(0, 2, 1).unsqueeze(-1), Gn, ga.double(), be.double(), eps)).squeeze(-1).permute(0, 2, 1)
+    exp = (exp + prior.double().reshape(B, M, 1) * pbeta.double()).reshape(B * M, C_)
+    eup = exp.reshape(B, H, W, C_).repeat_interleave(2, 1).repeat_interleave(2, 2).reshape(4 * B * M, C_)
+    scale = max(1.0, exp.abs().max().item())
+    xd, sd, gd, bd, pd, pbd = x.reshape(B * M, C_).cuda(), stats.cuda(), ga.cuda(), be.cuda(), prior.cuda(), pbeta.cuda()
+    dt = _op_dtype(fmt)
+    ldx, ldf, ldb, ldu = C_ + 4, C_ + 4, C_ + 8, C_ + 32
+
+    def call(x_, ldx_, s_, g_, b_, p_, pb_, oF, ldf_, oB, ldb_, oU, ldu_):
+        return L.lib().uni_groupnorm_act_ex(P(x_), ldx_, P(s_), P(g_), P(b_), eps, B, M, C_, Gn, act, P(p_), P(pb_), P(oF), ldf_, P(oB), ldb_, P(oU), ldu_,
+                                            W, fmt, L.stream_ptr())
+    pF = torch.zeros((B * M, C_), device=DEV)
+    pB, pU = torch.zeros((B * M, C_), device=DEV, dtype=dt), torch.zeros((4 * B * M, C_), device=DEV, dtype=dt)
+    L.check(call(xd, C_, sd, gd, bd, pd, pbd, pF, C_, pB, C_, pU, C_), "groupnorm_act_ex")
+    gx, gs, gg, gb, gp, gpb = gin("x", xd, ld=ldx), gin("stats", sd), gin("gamma", gd), gin("beta", bd), gin("prior", pd), gin("prior_beta", pbd)
+    oF, oB, oU = gout("out_f32", B * M, C_, torch.float32, ld=ldf), gout("out_op", B * M, C_, dt, ld=ldb), gout("out_up", 4 * B * M, C_, dt, ld=ldu)
+    L.check(call(gx, ldx, gs, gg, gb, gp, gpb, oF, ldf, oB, ldb, oU, ldu), "groupnorm_act_ex")
+    sync_check(gx, gs, gg, gb, gp, gpb, oF, oB, oU)
+    oF.check_equal(pF)
+    oB.check_equal(pB)
+    oU.check_equal(pU)
+    tol = (8e-3 if fmt == 0 else 2e-5) * scale
+    assert (oF.payload().cpu().double() - exp).abs().max() < 1e-4 * scale
+    assert (_op_decode(oB.payload(), fmt).cpu() - exp).abs().max() < tol
+    assert (_op_decode(oU.payload(), fmt).cpu() - eup).abs().max() < tol
+    G.record("uni_groupnorm_act_ex", "prior + outUp, fmt %d" % fmt, "B=%d M=%d C=%d G=%d W=%d" % (B, M, C_, Gn, W),
+             {"ldx": ldx, "ldf": ldf, "ldb": ldb, "ldu": ldu}, [gx, gs, gg, gb, gp, gpb, oF, oB, oU])
+
+
 @pytest.mark.parametrize("W", [96, 100])          # W % 16 == 0: 4-pixel kernel, otherwise the 1-pixel fallback
 @pytest.mark.parametrize("C_", [96, 192])
 def test_stem(L, C_, W):

@@ -235,7 +235,7 @@ def test_layernorm(L, C_):
 
 @pytest.mark.parametrize("shape", [(96, 20, 24), (192, 13, 10), (256, 25, 40), (384, 9, 16), (768, 10, 10), (1536, 5, 8),
                                    (192, 101, 163), (192, 151, 163), (768, 49, 83),     # 8-px and 2-row variants
-                                   (768, 127, 163), (256, 207, 323), (192, 261, 317), (384, 255, 163)])   # persistent LDS-weight variant (in-wave / LDS reduction)
+                                   (768, 127, 163), (256, 207, 323), (192, 261, 317), (384, 255, 163)])   # persistent LDS-weight variant (in-wave / LDS reduction): 2-row strips in all four (C = 256 falls back from 4 rows), 12 waves for C = 768 / 384, unpacked 8 waves for C = 192
 def test_dwconv7_ln(L, shape):
     C_, H, W = shape
     g = torch.Generator().manual_seed(C_ + H)
@@ -276,8 +276,11 @@ def _dwln_decode(out, fmt, M, C_):
                                    (192, 3, 150, 323), (384, 3, 127, 163), (192, 2, 201, 320)])      # packed-lane strip groups (ragged last group, full rows)
 def test_dwconv7_ln_batched_all_formats(L, shape, fmt):
     """uni_dwconv7_ln_ex = the call the engine makes per ConvNeXt block: B stacked maps, every operand format (bf16 / fp32 / f16x2 rows),
-    widths that are no multiple of the 8-px strips, odd heights (2- and 4-row kernels), against torch's depthwise conv + LayerNorm;
-    samples must not leak into each other (zero padding between stacked maps)."""
+    widths that are no multiple of the 8-px strips, odd heights, against torch's depthwise conv + LayerNorm; samples must not leak into
+    each other (zero padding between stacked maps).  Which kernel a shape runs is NOT asserted here: (256, 3, 57, 90) and (512, 5, 33, 70)
+    have too few strips for the LDS-weight kernels and run the plain 2-row kernel (dwconv7_ln2), no row of this table reaches a 4-row
+    instantiation.  tests/test_variant_census_gpu.py pins one case to every instantiation the engine dispatches or a documented switch
+    reaches (DESIGN.md section 5 names the ablation builds it leaves out) and asserts the variant each case ran."""
     C_, B, H, W = shape
     g = torch.Generator().manual_seed(C_ + H + B)
     x = torch.randn(B, C_, H, W, generator=g)

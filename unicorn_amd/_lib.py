@@ -19,6 +19,8 @@ class ModelCfg(C.Structure):
 PROTOS = {
     "uni_last_error": (C.c_char_p, []),
     "uni_version": (c_i, []),
+    "uni_variant_trace": (c_i, [c_i]),
+    "uni_variant_trace_read": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "uni_ctx_create": (C.c_void_p, [c_i, C.POINTER(ModelCfg)]),
     "uni_ctx_destroy": (None, [C.c_void_p]),
     "uni_ctx_load_param": (c_i, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), c_i]),
@@ -121,10 +123,17 @@ PROTOS = {
     "uni_mlp_pack": (c_i, [C.c_void_p, C.c_void_p, C.c_void_p, c_i, c_i, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "uni_mlp_fused": (c_i, [c_f, c_i, c_f, c_f, c_f, C.c_float, C.c_float, c_f, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p]),
     "uni_layernorm": (c_i, [c_f, c_i, c_f, c_f, C.c_float, c_i, c_i, c_f, c_f, C.c_void_p]),
+    "uni_layernorm_ex": (c_i, [c_f, c_i, c_f, c_f, C.c_float, c_i, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, C.c_void_p]),
     "uni_dwconv7_ln": (c_i, [c_f, c_f, c_f, c_f, c_f, C.c_float, c_i, c_i, c_i, c_f, C.c_void_p]),
     "uni_dwconv7_ln_ex": (c_i, [c_f, c_f, c_f, c_f, c_f, C.c_float, c_i, c_i, c_i, c_i, c_f, c_i, C.c_void_p]),
     "uni_msda_tokens": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
     "uni_groupnorm_act": (c_i, [c_f, c_f, c_f, c_f, C.c_float, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p]),
+    "uni_groupnorm_act_ex": (c_i, [c_f, c_i, c_f, c_f, c_f, C.c_float, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_f, c_i, c_f, c_i, c_i, c_i,
+                                   C.c_void_p]),
+    "uni_stem_ex": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_f, C.c_void_p]),
+    "uni_gemm_ex": (c_i, [c_f, c_i, c_f, C.c_float, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_i,
+                          C.c_void_p]),
+    "uni_cast_f32": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, C.c_void_p]),
     "uni_stem": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_f, C.c_void_p]),
 }
 

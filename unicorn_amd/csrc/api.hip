@@ -9,6 +9,7 @@
 
 #include <map>
 #include <mutex>
+#include <string>
 #include <utility>
 
 static thread_local char g_err[1024] = "";
@@ -17,6 +18,19 @@ void uni_set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+// variant trace (common.h): tag -> number of launches since uni_variant_trace(1)
+std::atomic<int> g_uni_variant_trace{0};
+static std::mutex g_vt_mu;
+static std::map<std::string, long long>& vt_map() { static std::map<std::string, long long> m; return m; }
+void uni_variant_record(const char* fmt, ...) {
+    char tag[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(tag, sizeof(tag), fmt, ap);
+    va_end(ap);
+    std::lock_guard<std::mutex> lk(g_vt_mu);
+    ++vt_map()[tag];
 }
 static inline hipStream_t S(uni_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static int post_launch() {
@@ -30,6 +44,26 @@ extern "C" {
 
 const char* uni_last_error(void) { return g_err; }
 int uni_version(void) { return 1; }
+
+int uni_variant_trace(int on) {
+    std::lock_guard<std::mutex> lk(g_vt_mu);
+    if (on) vt_map().clear();
+    g_uni_variant_trace.store(on ? 1 : 0, std::memory_order_relaxed);
+    return 0;
+}
+size_t uni_variant_trace_read(char* buf, size_t cap) {
+    std::string out;
+    {
+        std::lock_guard<std::mutex> lk(g_vt_mu);
+        for (const auto& kv : vt_map()) out += kv.first + "\t" + std::to_string(kv.second) + "\n";      // std::map: sorted by tag
+    }
+    if (buf && cap) {
+        const size_t n = out.size() < cap - 1 ? out.size() : cap - 1;
+        memcpy(buf, out.data(), n);
+        buf[n] = 0;
+    }
+    return out.size() + 1;
+}
 
 uni_ctx* uni_ctx_create(int device_id, const uni_model_cfg* cfg) {
     if (!cfg) { uni_set_error("cfg is NULL"); return nullptr; }
@@ -525,6 +559,26 @@ int uni_gemm_bf16(const uint16_t* A, int lda, const uint16_t* w_packed, int M, i
     g.outB = reinterpret_cast<bf16*>(outB); g.ldb = ldb; g.stats = gn_stats; g.cpg = cpg; g.force_cfg = force_cfg; g.dbg = force_cfg / 1000;
     API(launch_gemm(g, S(stream)));
 }
+int uni_gemm_ex(const void* A, int lda, const void* w_packed, float wscale, int fmt, int M, int N, int Hin, int Win, int Cin, int KH, int KW, int stride,
+                int pad, const float* bias, int act, int act_col0, const float* residual, int ldr, float* outF, int ldf, void* outB, int ldb,
+                double* gn_stats, int cpg, int force_cfg, uni_stream_t stream) {
+    UNI_REQUIRE(A && w_packed && (outF || outB), "gemm_ex: NULL argument");
+    UNI_REQUIRE(fmt >= 0 && fmt <= 2 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && Cin > 0 && N > 0, "gemm_ex: fmt=%d / bad geometry", fmt);
+    UNI_REQUIRE(act_col0 >= 0 && act_col0 <= N && force_cfg >= 0 && force_cfg < 1000, "gemm_ex: act_col0=%d force_cfg=%d (tile configuration only)", act_col0, force_cfg);
+    GemmArgs g;
+    g.A = reinterpret_cast<const bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const bf16*>(w_packed);
+    g.N = N; g.K = Cin * KH * KW; g.Kpad = cdiv(g.K, 64) * 64;
+    g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
+    const int Hout = (Hin + 2 * pad - KH) / stride + 1;
+    g.Wout = (Win + 2 * pad - KW) / stride + 1;
+    g.M = Hout * g.Wout;
+    UNI_REQUIRE(g.M == M, "gemm_ex: M=%d does not match conv geometry (%d)", M, g.M);
+    g.Mper = g.M;
+    g.bias = bias; g.act = act; g.act_col0 = act_col0; g.res = residual; g.ldr = ldr; g.outF = outF; g.ldf = ldf;
+    g.outB = reinterpret_cast<bf16*>(outB); g.ldb = ldb; g.stats = gn_stats; g.cpg = cpg; g.force_cfg = force_cfg; g.b32 = fmt;
+    g.wscale = fmt == FMT_H2 ? wscale : 1.f;
+    API(launch_gemm(g, S(stream)));
+}
 int uni_pack_weight_h2(const float* w, int N, int Cin, int KH, int KW, void* out, float* wscale_out) {
     UNI_REQUIRE(w && out && wscale_out && N > 0 && Cin > 0, "pack_weight_h2: bad argument");
     float mx = 0.f;
@@ -593,6 +647,10 @@ int uni_cast_h2(const float* x, int ldx, void* out, int ldo, int M, int C, uni_s
     UNI_REQUIRE(x && out, "cast_h2: NULL argument");
     API(launch_cast_operand(x, ldx, reinterpret_cast<bf16*>(out), ldo, M, C, S(stream), FMT_H2));
 }
+int uni_cast_f32(const float* x, int ldx, float* out, int ldo, int M, int C, uni_stream_t stream) {
+    UNI_REQUIRE(x && out, "cast_f32: NULL argument");
+    API(launch_cast_operand(x, ldx, reinterpret_cast<bf16*>(out), ldo, M, C, S(stream), FMT_F32));
+}
 int uni_cast_bf16(const float* x, int ldx, uint16_t* out, int ldo, int M, int C, uni_stream_t stream) {
     UNI_REQUIRE(x && out, "cast: NULL argument");
     API(launch_cast_operand(x, ldx, reinterpret_cast<bf16*>(out), ldo, M, C, S(stream)));
@@ -604,6 +662,39 @@ int uni_layernorm(const float* x, int ldx, const float* gamma, const float* beta
     a.x = x; a.ldx = ldx; a.gamma = gamma; a.beta = beta; a.eps = eps; a.M = M; a.C = C;
     a.outF = outF; a.ldf = C; a.outB = reinterpret_cast<bf16*>(outB); a.ldb = C;
     API(launch_layernorm(a, S(stream)));
+}
+int uni_layernorm_ex(const float* x, int ldx, const float* gamma, const float* beta, float eps, int M, int C, float* outF, int ldf,
+                     float* outF2, int pair_hw, void* outB, int ldb, int ps_h, int ps_w, int fmt, uni_stream_t stream) {
+    UNI_REQUIRE(x && gamma && beta && (outF || outB), "layernorm_ex: NULL argument");
+    UNI_REQUIRE(M > 0 && C > 0 && ldx >= C && fmt >= 0 && fmt <= 2, "layernorm_ex: M=%d C=%d ldx=%d fmt=%d", M, C, ldx, fmt);
+    if (outF) UNI_REQUIRE(ldf >= C && ldf % 4 == 0 && ((uintptr_t)outF & 15) == 0, "layernorm_ex: ldf=%d / outF must be 16-byte aligned", ldf);
+    UNI_REQUIRE(pair_hw >= 0 && (pair_hw > 0) == (outF2 != nullptr), "layernorm_ex: outF2 and pair_hw=%d go together", pair_hw);
+    if (pair_hw) UNI_REQUIRE(outF && ((uintptr_t)outF2 & 15) == 0 && M % (2 * pair_hw) == 0, "layernorm_ex: pair mode needs outF, outF2 and M=%d a multiple of 2 * pair_hw=%d", M, pair_hw);
+    UNI_REQUIRE(ps_h >= 0 && ps_w >= 0 && (ps_h > 0) == (ps_w > 0), "layernorm_ex: ps_h=%d ps_w=%d", ps_h, ps_w);
+    if (ps_h) UNI_REQUIRE(outB && M % (ps_h * ps_w) == 0 && (fmt != FMT_H2 || C % 32 == 0), "layernorm_ex: PixelShuffle needs outB, M=%d a multiple of ps_h * ps_w, C / 4 a multiple of 8 in f16x2", M);
+    if (outB && !ps_h) UNI_REQUIRE(ldb >= C && ldb % (fmt == FMT_H2 ? 8 : 4) == 0, "layernorm_ex: ldb=%d", ldb);
+    if (outB) UNI_REQUIRE(((uintptr_t)outB & 15) == 0, "layernorm_ex: outB must be 16-byte aligned");
+    LnArgs a;
+    a.x = x; a.ldx = ldx; a.gamma = gamma; a.beta = beta; a.eps = eps; a.M = M; a.C = C;
+    a.outF = outF; a.ldf = ldf; a.outF2 = outF2; a.pair_hw = pair_hw;
+    a.outB = reinterpret_cast<bf16*>(outB); a.ldb = ldb; a.ps_h = ps_h; a.ps_w = ps_w; a.b32 = fmt;
+    API(launch_layernorm(a, S(stream)));
+}
+int uni_groupnorm_act_ex(const float* x, int ldx, const double* stats, const float* gamma, const float* beta, float eps, int B, int M, int C,
+                         int G, int act, const float* prior, const float* prior_beta, float* outF, int ldf, void* outB, int ldb, void* outUp,
+                         int ldu, int W, int fmt, uni_stream_t stream) {
+    UNI_REQUIRE(x && stats && gamma && beta && (outF || outB || outUp), "groupnorm_act_ex: NULL argument");
+    UNI_REQUIRE(B > 0 && B < 65536 && M > 0 && C > 0 && C <= 8192 && G > 0 && G <= 32 && fmt >= 0 && fmt <= 2, "groupnorm_act_ex: B=%d M=%d C=%d G=%d fmt=%d", B, M, C, G, fmt);
+    UNI_REQUIRE(ldx >= C && ((uintptr_t)x & 15) == 0, "groupnorm_act_ex: ldx=%d / x must be 16-byte aligned", ldx);
+    UNI_REQUIRE((prior != nullptr) == (prior_beta != nullptr), "groupnorm_act_ex: prior and prior_beta go together");
+    if (outF) UNI_REQUIRE(ldf >= C && ldf % 4 == 0 && ((uintptr_t)outF & 15) == 0, "groupnorm_act_ex: ldf=%d / outF must be 16-byte aligned", ldf);
+    if (outB) UNI_REQUIRE(ldb >= C, "groupnorm_act_ex: ldb=%d", ldb);
+    if (outUp) UNI_REQUIRE(ldu >= C && W > 0 && M % W == 0, "groupnorm_act_ex: outUp needs ldu=%d >= C and M=%d a multiple of W=%d", ldu, M, W);
+    GnApplyArgs a;
+    a.x = x; a.ldx = ldx; a.stats = stats; a.gamma = gamma; a.beta = beta; a.eps = eps; a.M = M; a.C = C; a.G = G; a.act = act; a.B = B;
+    a.prior = prior; a.prior_beta = prior_beta; a.outF = outF; a.ldf = ldf; a.outB = reinterpret_cast<bf16*>(outB); a.ldb = ldb;
+    a.outUp = reinterpret_cast<bf16*>(outUp); a.ldu = ldu; a.W = W; a.b32 = fmt;
+    API(launch_gn_apply(a, S(stream)));
 }
 int uni_dwconv7_ln(const float* x, const float* w49c, const float* bias, const float* gamma, const float* beta, float eps, int H, int W,
                    int C, uint16_t* out, uni_stream_t stream) {
@@ -642,6 +733,13 @@ int uni_stem(const float* img, int H, int W, const float* w48c, const float* bia
     UNI_REQUIRE(img && w48c && bias && gamma && beta && out, "stem: NULL argument");
     StemArgs a;
     a.img = img; a.H = H; a.W = W; a.w = w48c; a.bias = bias; a.gamma = gamma; a.beta = beta; a.C = C; a.out = out;
+    API(launch_stem(a, S(stream)));
+}
+int uni_stem_ex(const float* img, int B, int H, int W, const float* w48c, const float* bias, const float* gamma, const float* beta, int C,
+                float* out, uni_stream_t stream) {
+    UNI_REQUIRE(img && w48c && bias && gamma && beta && out && B > 0, "stem_ex: bad argument");
+    StemArgs a;
+    a.img = img; a.H = H; a.W = W; a.B = B; a.w = w48c; a.bias = bias; a.gamma = gamma; a.beta = beta; a.C = C; a.out = out;
     API(launch_stem(a, S(stream)));
 }
 

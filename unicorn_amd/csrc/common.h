@@ -171,6 +171,21 @@ static inline hipError_t uni_lds_optin(const void* fn, int bytes) { return hipFu
 
 // error plumbing (api.cpp owns the storage)
 void uni_set_error(const char* fmt, ...);
+
+// Variant trace (api.hip owns the storage; uni_variant_trace / uni_variant_trace_read in include/unicorn_hip.h): every launcher reports the
+// kernel instantiation it is about to launch as a short tag, so a test can tell WHICH variant a shape ran.  Host code only.  Off (the
+// default): one relaxed atomic load per launch, no formatting, no lock, no allocation.  On: the tag is formatted and counted in a
+// mutex-protected map (the engine forks streams, parallel.py drives contexts from threads).
+extern std::atomic<int> g_uni_variant_trace;
+void uni_variant_record(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+template <class... A>
+static inline void uni_variant_note(const char* fmt, A... args) {
+    if (g_uni_variant_trace.load(std::memory_order_relaxed)) uni_variant_record(fmt, args...);
+}
+static inline void uni_variant_note(const char* tag) {
+    if (g_uni_variant_trace.load(std::memory_order_relaxed)) uni_variant_record("%s", tag);
+}
+static inline const char* uni_fmt_name(int fmt) { return fmt == 1 ? "f32" : fmt == 2 ? "h2" : "bf16"; }
 // opt every listed kernel instantiation into `bytes` of dynamic LDS, once per device (DevOnce::run); `return -1` with an error text on failure
 #define UNI_LDS_OPTIN(once, what, bytes, ...)                                                                                   \
     do {                                                                                                                        \

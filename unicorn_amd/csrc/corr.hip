@@ -580,6 +580,8 @@ int run(const float* eref, const float* ecur, const float* v, float* out, int R,
     // checked here, next to the launch, so a later per-precision change of pick_nsplit / corr_slots cannot write past it
     UNI_REQUIRE(ns_eff == 1 || (size_t)B * ns_eff * Q * (2 + KV) * sizeof(float) <= ws_bytes,
                 "corr: workspace too small for %d splits x %d frames x %d queries (%zu B given)", ns_eff, B, Q, ws_bytes);
+    uni_variant_note("corr %s KV=%d %s batched=%d vpf=%d lse=%d", precision == 3 ? "h1" : precision == 2 ? "h2" : precision ? "bf16x3" : "f32", KV,
+                     ns_eff > 1 ? "split" : "single", B > 1, vfs != 0, lse != nullptr);
     if (precision == 3) {
         size_t lds = (size_t)2 * 2 * TR * CD * sizeof(f16) + (size_t)2 * KV * TR * sizeof(float);
         hipLaunchKernelGGL((corr_h2_kernel<KV, 8, true>), dim3(cdiv(Q, QB2), ns_eff, B), dim3(512), lds, s, eref, ecur, v, out, ws, R,
@@ -600,6 +602,7 @@ int run(const float* eref, const float* ecur, const float* v, float* out, int R,
         hipLaunchKernelGGL((corr_f32_kernel<KV>), dim3(cdiv(Q, QB), ns_eff), dim3(256), lds, s, eref, ecur, v, out, ws, R,
                            Q, K, ns_eff, rps, ns_eff == 1 ? lse : nullptr);
     }
+    if (ns_eff > 1) uni_variant_note("corr merge KV=%d batched=%d lse=%d", KV, B > 1, lse != nullptr);
     if (ns_eff > 1)
         hipLaunchKernelGGL((corr_merge_kernel<KV>), dim3(cdiv(Q, 256), B), dim3(256), 0, s, ws, out, Q, K, ns_eff, lse);
     return 0;

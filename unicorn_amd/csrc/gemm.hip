@@ -330,6 +330,7 @@ static int launch_cfg(const GemmArgs& a, hipStream_t s) {
     if (lds > 65536)
         UNI_LDS_OPTIN(attr_once, "gemm_bf16", lds, reinterpret_cast<const void*>(&gemm_bf16_kernel<WM, WN, TM, TN, BK, CONV, true, NSTG>),
                       reinterpret_cast<const void*>(&gemm_bf16_kernel<WM, WN, TM, TN, BK, CONV, false, NSTG>));
+    uni_note_gemm(BK == 32 ? (NSTG == 4 ? "bf16_bk32s4" : NSTG == 5 ? "bf16_bk32s5" : "bf16_bk32s2") : "bf16_bk64s2", WM * 1000 + WN * 100 + TM * 10 + TN, CONV, a.stats != nullptr, a);
     if (a.stats) hipLaunchKernelGGL((gemm_bf16_kernel<WM, WN, TM, TN, BK, CONV, true, NSTG>), dim3(grid), dim3(64 * WM * WN), lds, s, a);
     else hipLaunchKernelGGL((gemm_bf16_kernel<WM, WN, TM, TN, BK, CONV, false, NSTG>), dim3(grid), dim3(64 * WM * WN), lds, s, a);
     return 0;
@@ -350,6 +351,7 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
         if (a.stats) UNI_REQUIRE(a.cpg > 0 && 128 / a.cpg + 2 <= 64, "gemm: cpg=%d unsupported", a.cpg);
         const int grid = cdiv(a.M, 64) * cdiv(a.N, 64);
         const size_t lds = (size_t)2 * (64 + 64) * 32 * sizeof(float);
+        uni_note_gemm("f32", 2211, conv, a.stats != nullptr, a);
         if (conv) hipLaunchKernelGGL((gemm_f32_kernel<true>), dim3(grid), dim3(256), lds, s, a);
         else hipLaunchKernelGGL((gemm_f32_kernel<false>), dim3(grid), dim3(256), lds, s, a);
         return 0;

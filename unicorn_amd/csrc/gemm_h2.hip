@@ -277,6 +277,7 @@ GemmArgs gemm_splitk_partial_args(const GemmArgs& a) {
     return g;
 }
 int launch_splitk_reduce(const GemmArgs& a, hipStream_t s) {
+    uni_variant_note("gemm:splitk_reduce bias=%d res=%d stats=%d stacked=%d", a.bias != nullptr, a.res != nullptr, a.stats != nullptr, a.M != a.Mper);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(a.Mper, RED_RB), a.M / a.Mper), dim3(256), 0, s, a);
     return 0;
 }
@@ -293,6 +294,7 @@ static int launch_h2_cfg(const GemmArgs& a, hipStream_t s) {
     if (lds > 65536)
         UNI_LDS_OPTIN(attr_once, "gemm_h2", lds, reinterpret_cast<const void*>(&gemm_h2_kernel<WM, WN, TM, TN, CONV, true, BKE>),
                       reinterpret_cast<const void*>(&gemm_h2_kernel<WM, WN, TM, TN, CONV, false, BKE>));
+    uni_note_gemm("h2", WM * 1000 + WN * 100 + TM * 10 + TN, CONV, a.stats && gy == 1, gy > 1 ? gemm_splitk_partial_args(a) : a);      // K ranges: bias / residual / sums belong to the reduce
     if (a.stats && gy == 1) hipLaunchKernelGGL((gemm_h2_kernel<WM, WN, TM, TN, CONV, true, BKE>), dim3(grid), dim3(64 * WM * WN), lds, s, a);
     else hipLaunchKernelGGL((gemm_h2_kernel<WM, WN, TM, TN, CONV, false, BKE>), dim3(grid, gy), dim3(64 * WM * WN), lds, s, a);
     if (gy > 1) return launch_splitk_reduce(a, s);

@@ -290,6 +290,7 @@ static int launch_h2d_spec(const GemmArgs& a, hipStream_t s) {      // producer 
     if (lds < (size_t)WM * WN * 32 * 32 * TN * sizeof(float)) lds = (size_t)WM * WN * 32 * 32 * TN * sizeof(float);
     static DevOnce attr_once;
     UNI_LDS_OPTIN(attr_once, "gemm_h2d (producer waves)", lds, reinterpret_cast<const void*>(&gemm_h2d_kernel<WM, WN, TM, TN, CONV, false, NST, true>));
+    uni_note_gemm("h2d_spec", WM * 10000 + WN * 1000 + TM * 100 + TN * 10 + NST, CONV, false, a);
     hipLaunchKernelGGL((gemm_h2d_kernel<WM, WN, TM, TN, CONV, false, NST, true>), dim3(grid), dim3(128 * WM * WN), lds, s, a);
     return 0;
 }
@@ -305,6 +306,7 @@ static int launch_h2d_cfg(const GemmArgs& a, hipStream_t s) {
     static DevOnce attr_once;
     UNI_LDS_OPTIN(attr_once, "gemm_h2d", lds, reinterpret_cast<const void*>(&gemm_h2d_kernel<WM, WN, TM, TN, CONV, true, NST>),
                   reinterpret_cast<const void*>(&gemm_h2d_kernel<WM, WN, TM, TN, CONV, false, NST>));
+    uni_note_gemm("h2d", WM * 10000 + WN * 1000 + TM * 100 + TN * 10 + NST, CONV, a.stats && gy == 1, gy > 1 ? gemm_splitk_partial_args(a) : a);      // K ranges: bias / residual / sums belong to the reduce
     if (a.stats && gy == 1) hipLaunchKernelGGL((gemm_h2d_kernel<WM, WN, TM, TN, CONV, true, NST>), dim3(grid), dim3(64 * WM * WN), lds, s, a);
     else hipLaunchKernelGGL((gemm_h2d_kernel<WM, WN, TM, TN, CONV, false, NST>), dim3(grid, gy), dim3(64 * WM * WN), lds, s, a);
     if (gy > 1) return launch_splitk_reduce(a, s);

@@ -437,6 +437,7 @@ template <int ACT, bool OUTF, bool CONV, bool STATS, int FMT>
 static int launch_h2q_inst(const GemmArgs& a, int grid, hipStream_t s) {
     static DevOnce attr_once;
     UNI_LDS_OPTIN(attr_once, "gemm_h2q", LDS_BYTES, reinterpret_cast<const void*>(&gemm_h2q_kernel<ACT, OUTF, CONV, STATS, FMT>));
+    uni_note_gemm(OUTF ? "h2q_outF" : "h2q_outB", 188, CONV, STATS, a);      // (ACT, FMT: the act= / fmt= fields of the tag)
     hipLaunchKernelGGL((gemm_h2q_kernel<ACT, OUTF, CONV, STATS, FMT>), dim3(grid), dim3(64 * NW), LDS_BYTES, s, a);
     return 0;
 }

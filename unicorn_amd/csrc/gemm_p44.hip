@@ -247,6 +247,7 @@ template <int ACT, bool OUTF>
 static int launch_p44_inst(const GemmArgs& a, int grid, hipStream_t s) {
     static DevOnce attr_once;
     UNI_LDS_OPTIN(attr_once, "gemm_p44", LDS_BYTES, reinterpret_cast<const void*>(&gemm_bf16_p44_kernel<ACT, OUTF>));
+    uni_note_gemm(OUTF ? "p44_outF" : "p44_outB", 144, false, false, a);
     hipLaunchKernelGGL((gemm_bf16_p44_kernel<ACT, OUTF>), dim3(grid), dim3(64 * NW), LDS_BYTES, s, a);
     return 0;
 }

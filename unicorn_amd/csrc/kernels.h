@@ -28,6 +28,15 @@ struct GemmArgs {
     int dbg = 0;                              // ablation switches for tools/gemm_bench.py (1 = no DMA after tile 0, 2 = no MFMA)
     int epi = 0;                              // set by launch_gemm: 1 = LDS-staged, row-coalesced epilogue stores
 };
+// variant trace tag of one GEMM launch (common.h: uni_variant_note).  family = the kernel, cfg = its tile configuration; then every
+// launch-uniform switch that changes index arithmetic or the store path: implicit conv, GroupNorm statistics, K ranges, staged epilogue,
+// which outputs exist, residual, activation (+ column window), outF row remap, stacked samples.
+static inline void uni_note_gemm(const char* family, int cfg, bool conv, bool stats, const GemmArgs& a) {
+    if (!g_uni_variant_trace.load(std::memory_order_relaxed)) return;
+    uni_variant_record("gemm:%s cfg=%d fmt=%s conv=%d stats=%d splitk=%d epi=%d outF=%d outB=%d res=%d act=%d%s remap=%d stacked=%d", family, cfg,
+                       uni_fmt_name(a.b32), (int)conv, (int)stats, a.splitk > 1 ? 1 : 0, a.epi, a.outF != nullptr, a.outB != nullptr,
+                       a.res != nullptr, a.act, a.act_col0 ? "w" : "", a.out_hw != 0, a.Mper > 0 && a.M != a.Mper);
+}
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 int launch_gemm_h2(const GemmArgs& a, hipStream_t s);     // gemm_h2.hip (reached through launch_gemm when a.b32 == FMT_H2)
 uint16_t f32_to_f16_host(float f);

@@ -21,6 +21,7 @@ int launch_cast_operand(const float* x, int ldx, bf16* out, int ldo, int M, int 
     long total = (long)M * (C / 8);
     int grid = (int)((total + 255) / 256);
     if (grid > 2048) grid = 2048;
+    uni_variant_note("cast_operand fmt=%s", uni_fmt_name(b32));
     hipLaunchKernelGGL(cast_operand_kernel, dim3(grid), dim3(256), 0, s, x, ldx, out, ldo, M, C / 8, b32);
     return 0;
 }
@@ -43,6 +44,7 @@ int launch_cast_operand_pair(const float* x0, const float* x1, bf16* out, int hw
     const long total = (long)2 * B * hw * (C / 8);
     int grid = (int)((total + 255) / 256);
     if (grid > 4096) grid = 4096;
+    uni_variant_note("cast_operand_pair fmt=%s batched=%d", uni_fmt_name(b32), B > 1);
     hipLaunchKernelGGL(cast_operand_pair_kernel, dim3(grid), dim3(256), 0, s, x0, x1, out, hw, C / 8, B, b32);
     return 0;
 }
@@ -66,6 +68,7 @@ int launch_pixel_shuffle_bf16(const float* x, bf16* out, int h, int w, int C, hi
     long total = (long)h * w * C * B;
     int grid = (int)((total + 255) / 256);
     if (grid > 4096) grid = 4096;
+    uni_variant_note("pixel_shuffle_bf16 fmt=%s batched=%d", uni_fmt_name(b32), B > 1);
     hipLaunchKernelGGL(pixel_shuffle_kernel, dim3(grid), dim3(256), 0, s, x, out, h, w, C, b32, B);
     return 0;
 }
@@ -90,6 +93,7 @@ __global__ void prior_pyramid_kernel(const float* p8, float* p16, float* p32, in
 int launch_prior_pyramid(const float* p8, float* p16, float* p32, int K, int H8, int W8, hipStream_t s) {
     int n = K * ((H8 / 2) * (W8 / 2) + (H8 / 4) * (W8 / 4));
     if (n == 0) return 0;
+    uni_variant_note("prior_pyramid");
     hipLaunchKernelGGL(prior_pyramid_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p8, p16, p32, K, H8, W8);
     return 0;
 }
@@ -114,6 +118,7 @@ __global__ void decode_kernel(float* out, int A0, int W0, int A1, int W1, int A2
 }
 int launch_decode(const float* raw, float* out, int A0, int W0, int A1, int W1, int A2, int W2, int nch, hipStream_t s, int B) {
     UNI_REQUIRE(raw == out, "decode: in-place only");
+    uni_variant_note("decode batched=%d", B > 1);
     hipLaunchKernelGGL(decode_kernel, dim3(cdiv((A0 + A1 + A2) * B, 256)), dim3(256), 0, s, out, A0, W0, A1, W1, A2, W2, nch, B);
     return 0;
 }
@@ -151,6 +156,7 @@ int launch_add_aligned_bilinear(const float* src, int h, int w, int C, int facto
     long total = (long)factor * h * factor * w * (C / 4);
     int grid = (int)((total + 255) / 256);
     if (grid > 4096) grid = 4096;
+    uni_variant_note("add_aligned_bilinear factor=%d batched=%d", factor, B > 1);
     hipLaunchKernelGGL(add_aligned_bilinear_kernel, dim3(grid, B), dim3(256), 0, s, src, h, w, C, factor, dst);
     return 0;
 }
@@ -182,6 +188,7 @@ __global__ void pos_embed_kernel(const float* row, const float* col, int sz, int
     }
 }
 int launch_pos_embed(const float* row, const float* col, int sz, int nf, float* out, int h, int w, hipStream_t s) {
+    uni_variant_note("pos_embed");
     hipLaunchKernelGGL(pos_embed_kernel, dim3(cdiv(h * w * 2 * nf, 256)), dim3(256), 0, s, row, col, sz, nf, out, h, w);
     return 0;
 }
@@ -338,6 +345,7 @@ int launch_condinst(const CondInstArgs& a, hipStream_t s) {
     if (a.n == 0) return 0;
     UNI_REQUIRE(a.r >= 1 && a.d_rate >= 1, "condinst: r=%d d_rate=%d", a.r, a.d_rate);
     const int hw = a.H * a.W, rr = a.r * a.r;
+    uni_variant_note("condinst final=%d", a.out != nullptr);
     hipLaunchKernelGGL(condinst_mlp_kernel, dim3(cdiv(hw, 256), a.n), dim3(256), 0, s, a);
     hipLaunchKernelGGL(condinst_upsample_kernel, dim3(cdiv(hw * rr, 256), cdiv(a.n, CU_IC)), dim3(256), 0, s, a);
     if (!a.out) return 0;          // the caller continues from coarse_ws (uni_condinst_masks_u8: fused upsample + resize, mask_post.hip)
@@ -371,6 +379,7 @@ int launch_add_pos_bf16(const float* src, const float* pos0, const float* pos1, 
     long total = (long)2 * hw * (C / 4) * B;
     int grid = (int)((total + 255) / 256);
     if (grid > 2048) grid = 2048;
+    uni_variant_note("add_pos_bf16 fmt=%s batched=%d", uni_fmt_name(b32), B > 1);
     hipLaunchKernelGGL(add_pos_kernel, dim3(grid), dim3(256), 0, s, src, pos0, pos1, lvl, out, hw, C, b32, B);
     return 0;
 }

@@ -761,6 +761,7 @@ static int launch_mlp16_k(const MlpArgs& a, int grid, hipStream_t s) {
     constexpr int lds = Geo16<C>::LDS;
     static DevOnce attr_once;
     UNI_LDS_OPTIN(attr_once, "mlp_fused16", lds, reinterpret_cast<const void*>(&mlp_fused16_kernel<C, OUTB, DBG>));
+    uni_variant_note("mlp_fused layout=1 C=%d outB=%d dbg=%d", C, (int)OUTB, DBG);
     hipLaunchKernelGGL((mlp_fused16_kernel<C, OUTB, DBG>), dim3(grid), dim3(64 * MW16), lds, s, a);
     return 0;
 }
@@ -770,6 +771,7 @@ static int launch_mlp_k(const MlpArgs& a, int grid, hipStream_t s) {
     constexpr int lds = Geo<C>::LDS;
     static DevOnce attr_once;
     UNI_LDS_OPTIN(attr_once, "mlp_fused", lds, reinterpret_cast<const void*>(&mlp_fused_kernel<C, CH, OUTB, DBG>));
+    uni_variant_note("mlp_fused layout=0 C=%d outB=%d dbg=%d", C, (int)OUTB, DBG);
     hipLaunchKernelGGL((mlp_fused_kernel<C, CH, OUTB, DBG>), dim3(grid), dim3(64 * MW), lds, s, a);
     return 0;
 }

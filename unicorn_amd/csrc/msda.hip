@@ -278,6 +278,7 @@ __global__ __launch_bounds__(256) void msda_wave_kernel(MsdaFusedArgs p) {
 
 int launch_msda_fused(const MsdaFusedArgs& a, hipStream_t s) {
     const long tasks = (long)2 * a.h * a.w * 8 * a.B;
+    uni_variant_note("msda_fused fmt=%s batched=%d", uni_fmt_name(a.b32), a.B > 1);
     hipLaunchKernelGGL(msda_wave_kernel, dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, s, a);
     return 0;
 }

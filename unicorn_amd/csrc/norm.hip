@@ -79,6 +79,8 @@ int launch_layernorm(const LnArgs& a, hipStream_t s) {
     UNI_REQUIRE(((uintptr_t)a.x & 15) == 0, "layernorm: x not 16-B aligned");
     int ni = cdiv(a.C / 4, 64);
     dim3 grid(cdiv(a.M, 4)), block(256);
+    uni_variant_note("layernorm NI=%d fmt=%s ps=%d pair=%d outF=%d outB=%d", ni <= 4 ? ni : 6, uni_fmt_name(a.b32), a.ps_h != 0, a.pair_hw != 0, a.outF != nullptr,
+                     a.outB != nullptr);
     switch (ni) {
         case 1: hipLaunchKernelGGL(layernorm_kernel<1>, grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL(layernorm_kernel<2>, grid, block, 0, s, a); break;
@@ -195,6 +197,11 @@ int launch_gn_apply(const GnApplyArgs& a, hipStream_t s) {
         grid = (grid + q - 1) / q * q;
     }
     const bool fast = a.b32 != FMT_F32;
+    {
+        const int act_t = a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_SILU ? a.act : -1;      // the ACT template argument
+        uni_variant_note("gn_apply ACT=%d FAST=%d fmt=%s batched=%d prior=%d outUp=%d outF=%d outB=%d", act_t, (int)(fast && act_t >= 0), uni_fmt_name(a.b32), nb > 1,
+                         a.prior != nullptr, a.outUp != nullptr, a.outF != nullptr, a.outB != nullptr);
+    }
 #define GN_GO(ACT, F) hipLaunchKernelGGL((gn_apply_kernel<ACT, F>), dim3((unsigned)grid, nb), dim3(256), 2 * a.C * sizeof(float), s, a)
     switch (a.act) {
         case ACT_NONE: if (fast) GN_GO(ACT_NONE, true); else GN_GO(ACT_NONE, false); break;
@@ -979,6 +986,7 @@ int launch_dwconv7_ln(const DwLnArgs& a, hipStream_t s) {
             constexpr int ldsb = 3 * 16 * 192 * 16 + 2 * 3 * 16 * 4;
             static DevOnce once;
             UNI_LDS_OPTIN(once, "dwconv7_lns", ldsb, reinterpret_cast<const void*>(&dwconv7_lns_kernel<768>));
+            uni_variant_note("dwconv7_ln lns<768> fmt=%s batched=%d", uni_fmt_name(a.b32), nb > 1);
             hipLaunchKernelGGL((dwconv7_lns_kernel<768>), dim3(nst), dim3(768), ldsb, s, a, spr, nst);
             return 0;
         }
@@ -1008,6 +1016,7 @@ int launch_dwconv7_ln(const DwLnArgs& a, hipStream_t s) {
                 static const int dbg = getenv("UNI_DW_DBG") ? atoi(getenv("UNI_DW_DBG")) : 0;      // ablation builds of the stage-2 kernel (tools/dwln_bench.py)
                 if (dbg && a.C == 768 && rows == 2) {
 #define DWB_DBG(D) if (dbg == D) { static DevOnce once; UNI_LDS_OPTIN(once, "dwconv7_lnb (ablation)", 163840, reinterpret_cast<const void*>(&dwconv7_lnb_kernel<768, 2, D>)); \
+                                   uni_variant_note("dwconv7_ln lnb<C=768,ROWS=2,DBG=%d,NW=8,PACK=0> fmt=%s batched=%d", D, uni_fmt_name(a.b32), nb > 1); \
                                    hipLaunchKernelGGL((dwconv7_lnb_kernel<768, 2, D>), grid, block, ldsw, s, a, Sw, spr, nst); return 0; }
                     DWB_DBG(1) DWB_DBG(2) DWB_DBG(4) DWB_DBG(8) DWB_DBG(3) DWB_DBG(9) DWB_DBG(15)
 #undef DWB_DBG
@@ -1026,6 +1035,7 @@ int launch_dwconv7_ln(const DwLnArgs& a, hipStream_t s) {
                     const size_t ldsp = (size_t)49 * a.C * 4 + (size_t)2 * (nw * 64 / gran) * 16 * 4;
                     if (cdiv(nstg, Sg) >= 384) {
 #define DWB_PACK(CC, NWW) if (a.C == CC && nw == NWW) { static DevOnce once; UNI_LDS_OPTIN(once, "dwconv7_lnb (packed lanes)", 163840, reinterpret_cast<const void*>(&dwconv7_lnb_kernel<CC, 2, 0, NWW, true>)); \
+                                     uni_variant_note("dwconv7_ln lnb<C=%d,ROWS=2,DBG=0,NW=%d,PACK=1> fmt=%s batched=%d", CC, NWW, uni_fmt_name(a.b32), nb > 1); \
                                      hipLaunchKernelGGL((dwconv7_lnb_kernel<CC, 2, 0, NWW, true>), grid, dim3(NWW * 64), ldsp, s, a, Sg, sprg, nstg); return 0; }
                         DWB_PACK(192, 6) DWB_PACK(192, 9) DWB_PACK(192, 12) DWB_PACK(384, 6) DWB_PACK(384, 9) DWB_PACK(384, 12)
 #undef DWB_PACK
@@ -1038,24 +1048,29 @@ int launch_dwconv7_ln(const DwLnArgs& a, hipStream_t s) {
                     const int Sw12 = 12 / wps;
                     const size_t lds12 = (size_t)49 * a.C * 4 + (size_t)2 * 12 * 16 * 4;
 #define DWB_W12(CC) if (a.C == CC) { static DevOnce once; UNI_LDS_OPTIN(once, "dwconv7_lnb (12 waves)", 163840, reinterpret_cast<const void*>(&dwconv7_lnb_kernel<CC, 2, 0, 12>)); \
+                                     uni_variant_note("dwconv7_ln lnb<C=%d,ROWS=2,DBG=0,NW=12,PACK=0> fmt=%s batched=%d", CC, uni_fmt_name(a.b32), nb > 1); \
                                      hipLaunchKernelGGL((dwconv7_lnb_kernel<CC, 2, 0, 12>), grid, dim3(Sw12 * wps * 64), lds12, s, a, Sw12, spr, nst); return 0; }
                     DWB_W12(192) DWB_W12(384) DWB_W12(768)
 #undef DWB_W12
                 }
-#define DWB_GO(CC, RR) if (a.C == CC && rows == RR) { hipLaunchKernelGGL((dwconv7_lnb_kernel<CC, RR>), grid, block, ldsw, s, a, Sw, spr, nst); return 0; }
+#define DWB_GO(CC, RR) if (a.C == CC && rows == RR) { uni_variant_note("dwconv7_ln lnb<C=%d,ROWS=%d,DBG=0,NW=8,PACK=0> fmt=%s batched=%d", CC, RR, uni_fmt_name(a.b32), nb > 1); \
+                         hipLaunchKernelGGL((dwconv7_lnb_kernel<CC, RR>), grid, block, ldsw, s, a, Sw, spr, nst); return 0; }
                 DWB_ALL(DWB_GO)
 #undef DWB_GO
 #undef DWB_ALL
             }
         }
+        uni_variant_note("dwconv7_ln ln2 CG=%d S=%d fmt=%s batched=%d", CG, S, uni_fmt_name(a.b32), nb > 1);
         hipLaunchKernelGGL(dwconv7_ln2_kernel, dim3(cdiv(nstrips, S)), dim3(T), strip_reduce_lds(S, CG, 16), s, a, S, CG, spr, nstrips);
         return 0;
     }
     if (px == 8) {
         const int spr = cdiv(a.W, 8), nstrips = spr * a.H * nb;
+        uni_variant_note("dwconv7_ln ln<PX=8> CG=%d S=%d fmt=%s batched=%d", CG, S, uni_fmt_name(a.b32), nb > 1);
         hipLaunchKernelGGL(dwconv7_ln_kernel<8>, dim3(cdiv(nstrips, S)), dim3(T), strip_reduce_lds(S, CG, 8), s, a, S, CG, spr, nstrips);
     } else {
         const int spr = cdiv(a.W, 4), nstrips = spr * a.H * nb;
+        uni_variant_note("dwconv7_ln ln<PX=4> CG=%d S=%d fmt=%s batched=%d", CG, S, uni_fmt_name(a.b32), nb > 1);
         hipLaunchKernelGGL(dwconv7_ln_kernel<4>, dim3(cdiv(nstrips, S)), dim3(T), strip_reduce_lds(S, CG, 4), s, a, S, CG, spr, nstrips);
     }
     return 0;
@@ -1197,11 +1212,13 @@ int launch_stem(const StemArgs& a, hipStream_t s) {
         const int spr = a.W / 16, nstrips = npix / 4;
         const int T4 = cdiv(S * CG, 64) * 64;
         size_t lds4 = S * 192 * sizeof(float) + strip_reduce_lds(S, CG, 4);
+        uni_variant_note("stem 4px CG=%d S=%d batched=%d", CG, S, a.B > 1);
         hipLaunchKernelGGL(stem4_kernel, dim3(cdiv(nstrips, S)), dim3(T4), lds4, s, a, S, CG, nstrips, spr);
         return 0;
     }
     const int T = cdiv(S * CG, 64) * 64;
     size_t lds = S * 48 * sizeof(float) + strip_reduce_lds(S, CG, 1);
+    uni_variant_note("stem 1px CG=%d S=%d batched=%d", CG, S, a.B > 1);
     hipLaunchKernelGGL(stem_kernel, dim3(cdiv(npix, S)), dim3(T), lds, s, a, S, CG, npix);
     return 0;
 }
