@@ -419,6 +419,54 @@ int uni_mot_corr_loss_bwd_f64(const double* embed_0, const int64_t* strides_0, c
                               double* grad_embed_0, const int64_t* grad_strides_0, double* grad_embed_1, const int64_t* grad_strides_1,
                               void* workspace, size_t workspace_bytes, uni_stream_t stream);
 
+/* What stands around the label propagation in the SOT / VOS TRAINING losses (unicorn/models/unicorn.py:315-337 compute_loss_sot, :339-390
+ * compute_loss_vos) for a whole BATCH, without a host synchronisation, a read-back or an allocation; the number of launches does not
+ * depend on the data.  The propagation itself is uni_corr_softmax_pv_lse / _bwd on the label rows these entries produce.
+ *   targets   [B][2][M][6] fp32, contiguous: rows (class, cx, cy, w, h, track id) of frame 0 and frame 1; fp32 in the _f64 forms too.
+ *   maps      H8 x W8 pixels (stride 8: the image is 8 H8 x 8 W8), H8, W8 >= 4; Q = H8 W8.
+ * uni_prop_labels (2 launches; not differentiable):
+ *   sot = 1:  Kc = 1, slot 0 of every sample is (row 0 of frame 0, row 0 of frame 1) whatever the ids (:324, :332); num_matched = 1.
+ *   sot = 0:  for i = 0 .. M-1 with id0[i] != 0, j = the first j with id1[j] != 0 && id1[j] == id0[i] (fp32 compare, :352-361); the
+ *             matched i fill the slots in the order of i, at most Kc <= M of them (the reference's max_matched_inst).
+ *   -> matched [B][Kc][2] int32 = (i, j), -1 in slots >= num_matched[b]; num_matched [B] int32;
+ *      gt0, gt1 [B][Kc][Q]: the label rows of frame 0 (row i) and frame 1 (row j), zeros in slots >= num_matched[b]; all completely written.
+ *   masks == NULL: F.interpolate(get_label_map(box), 1/8, bilinear) (:521-533) = the mean of the central 2 x 2 of every 8 x 8 block of the
+ *             full-resolution box mask, which is never formed.  Corners cx -+ 0.5 w, cy -+ 0.5 h in fp32, rounded half to even; the
+ *             start clamped to >= 0; the end by Python's slice rules: above the size it is clipped, negative e means size + e, end <= start is
+ *             an empty box.
+ *   masks [B][2][M][r H8][r W8], fp32 (mask_u8 = 0) or uint8 (mask_u8 = 1), mask_rate r = 1, 2, 4: init_with_mask (:56-58, :365-366), the
+ *             bilinear 1/r of masks[b][0][i] and masks[b][1][j]: the pixel, the 2 x 2 block, the central 2 x 2 of the 4 x 4 block, read in place.
+ * uni_prop_dice_pyramid_fwd (2 launches): pred [B][Kc][H8][W8] (the propagated labels), gt1 [B][Kc][Q] ->
+ *   p16 [B][Kc][H8/2][W8/2], p32 [B][Kc][H8/4][W8/4] = F.interpolate(pred, 1/2 and 1/4, bilinear) (:329-331, :372-374): rows / columns
+ *             2y, 2y+1 and 4y+1, 4y+2; odd sizes keep the floor, trailing rows / columns have no parent;
+ *   loss      dice_coefficient (:509-519), 1 - 2 I / (X2 + T2 + 1e-5) with I = sum x t, X2 = sum x^2, T2 = sum t^2.
+ *             num_matched != NULL: [B][Kc], one Dice per slot, 0 in slots >= num_matched[b] (read on the device);
+ *             num_matched == NULL: ONE value over the whole batch, as compute_loss_sot flattens it;
+ *   sums      [B Kc][3] (or [1][3]) double = I, X2, T2, for the backward.  Sums are double in both precisions, in a fixed order.
+ * uni_prop_dice_pyramid_bwd (1 launch): grad_pred [B][Kc][H8][W8], completely written, =
+ *   grad_p8 + 0.25 grad_p16[parent] + 0.25 grad_p32[parent] + grad_loss (-2 t / U + 4 I x / U^2), U = X2 + T2 + 1e-5.
+ *   Each of grad_p8, grad_p16, grad_p32, grad_loss may be NULL (left out).  Slots >= num_matched[b] get exactly zero.  One writer per
+ *   element, no atomics: two calls give the same bits.
+ * 16-byte accesses are used when W8 % 4 == 0 and the pointers are aligned for them; any other shape / alignment takes the scalar form.
+ * Limits: 1 <= Kc <= M <= 1024, B Kc <= 32767, H8, W8 >= 4, B Kc Q < 2^31; other shapes are refused with an error string and
+ * uni_prop_workspace_bytes returns 0 for them.  workspace: 8-byte aligned, >= uni_prop_workspace_bytes(B, Kc, Q) = 24 B Kc ceil(Q / 1024)
+ * bytes rounded up to 256, in both precisions; the forward's scratch only. */
+size_t uni_prop_workspace_bytes(int B, int Kc, int Q);
+int uni_prop_labels(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int mask_rate,
+                    int32_t* matched, int32_t* num_matched, float* gt0, float* gt1, uni_stream_t stream);
+int uni_prop_labels_f64(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int mask_rate,
+                        int32_t* matched, int32_t* num_matched, double* gt0, double* gt1, uni_stream_t stream);
+int uni_prop_dice_pyramid_fwd(const float* pred, const float* gt1, const int32_t* num_matched, int B, int Kc, int H8, int W8, float* p16, float* p32,
+                              float* loss, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_prop_dice_pyramid_fwd_f64(const double* pred, const double* gt1, const int32_t* num_matched, int B, int Kc, int H8, int W8, double* p16,
+                                  double* p32, double* loss, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_prop_dice_pyramid_bwd(const float* pred, const float* gt1, const int32_t* num_matched, const double* sums, const float* grad_p8,
+                              const float* grad_p16, const float* grad_p32, const float* grad_loss, int B, int Kc, int H8, int W8, float* grad_pred,
+                              uni_stream_t stream);
+int uni_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const int32_t* num_matched, const double* sums, const double* grad_p8,
+                                  const double* grad_p16, const double* grad_p32, const double* grad_loss, int B, int Kc, int H8, int W8,
+                                  double* grad_pred, uni_stream_t stream);
+
 /* Input letterbox on the device (row 0 / N1): PreprocessorX.process (external/lib/test/tracker/unicorn_sot.py:111-123,
  * swap_rb = 1) and preproc (unicorn/data/data_augment.py:194-214, swap_rb = 0).  img_hwc: (h, w, 3) uint8 DEVICE buffer;
  * out_chw: (3, H, W) fp32 = cv2.resize(INTER_LINEAR, 8-bit fixed point) to (int(w r), int(h r)), r = min(H/h, W/w),

@@ -412,6 +412,39 @@ int uni_head_mask_loss_bwd_f64(const double* mask_feats, const double* up_masks,
     API(launch_head_mask_loss_bwd_f64(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, sums, grad_out, grad_mask_feats, grad_up_masks, grad_params, ld_grad, workspace,
                                   workspace_bytes, S(stream)));
 }
+size_t uni_prop_workspace_bytes(int B, int Kc, int Q) { return prop_workspace_bytes(B, Kc, Q); }
+int uni_prop_labels(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int mask_rate,
+                    int32_t* matched, int32_t* num_matched, float* gt0, float* gt1, uni_stream_t stream) {
+    UNI_REQUIRE(targets && matched && num_matched && gt0 && gt1, "prop_labels: NULL argument");
+    API(launch_prop_labels(targets, masks, mask_u8, B, M, Kc, sot, H8, W8, mask_rate, matched, num_matched, gt0, gt1, S(stream)));
+}
+int uni_prop_labels_f64(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int mask_rate,
+                        int32_t* matched, int32_t* num_matched, double* gt0, double* gt1, uni_stream_t stream) {
+    UNI_REQUIRE(targets && matched && num_matched && gt0 && gt1, "prop_labels_f64: NULL argument");
+    API(launch_prop_labels_f64(targets, masks, mask_u8, B, M, Kc, sot, H8, W8, mask_rate, matched, num_matched, gt0, gt1, S(stream)));
+}
+int uni_prop_dice_pyramid_fwd(const float* pred, const float* gt1, const int32_t* num_matched, int B, int Kc, int H8, int W8, float* p16, float* p32,
+                              float* loss, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(pred && gt1 && p16 && p32 && loss && sums && workspace, "prop_dice_pyramid_fwd: NULL argument");
+    API(launch_prop_dice_pyramid_fwd(pred, gt1, num_matched, B, Kc, H8, W8, p16, p32, loss, sums, workspace, workspace_bytes, S(stream)));
+}
+int uni_prop_dice_pyramid_fwd_f64(const double* pred, const double* gt1, const int32_t* num_matched, int B, int Kc, int H8, int W8, double* p16,
+                                  double* p32, double* loss, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
+    UNI_REQUIRE(pred && gt1 && p16 && p32 && loss && sums && workspace, "prop_dice_pyramid_fwd_f64: NULL argument");
+    API(launch_prop_dice_pyramid_fwd_f64(pred, gt1, num_matched, B, Kc, H8, W8, p16, p32, loss, sums, workspace, workspace_bytes, S(stream)));
+}
+int uni_prop_dice_pyramid_bwd(const float* pred, const float* gt1, const int32_t* num_matched, const double* sums, const float* grad_p8,
+                              const float* grad_p16, const float* grad_p32, const float* grad_loss, int B, int Kc, int H8, int W8, float* grad_pred,
+                              uni_stream_t stream) {
+    UNI_REQUIRE(pred && gt1 && sums && grad_pred, "prop_dice_pyramid_bwd: NULL argument");
+    API(launch_prop_dice_pyramid_bwd(pred, gt1, num_matched, sums, grad_p8, grad_p16, grad_p32, grad_loss, B, Kc, H8, W8, grad_pred, S(stream)));
+}
+int uni_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const int32_t* num_matched, const double* sums, const double* grad_p8,
+                                  const double* grad_p16, const double* grad_p32, const double* grad_loss, int B, int Kc, int H8, int W8,
+                                  double* grad_pred, uni_stream_t stream) {
+    UNI_REQUIRE(pred && gt1 && sums && grad_pred, "prop_dice_pyramid_bwd_f64: NULL argument");
+    API(launch_prop_dice_pyramid_bwd_f64(pred, gt1, num_matched, sums, grad_p8, grad_p16, grad_p32, grad_loss, B, Kc, H8, W8, grad_pred, S(stream)));
+}
 size_t uni_mot_corr_workspace_bytes(int B, int M, int C) { return mot_corr_workspace_bytes(B, M, C); }
 int uni_mot_corr_loss_fwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
                           int B, int C, int H, int W, int M, float stride, int flags, float* loss, void* workspace, size_t workspace_bytes,

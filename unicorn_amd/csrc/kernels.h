@@ -242,6 +242,26 @@ int launch_mot_corr_fwd_f64(const double* e0, McStride s0, const double* e1, McS
 int launch_mot_corr_bwd_f64(const double* e0, McStride s0, const double* e1, McStride s1, const float* targets, const double* gout, int B, int C,
                             int H, int W, int M, float stride, int flags, double* g0, McStride gs0, double* g1, McStride gs1, void* ws,
                             size_t ws_bytes, hipStream_t s);
+// prop_loss.hip: what stands around the label propagation in the SOT / VOS training losses (unicorn.py:315-390), fp32 and fp64, no host read.
+// launch_prop_labels: targets [B][2][M][6] fp32 (+ masks [B][2][M][r H8][r W8] fp32 / uint8, or NULL: boxes) -> matched [B][Kc][2],
+// num_matched [B], gt0 / gt1 [B][Kc][H8 W8], all completely written; sot: one slot (0, 0) per sample.  launch_prop_dice_pyramid_fwd: pred, gt1
+// [B][Kc][H8][W8] -> p16, p32, loss ([B][Kc], or ONE value when num_matched is NULL: the SOT Dice over the batch), sums [groups][3] double
+// (I, X2, T2).  _bwd: g_pred [B][Kc][H8][W8] completely written from the upstream gradients (each may be NULL).  Workspace (forward only):
+// prop_workspace_bytes in both precisions.
+size_t prop_workspace_bytes(int B, int Kc, int Q);
+int launch_prop_labels(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int r, int* matched,
+                       int* num_matched, float* gt0, float* gt1, hipStream_t s);
+int launch_prop_labels_f64(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int r, int* matched,
+                           int* num_matched, double* gt0, double* gt1, hipStream_t s);
+int launch_prop_dice_pyramid_fwd(const float* pred, const float* gt1, const int* num_matched, int B, int Kc, int H8, int W8, float* p16, float* p32,
+                                 float* loss, double* sums, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_prop_dice_pyramid_fwd_f64(const double* pred, const double* gt1, const int* num_matched, int B, int Kc, int H8, int W8, double* p16,
+                                     double* p32, double* loss, double* sums, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_prop_dice_pyramid_bwd(const float* pred, const float* gt1, const int* num_matched, const double* sums, const float* g8, const float* g16,
+                                 const float* g32, const float* gl, int B, int Kc, int H8, int W8, float* gpred, hipStream_t s);
+int launch_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const int* num_matched, const double* sums, const double* g8,
+                                     const double* g16, const double* g32, const double* gl, int B, int Kc, int H8, int W8, double* gpred,
+                                     hipStream_t s);
 // head_loss.hip: the four detection losses of get_losses (unicorn_head_mask.py:646-745) for a batch from the device-side results of
 // launch_simota_assign, forward + backward, fp32 and fp64, two launches each way and no host read-back.  outputs [B][A][ld >= 5 + C],
 // origin [B][A][ldo >= 4] or NULL, labels [B][M][5], fg / mg / miou [B][A], num_fg / num_gt [B] device, xs / ys / st [A] ->

@@ -888,6 +888,166 @@ def mot_corr_loss(embed_0, embed_1, targets, s=8, bidirect=True, grid_sample=Tru
     return MotCorrLossFunction.apply(embed_0, embed_1, targets.detach().float().contiguous(), float(s), flags)
 
 
+_PL_SFX = {torch.float32: "", torch.float64: "_f64"}
+
+
+def _prop_ws(dev, B, Kc, Q):
+    need = L.lib().uni_prop_workspace_bytes(B, Kc, Q)
+    if need == 0:
+        raise L.UnicornHipError("prop_loss: shape B=%d Kc=%d Q=%d is outside the limits of uni_prop_dice_pyramid_fwd (include/unicorn_hip.h)" % (B, Kc, Q))
+    return torch.empty(need, device=dev, dtype=torch.uint8)
+
+
+def prop_labels(targets, H8, W8, Kc, dtype=torch.float32, masks=None, sot=False):
+    """`uni_prop_labels`: targets (B, 2, M, 6) fp32 contiguous device rows [cls, cx, cy, w, h, trackid] (+ masks (B, 2, M, r H8, r W8) fp32 / uint8
+    contiguous, r = 1, 2, 4) -> matched (B, Kc, 2) int32, num_matched (B,) int32, gt0, gt1 (B, Kc, H8 W8) of `dtype`: the match table of
+    compute_loss_vos (unicorn.py:352-361; sot: row 0 of both frames) and the stride-8 label rows of both frames, from boxes
+    (F.interpolate(get_label_map(..), 1/8)) or from the masks (init_with_mask).  Not differentiable, no host synchronisation."""
+    B, M, dev = targets.shape[0], targets.shape[2], targets.device
+    matched = torch.empty((B, Kc, 2), device=dev, dtype=torch.int32)
+    num = torch.empty((B,), device=dev, dtype=torch.int32)
+    gt0 = torch.empty((B, Kc, H8 * W8), device=dev, dtype=dtype)
+    gt1 = torch.empty_like(gt0)
+    r = 0 if masks is None else masks.shape[3] // H8
+    name = "uni_prop_labels" + _PL_SFX[dtype]
+    with torch.cuda.device(dev):
+        L.check(getattr(L.lib(), name)(L.ptr(targets), L.ptr(masks), 1 if masks is not None and masks.dtype == torch.uint8 else 0, B, M, Kc,
+                                       1 if sot else 0, H8, W8, r, L.ptr(matched), L.ptr(num), L.ptr(gt0), L.ptr(gt1), L.stream_ptr()), name)
+    return matched, num, gt0, gt1
+
+
+class PropDiceFunction(torch.autograd.Function):
+    """The Dice loss and the prior pyramid behind the label propagation (unicorn.py:329-334, :372-379, :509-519) in one forward pass and ONE
+    backward kernel: apply(pred (B, Kc, H8, W8), gt1 (B, Kc, H8 W8), num_matched (B,) int32 or None) -> (loss, p8, p16, p32).
+    p8 is `pred` itself; p16 / p32 = F.interpolate(pred, 1/2 and 1/4, bilinear).  num_matched given: loss (B, Kc), one Dice per slot, zero
+    behind num_matched[b]; None: ONE Dice over the batch (the SOT branch).  Differentiable in pred; the upstream gradients of all four
+    outputs are honoured, and one that is None costs nothing.  Saves pred, gt1 and three sums per Dice.  No host synchronisation; one
+    writer per gradient element: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, pred, gt1, num_matched):
+        B, Kc, H8, W8 = pred.shape
+        dev, dt = pred.device, pred.dtype
+        pred_, gt_ = pred.detach().contiguous(), gt1.contiguous()
+        groups = 1 if num_matched is None else B * Kc
+        p16 = torch.empty((B, Kc, H8 // 2, W8 // 2), device=dev, dtype=dt)
+        p32 = torch.empty((B, Kc, H8 // 4, W8 // 4), device=dev, dtype=dt)
+        loss = torch.empty(() if num_matched is None else (B, Kc), device=dev, dtype=dt)
+        sums = torch.empty((groups, 3), device=dev, dtype=torch.float64)
+        name = "uni_prop_dice_pyramid_fwd" + _PL_SFX[dt]
+        with torch.cuda.device(dev):
+            ws = _prop_ws(dev, B, Kc, H8 * W8)
+            L.check(getattr(L.lib(), name)(L.ptr(pred_), L.ptr(gt_), L.ptr(num_matched), B, Kc, H8, W8, L.ptr(p16), L.ptr(p32), L.ptr(loss), L.ptr(sums),
+                                           L.ptr(ws), ws.numel(), L.stream_ptr()), name)
+        ctx.save_for_backward(pred_, gt_, num_matched, sums)
+        ctx.set_materialize_grads(False)
+        return loss, pred, p16, p32
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, g_p8, g_p16, g_p32):
+        pred, gt1, num_matched, sums = ctx.saved_tensors
+        if not ctx.needs_input_grad[0] or (g_loss is None and g_p8 is None and g_p16 is None and g_p32 is None):
+            return None, None, None
+        B, Kc, H8, W8 = pred.shape
+        gs = [None if g is None else g.contiguous() for g in (g_p8, g_p16, g_p32, g_loss)]
+        g_pred = torch.empty_like(pred)                   # written completely by the call
+        name = "uni_prop_dice_pyramid_bwd" + _PL_SFX[pred.dtype]
+        with torch.cuda.device(pred.device):
+            L.check(getattr(L.lib(), name)(L.ptr(pred), L.ptr(gt1), L.ptr(num_matched), L.ptr(sums), *map(L.ptr, gs), B, Kc, H8, W8, L.ptr(g_pred),
+                                           L.stream_ptr()), name)
+        return g_pred, None, None
+
+
+def _prop_args(what, embed_0, embed_1, targets, img_size):
+    """the checks the two label-propagation losses share -> (B, C, H8, W8, M)"""
+    for n, t in (("embed_0", embed_0), ("embed_1", embed_1), ("targets", targets)):
+        if not isinstance(t, torch.Tensor):
+            raise L.UnicornHipError("%s: %s is not a tensor" % (what, n))
+    if embed_0.dim() != 4 or embed_1.shape != embed_0.shape or targets.dim() != 4 or targets.shape[0] != embed_0.shape[0] \
+            or targets.shape[1] != 2 or targets.shape[3] != 6 or targets.shape[2] < 1 or embed_0.shape[0] < 1:
+        raise L.UnicornHipError("%s: shapes %s, %s, %s do not fit embed_0 (B,C,H8,W8), embed_1 (B,C,H8,W8), targets (B,2,M,6) with B, M >= 1"
+                                % (what, tuple(embed_0.shape), tuple(embed_1.shape), tuple(targets.shape)))
+    try:
+        H, W = int(img_size[0]), int(img_size[1])
+    except (TypeError, IndexError, ValueError):
+        raise L.UnicornHipError("%s: img_size %r is not (height, width)" % (what, img_size))
+    B, Cc, H8, W8 = embed_0.shape
+    if H != 8 * H8 or W != 8 * W8 or H8 < 4 or W8 < 4:
+        raise L.UnicornHipError("%s: img_size (%d, %d) is not 8 x the %d x %d maps, or a map side is below 4" % (what, H, W, H8, W8))
+    if embed_0.dtype not in _PL_SFX or embed_1.dtype != embed_0.dtype:
+        raise L.UnicornHipError("%s: embedding dtypes %s / %s unsupported (both fp32 or both fp64; no fp16 / autocast input: the reference "
+                                "computes the embeddings under autocast(enabled=False))" % (what, embed_0.dtype, embed_1.dtype))
+    if Cc > 128 or (embed_0.dtype == torch.float32 and Cc != 128):
+        raise L.UnicornHipError("%s: C = %d channels unsupported: fp32 maps need C == 128, the limit of uni_corr_softmax_pv_lse (precision 0); "
+                                "fp64 maps C <= 128" % (what, Cc))
+    if targets.shape[2] > 1024:
+        raise L.UnicornHipError("%s: M = %d rows per frame is outside M <= 1024" % (what, targets.shape[2]))
+    return B, Cc, H8, W8, targets.shape[2]
+
+
+def _prop_propagate(embed_0, embed_1, gt0):
+    """propagate_labels on (B, C, H8, W8) maps; fp64 maps of fewer than 128 channels are padded with zero channels (the fp64 kernels are
+    written for 128 too; a zero channel adds an exact zero to every dot product)"""
+    e0, e1 = embed_0.flatten(2).transpose(1, 2), embed_1.flatten(2).transpose(1, 2)
+    if e0.shape[2] < 128:
+        e0, e1 = torch.nn.functional.pad(e0, (0, 128 - e0.shape[2])), torch.nn.functional.pad(e1, (0, 128 - e1.shape[2]))
+    return CorrSoftmaxPVFunction.apply(e0, e1, gt0, 0)
+
+
+def sot_prop_loss(embed_0, embed_1, targets, img_size):
+    """The label-propagation part of Unicorn.compute_loss_sot (unicorn.py:321-334, propagate=True) for the whole batch without a host
+    synchronisation: embed_0, embed_1 (B, 128, H8, W8) fp32 (or both fp64, C <= 128), NCHW or channels-last; targets (B, 2, M, 6) rows
+    [cls, cx, cy, w, h, trackid], converted with .detach().float(); img_size (H, W) = (8 H8, 8 W8).  Row 0 of each frame is the object.
+    -> corr_loss (0-d: ONE Dice over the batch, as the reference flattens it), (p8 (B,1,H8,W8), p16, p32) = pred_lbs1_ms for the head.
+    The label maps are built on the device without the full-resolution map (get_label_map's .tolist() is a synchronisation per sample);
+    the HW x HW matrix is never formed (propagate_labels); Dice and pyramid are one pass, their backward one kernel.  corr_loss and the three
+    priors are differentiable in both embeddings."""
+    B, Cc, H8, W8, M = _prop_args("sot_prop_loss", embed_0, embed_1, targets, img_size)
+    _need_cuda(embed_0, embed_1, targets)
+    if len({t.device for t in (embed_0, embed_1, targets)}) != 1:
+        raise L.UnicornHipError("sot_prop_loss: tensors on different devices")
+    t = targets.detach().float().contiguous()
+    _, _, gt0, gt1 = prop_labels(t, H8, W8, 1, embed_0.dtype, None, sot=True)
+    pred = _prop_propagate(embed_0, embed_1, gt0).view(B, 1, H8, W8)
+    loss, p8, p16, p32 = PropDiceFunction.apply(pred, gt1, None)
+    return loss, (p8, p16, p32)
+
+
+def vos_prop_loss(embed_0, embed_1, targets, img_size, masks=None, max_inst=None):
+    """The label-propagation part of Unicorn.compute_loss_vos (unicorn.py:342-379 without the head call) for the whole batch and ALL matched
+    instances at once, without a host synchronisation: embeddings, targets, img_size as in sot_prop_loss; masks (B, 2, M, r H8, r W8) fp32 or
+    uint8 with r = 1, 2, 4 = init_with_mask with scale_factor 1 / r (labels from the masks instead of the boxes); max_inst = the
+    reference's max_matched_inst.  Kc = min(M, max_inst or M) slots per sample, filled in the reference's order: i = 0 .. M-1 with
+    id_r[i] != 0 and the first j with id_c[j] != 0 and id_c[j] == id_r[i] (fp32 compare).
+    -> corr_loss (B, Kc) one Dice per slot, (p8 (B,Kc,H8,W8), p16, p32) the priors of every instance, matched (B, Kc, 2) int32 = (i, j),
+    num_matched (B,) int32.  Slots >= num_matched[b] hold -1, zero loss, zero priors and carry exactly zero gradient.  The reference's
+    average_dict is corr_loss.sum() / num_matched.sum().clamp(min=1) on the device.  All instances of a sample are value rows of ONE
+    propagation; the backward of the correlation walks them in chunks of 8 rows (KMAX in csrc/corr_bwd.hip), each chunk one more recompute
+    pass over the HW x HW tiles."""
+    B, Cc, H8, W8, M = _prop_args("vos_prop_loss", embed_0, embed_1, targets, img_size)
+    if max_inst is not None and int(max_inst) < 1:
+        raise L.UnicornHipError("vos_prop_loss: max_inst = %r is not positive" % (max_inst,))
+    Kc = M if max_inst is None else min(M, int(max_inst))
+    if masks is not None:
+        if not isinstance(masks, torch.Tensor) or masks.dim() != 5 or tuple(masks.shape[:3]) != (B, 2, M) \
+                or not any(tuple(masks.shape[3:]) == (r * H8, r * W8) for r in (1, 2, 4)):
+            raise L.UnicornHipError("vos_prop_loss: masks %s do not fit (B, 2, M, r H8, r W8) = (%d, 2, %d, r x %d, r x %d) with r = 1, 2 or 4"
+                                    % (None if not isinstance(masks, torch.Tensor) else tuple(masks.shape), B, M, H8, W8))
+        if masks.dtype not in (torch.float32, torch.uint8):
+            raise L.UnicornHipError("vos_prop_loss: masks of dtype %s unsupported (fp32 or uint8)" % masks.dtype)
+    _need_cuda(embed_0, embed_1, targets, masks)
+    if len({t.device for t in (embed_0, embed_1, targets) + (() if masks is None else (masks,))}) != 1:
+        raise L.UnicornHipError("vos_prop_loss: tensors on different devices")
+    if B * Kc > 32767:
+        raise L.UnicornHipError("vos_prop_loss: B x Kc = %d x %d slots is outside B Kc <= 32767" % (B, Kc))
+    t = targets.detach().float().contiguous()
+    matched, num, gt0, gt1 = prop_labels(t, H8, W8, Kc, embed_0.dtype, None if masks is None else masks.detach().contiguous())
+    pred = _prop_propagate(embed_0, embed_1, gt0).view(B, Kc, H8, W8)
+    loss, p8, p16, p32 = PropDiceFunction.apply(pred, gt1, num)
+    return loss, (p8, p16, p32), matched, num
+
+
 def condinst_masks_resized(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate, d_rate, r, H, W, thr=None):
     """condinst_masks + mask_resize in ONE call (uni_condinst_masks_u8): the CondInst scores of `params` resized by 1/r and pasted into
     (N, H, W) maps -- `> thr` bytes (mot_evaluator.py:804-805) or, with thr=None, fp32 probabilities (unicorn_vos.py:141-152) -- without the
