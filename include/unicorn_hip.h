@@ -467,6 +467,48 @@ int uni_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const i
                                   const double* grad_p16, const double* grad_p32, const double* grad_loss, int B, int Kc, int H8, int W8,
                                   double* grad_pred, uni_stream_t stream);
 
+/* The tail of a TRAINING iteration (unicorn/core/trainer.py:260-275): scaler.step(optimizer) with torch.optim.AdamW (single-tensor form,
+ * amsgrad = maximize = False; exp/unicorn_track.py:380-381), scaler.update() and ModelEMA.update (unicorn/utils/ema.py:50-63) over a LIST of fp32
+ * tensors in one pass over memory, without a host synchronisation, a read-back or an allocation.  At most three kernel launches with a scaler
+ * (check, update, finish) and two without, whatever the number and the sizes of the tensors; with a scaler one 4-byte memset node clears found_inf.
+ *   table      n_tensors entries of 64 bytes, 8-byte aligned, in device memory:
+ *                offset  0  float*  p        parameter (or, for an EMA-only entry, the model's float buffer / gradient-less parameter: read only)
+ *                offset  8  float*  g        gradient, NULL = absent
+ *                offset 16  float*  m        exp_avg      (may be NULL in an EMA-only entry)
+ *                offset 24  float*  v        exp_avg_sq   (may be NULL in an EMA-only entry)
+ *                offset 32  float*  e        the EMA copy
+ *                offset 40  int64   n        elements (0 allowed: the entry has no chunk)
+ *                offset 48  double  lr_factor   the entry's learning rate is lr x lr_factor (the trainer's param_group["factor"])
+ *                offset 56  float   weight_decay
+ *                offset 60  int32   flags    UNI_OPT_HAS_GRAD: AdamW + EMA; 0: EMA only
+ *              The arrays of an entry are n dense elements each, updated in storage order; arrays of different entries do not overlap.
+ *   block_map  total_chunks entries of 8 bytes: int32 tensor, uint32 chunk -> elements [chunk CH, min(n, (chunk + 1) CH)) of that tensor,
+ *              CH = uni_opt_chunk_elems() (a multiple of 4).  Every element of every tensor is covered by exactly one entry.  The first
+ *              vec_chunks entries are processed with 16-byte accesses (scalar head / tail of at most 3 elements): all non-NULL pointers of
+ *              their tensor must share their address modulo 16.  The other entries are processed element by element (pointers misaligned
+ *              relative to each other).  Entries that name no tensor of the table, or a chunk behind its end, are skipped.
+ *   uni_opt_table_bytes(n_tensors, total_chunks): bytes of ONE upload image that holds both, each part rounded up to 256 bytes: the table
+ *              at offset 0, the block map at offset uni_opt_table_bytes(n_tensors, 0).  0 for negative arguments.
+ *   state      step (fp32, one word for the list, as torch keeps it per tensor); scale (fp32), growth_tracker (int32), found_inf (fp32): the
+ *              scaler's words, all three NULL = no scaler.  found_inf is cleared by the call and holds 1.0 after a skipped step, else 0.
+ * The call:  with a scaler inv = float(1 / double(scale)) and found_inf = any(!isfinite(g inv)) over all gradients (the product is tested, as
+ *   unscale_ does); without one inv = 1 and there is no check.  If not found_inf, with t = step + 1 and gh = g inv, per element of an entry
+ *   with UNI_OPT_HAS_GRAD:  p *= 1 - lr_i wd_i;  m += (gh - m)(1 - beta1);  v = v beta2 + (1 - beta2) gh gh;
+ *   p -= (lr_i / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps), the bias corrections in double from the device step.  Then, always
+ *   and for every entry, e = fl(fl(e float(ema_decay)) + fl(float(1 - ema_decay) p)) with the p just written: three separate roundings, bit-equal to
+ *   the two lines of ModelEMA.update.  Finish: step += 1 unless skipped; torch's _amp_update_scale_ exactly (found_inf: scale *= backoff_factor,
+ *   tracker = 0; else tracker += 1 and at growth_interval scale *= growth_factor if that is finite, tracker = 0).  After a skipped step p, m, v
+ *   and step keep their bits.  The gradients are left scaled (the unscaled value lives in registers only).
+ * One writer per element, no atomics: two calls from the same state give the same bits.  Limits: 0 <= vec_chunks <= total_chunks < 2^31,
+ * n < 2^32 CH; errors (-1 and a uni_last_error text): NULL table / block_map / step, negative sizes, table_bytes < 64 n_tensors or map_bytes <
+ * 8 total_chunks ("too small"), a scaler without its three words or with growth_interval < 1. */
+#define UNI_OPT_HAS_GRAD 1
+int uni_opt_chunk_elems(void);
+size_t uni_opt_table_bytes(int n_tensors, int total_chunks);
+int uni_opt_step(const void* table, size_t table_bytes, const void* block_map, size_t map_bytes, int n_tensors, int vec_chunks, int total_chunks,
+                 float* step, float* scale, int32_t* growth_tracker, float* found_inf, double lr, double beta1, double beta2, double eps,
+                 double ema_decay, double growth_factor, double backoff_factor, int growth_interval, uni_stream_t stream);
+
 /* Input letterbox on the device (row 0 / N1): PreprocessorX.process (external/lib/test/tracker/unicorn_sot.py:111-123,
  * swap_rb = 1) and preproc (unicorn/data/data_augment.py:194-214, swap_rb = 0).  img_hwc: (h, w, 3) uint8 DEVICE buffer;
  * out_chw: (3, H, W) fp32 = cv2.resize(INTER_LINEAR, 8-bit fixed point) to (int(w r), int(h r)), r = min(H/h, W/w),

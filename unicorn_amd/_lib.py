@@ -113,6 +113,10 @@ PROTOS = {
     "uni_prop_dice_pyramid_fwd_f64": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_prop_dice_pyramid_bwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
     "uni_prop_dice_pyramid_bwd_f64": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
+    "uni_opt_chunk_elems": (c_i, []),
+    "uni_opt_table_bytes": (C.c_size_t, [c_i, c_i]),
+    "uni_opt_step": (c_i, [c_f, C.c_size_t, c_f, C.c_size_t, c_i, c_i, c_i, c_f, c_f, c_f, c_f, C.c_double, C.c_double, C.c_double, C.c_double,
+                           C.c_double, C.c_double, C.c_double, c_i, C.c_void_p]),
     "uni_mask_resize": (c_i, [c_f, c_i, c_i, c_i, C.c_double, c_i, c_i, C.c_float, c_f, c_f, C.c_void_p]),
     "uni_vos_merge": (c_i, [c_f, c_f, c_i, c_i, c_i, C.c_double, c_f, c_f, c_i, c_i, c_i, c_f, C.c_void_p]),
     "uni_mots_overlap_free": (c_i, [c_f, c_i, c_i, c_i, c_f, C.c_void_p]),

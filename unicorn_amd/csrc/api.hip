@@ -445,6 +445,15 @@ int uni_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const i
     UNI_REQUIRE(pred && gt1 && sums && grad_pred, "prop_dice_pyramid_bwd_f64: NULL argument");
     API(launch_prop_dice_pyramid_bwd_f64(pred, gt1, num_matched, sums, grad_p8, grad_p16, grad_p32, grad_loss, B, Kc, H8, W8, grad_pred, S(stream)));
 }
+int uni_opt_chunk_elems(void) { return opt_chunk_elems(); }
+size_t uni_opt_table_bytes(int n_tensors, int total_chunks) { return opt_table_bytes(n_tensors, total_chunks); }
+int uni_opt_step(const void* table, size_t table_bytes, const void* block_map, size_t map_bytes, int n_tensors, int vec_chunks, int total_chunks,
+                 float* step, float* scale, int32_t* growth_tracker, float* found_inf, double lr, double beta1, double beta2, double eps,
+                 double ema_decay, double growth_factor, double backoff_factor, int growth_interval, uni_stream_t stream) {
+    UNI_REQUIRE(table && block_map && step, "opt_step: NULL argument");
+    API(launch_opt_step(table, table_bytes, block_map, map_bytes, n_tensors, vec_chunks, total_chunks, step, scale, growth_tracker, found_inf, lr, beta1,
+                        beta2, eps, ema_decay, growth_factor, backoff_factor, growth_interval, S(stream)));
+}
 size_t uni_mot_corr_workspace_bytes(int B, int M, int C) { return mot_corr_workspace_bytes(B, M, C); }
 int uni_mot_corr_loss_fwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
                           int B, int C, int H, int W, int M, float stride, int flags, float* loss, void* workspace, size_t workspace_bytes,

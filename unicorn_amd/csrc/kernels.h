@@ -262,6 +262,13 @@ int launch_prop_dice_pyramid_bwd(const float* pred, const float* gt1, const int*
 int launch_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const int* num_matched, const double* sums, const double* g8,
                                      const double* g16, const double* g32, const double* gl, int B, int Kc, int H8, int W8, double* gpred,
                                      hipStream_t s);
+// opt_step.hip: GradScaler.step + torch.optim.AdamW + GradScaler.update + ModelEMA.update (trainer.py:260-275, utils/ema.py:50-63) over a list of
+// fp32 tensors through a tensor table and a block map in device memory (layouts: include/unicorn_hip.h), at most three launches, no host read.
+int opt_chunk_elems();
+size_t opt_table_bytes(int n_tensors, long long total_chunks);
+int launch_opt_step(const void* table, size_t table_bytes, const void* block_map, size_t map_bytes, int n_tensors, int vec_chunks, int total_chunks,
+                    float* step, float* scale, int* growth_tracker, float* found_inf, double lr, double beta1, double beta2, double eps,
+                    double ema_decay, double growth_factor, double backoff_factor, int growth_interval, hipStream_t s);
 // head_loss.hip: the four detection losses of get_losses (unicorn_head_mask.py:646-745) for a batch from the device-side results of
 // launch_simota_assign, forward + backward, fp32 and fp64, two launches each way and no host read-back.  outputs [B][A][ld >= 5 + C],
 // origin [B][A][ldo >= 4] or NULL, labels [B][M][5], fg / mg / miou [B][A], num_fg / num_gt [B] device, xs / ys / st [A] ->

@@ -1253,3 +1253,45 @@ def rle_encode(masks, max_runs=1 << 14):
     top = max(ln)
     host = chars[:, :top].cpu().numpy()
     return [host[i, :ln[i]].tobytes() for i in range(N)]
+
+
+def adamw_ema_step(params, grads, exp_avgs, exp_avg_sqs, emas, step, *, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, lr_factors=None,
+                   ema_decay, scaler=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, plan=None):
+    """`uni_opt_step`, the functional form of unicorn_amd.optim.FusedAdamWEMA over lists of fp32 device tensors, all updated IN PLACE:
+    GradScaler.step (unscale, non-finite check, skip) + torch.optim.AdamW's single-tensor update + GradScaler.update + ModelEMA.update
+    (trainer.py:260-275, utils/ema.py:50-63) in at most three launches and without a host read-back.
+
+    params[i], emas[i]                  parameter (or float buffer) and its EMA copy
+    grads[i], exp_avgs[i], exp_avg_sqs[i]   None = no gradient: the entry gets the EMA update only
+    step                                one fp32 device word (t - 1); incremented unless the step is skipped
+    lr, lr_factors[i], weight_decay     the entry's learning rate is lr * lr_factors[i]; weight_decay a float or one per entry
+    ema_decay                           d of `e = e * d + (1 - d) * p` (ModelEMA: decay * (1 - exp(-updates / 2000)), a host scalar)
+    scaler                              None or (scale fp32, growth_tracker int32, found_inf fp32) device words; found_inf is cleared by the call
+    plan                                the StepPlan a previous call returned: while the addresses and per-entry scalars stay the same, nothing
+                                        is uploaded.  -> the plan
+
+    The gradients are left scaled.  Entries must be dense with identical strides (a channels_last parameter with channels_last partners is
+    updated in storage order); bad arguments raise ValueError before the library is touched."""
+    from . import optim
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(emas) == n):
+        raise ValueError("adamw_ema_step: the five lists differ in length")
+    wds = [float(weight_decay)] * n if not hasattr(weight_decay, "__len__") else [float(w) for w in weight_decay]
+    lrf = [1.0] * n if lr_factors is None else [float(f) for f in lr_factors]
+    if len(wds) != n or len(lrf) != n:
+        raise ValueError("adamw_ema_step: lr_factors / weight_decay need one value per entry")
+    entries = [(p, g, m if g is not None else None, v if g is not None else None, e) for p, g, m, v, e in zip(params, grads, exp_avgs, exp_avg_sqs, emas)]
+    dev = optim.check_entries(entries, device_check=False)
+    optim.check_state_words(step, scaler, dev)
+    optim.need_cuda(dev)
+    if dev is None:
+        raise ValueError("adamw_ema_step: empty list")
+    addr = [[0 if t is None else t.data_ptr() for t in ent] for ent in entries]
+    key = (addr, lrf, wds)
+    plan = plan or optim.StepPlan()
+    if plan.key != key:
+        cols = {k: [a[j] for a in addr] for j, k in enumerate(("p", "g", "m", "v", "e"))}
+        cols.update(n=[ent[0].numel() for ent in entries], lr_factor=lrf, wd=wds, has_grad=[ent[1] is not None for ent in entries])
+        plan.upload(key, cols, dev)
+    plan.launch(step, scaler, lr, betas, eps, ema_decay, growth_factor, backoff_factor, growth_interval)
+    return plan
