@@ -60,10 +60,24 @@ __device__ __forceinline__ float act_apply_fast(float x, int act) {
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// 64-lane xor-butterfly sum (float, double, int, long long): every lane ends up with the total, the order is fixed
+template <typename V>
+__device__ __forceinline__ V wave_sum(V v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+// sum over a block of TB threads in a fixed tree (wave_sum, then the waves in ascending order); sm holds TB / 64 values; the result in thread 0
+template <int TB, typename V>
+__device__ __forceinline__ V block_sum(V v, V* sm) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    V r = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < TB / 64; ++w) r += sm[w];
+    __syncthreads();
+    return r;
 }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

@@ -22,14 +22,14 @@
 //             cl_dfeat_kernel    thread = coarse pixel, loops the instances of a chunk -> partials;  cl_dfeat_final adds the chunks in order
 //
 // The chunked A buffer (CL_CH x HW x 9) keeps the workspace at O(n HW) with a small constant instead of 9 x the logits.
+//
+// The kernels here are shells: the arithmetic and every summation order live in condinst_dev.h (the cl_* bodies), which
+// head_mask_loss.hip calls too.  A shell picks the instance (compacted index) and the rows it reads.
 #include "condinst_dev.h"
 
 namespace {
 
-constexpr int CL_IC = 8;       // forward: instances per thread (the tap softmax does not depend on the instance, misc.hip CU_IC)
 constexpr int CL_CH = 16;      // backward: instances per chunk launch
-constexpr int CL_PPT = 4;      // cl_dparams_kernel: coarse pixels per thread
-constexpr int CL_FB = 128;     // cl_dfeat_kernel block
 
 template <typename T>
 __global__ __launch_bounds__(256) void cl_mlp_kernel(const T* __restrict__ mask_feats, const T* __restrict__ params, int ldp,
@@ -60,52 +60,17 @@ __global__ __launch_bounds__(256) void cl_dice_kernel(const T* __restrict__ up_m
     const int y = pix / W, x = pix - y * W;
     const size_t fine = (size_t)(r * y + i) * (r * W) + r * x + j, fsz = (size_t)HWc * rr;
     const int i0 = blockIdx.y * CL_IC, cnt = min(n - i0, CL_IC);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int k = 0; k < cnt; ++k) {
-        T sg = (T)0, ss = (T)0, gg = (T)0;
-        if (valid) {
-            const T* L = logits + (size_t)(i0 + k) * HWc;
-            T u = (T)0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) u += wt[t] * (off[t] >= 0 ? L[off[t]] : (T)0);
-            const T s = (T)1 / ((T)1 + cl_exp<T>(-u));
-            const T g = gt[(size_t)(i0 + k) * fsz + fine];
-            sg = s * g; ss = s * s; gg = g * g;
-        }
-        sg = cl_wave_sum(sg); ss = cl_wave_sum(ss); gg = cl_wave_sum(gg);
-        if (lane == 0) { red[wave][3 * k] = sg; red[wave][3 * k + 1] = ss; red[wave][3 * k + 2] = gg; }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 3 * cnt) {
-        const int t = threadIdx.x;
-        part[((size_t)(i0 + t / 3) * nblk + blockIdx.x) * 3 + t % 3] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-    }
+    const auto g_at = [=](int inst) { return gt[(size_t)inst * fsz + fine]; };
+    for (int k = 0; k < cnt; ++k) cl_dice_accum(wt, off, valid, logits, HWc, g_at, i0 + k, red, k);
+    cl_dice_combine(i0, cnt, red, part, nblk);
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void cl_dice_final(const T* __restrict__ part, int nblk, T* __restrict__ sums, T* __restrict__ loss) {
     __shared__ T red[3][256];
-    const int inst = blockIdx.x, tid = threadIdx.x;
-    T a[3] = {(T)0, (T)0, (T)0};
-    for (int b = tid; b < nblk; b += 256) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a[c] += part[((size_t)inst * nblk + b) * 3 + c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) red[c][tid] = a[c];
-    __syncthreads();
-    for (int d = 128; d >= 1; d >>= 1) {
-        if (tid < d) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) red[c][tid] += red[c][tid + d];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const T I = red[0][0], U = red[1][0] + red[2][0] + (T)1e-5;
-        sums[inst * 3] = I; sums[inst * 3 + 1] = red[1][0]; sums[inst * 3 + 2] = red[2][0];
-        loss[inst] = (T)1 - (T)2 * I / U;
-    }
+    T a[3];
+    cl_dice_partial(part, blockIdx.x, nblk, a);
+    cl_dice_finish(a, red, blockIdx.x, sums, loss);
 }
 
 template <typename T>
@@ -125,40 +90,11 @@ __global__ __launch_bounds__(256) void cl_du_kernel(const T* __restrict__ up_mas
     T* gum = grad_um ? grad_um + (size_t)pix * 9 * rr + i * r + j : nullptr;
 #pragma unroll
     for (int t = 0; t < 9; ++t) acc[t] = (gum && valid && c0 > 0) ? gum[t * rr] : (T)0;
-    const int span = PX * r, pix0 = blockIdx.x * PX;
+    const auto g_at = [=](int inst) { return gt[(size_t)inst * fsz + fine]; };
     for (int k = 0; k < cnt; ++k) {
-        const int inst = c0 + k;
-        const T I = sums[inst * 3], U = sums[inst * 3 + 1] + sums[inst * 3 + 2] + (T)1e-5, go = gout[inst];
-        const T ca = (T)-2 * go / U, cb = (T)4 * go * I / (U * U);
         T c[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) c[t] = (T)0;
-        if (valid) {
-            const T* L = logits + (size_t)inst * HWc;
-            T Lt[9], u = (T)0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) { Lt[t] = off[t] >= 0 ? L[off[t]] : (T)0; u += wt[t] * Lt[t]; }
-            const T s = (T)1 / ((T)1 + cl_exp<T>(-u));
-            const T g = gt[(size_t)inst * fsz + fine];
-            const T du = (ca * g + cb * s) * (s * ((T)1 - s));
-#pragma unroll
-            for (int t = 0; t < 9; ++t) { c[t] = wt[t] * du; acc[t] += c[t] * (Lt[t] - u); }
-        }
-        if (want_dl) {
-#pragma unroll
-            for (int t = 0; t < 9; ++t) cs[t][threadIdx.x] = c[t];
-            __syncthreads();
-            for (int o = threadIdx.x; o < PX * 9; o += 256) {
-                const int pl = o / 9, t = o - pl * 9;
-                if (pix0 + pl < HWc) {
-                    T s = (T)0;
-                    for (int ii = 0; ii < r; ++ii)
-                        for (int jj = 0; jj < r; ++jj) s += cs[t][ii * span + pl * r + jj];
-                    A[((size_t)k * HWc + pix0 + pl) * 9 + t] = s;
-                }
-            }
-            __syncthreads();
-        }
+        cl_du_instance(sums, gout[c0 + k], wt, off, valid, logits, HWc, g_at, c0 + k, c, acc);
+        if (want_dl) cl_stage_taps(c, cs, A, k, r, PX, HWc);
     }
     if (gum && valid) {
 #pragma unroll
@@ -171,42 +107,7 @@ __global__ __launch_bounds__(256) void cl_gather_kernel(const T* __restrict__ A,
     const int HWc = H * W, q = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
     if (q >= HWc) return;
     const int y = q / W, x = q - y * W;
-    T s = (T)0;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {      // the coarse pixel p whose tap t reads q: p + delta_t = q
-        const int yy = y - (t / 3 - 1), xx = x - (t % 3 - 1);
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) s += A[((size_t)k * HWc + yy * W + xx) * 9 + t];
-    }
-    dL[(size_t)(c0 + k) * HWc + q] = s;
-}
-
-template <typename T, int HALF>
-__device__ __forceinline__ void cl_dparams_half(const T* prm, T (*red)[CL_NP], const T* __restrict__ mask_feats, const T* __restrict__ inst_loc,
-                                                const int* __restrict__ inst_lvl, const T* __restrict__ dL, int HWc, int W, T* __restrict__ part,
-                                                int nblk) {
-    const int inst = blockIdx.y, tid = threadIdx.x;
-    T gp[CL_NP];
-#pragma unroll
-    for (int i = 0; i < CL_NP; ++i) gp[i] = (T)0;
-    for (int k = 0; k < CL_PPT; ++k) {
-        const int pix = (blockIdx.x * CL_PPT + k) * 256 + tid;
-        if (pix < HWc) {
-            T in[10];
-            cl_inputs(mask_feats, inst_loc, inst_lvl, inst, pix, W, in);
-            cl_mlp_bwd<T, HALF>(prm, in, dL[(size_t)inst * HWc + pix], gp, nullptr);
-        }
-    }
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int i = 0; i < CL_NP; ++i) {
-        if (cl_in_half(HALF, i)) {
-            const T v = cl_wave_sum(gp[i]);
-            if (lane == 0) red[wave][i] = v;
-        }
-    }
-    __syncthreads();
-    if (tid < CL_NP && cl_in_half(HALF, tid))
-        part[((size_t)inst * nblk + blockIdx.x) * CL_NP + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    dL[(size_t)(c0 + k) * HWc + q] = cl_gather_pixel(A, k, y, x, H, W);
 }
 
 template <typename T>
@@ -217,8 +118,8 @@ __global__ __launch_bounds__(256) void cl_dparams_kernel(const T* __restrict__ m
     __shared__ T red[4][CL_NP];
     for (int i = threadIdx.x; i < CL_NP; i += 256) prm[i] = params[(size_t)blockIdx.y * ldp + i];
     __syncthreads();
-    if (blockIdx.z == 0) cl_dparams_half<T, 0>(prm, red, mask_feats, inst_loc, inst_lvl, dL, HWc, W, part, nblk);
-    else cl_dparams_half<T, 1>(prm, red, mask_feats, inst_loc, inst_lvl, dL, HWc, W, part, nblk);
+    if (blockIdx.z == 0) cl_dparams_half<T, 0>(prm, red, mask_feats, inst_loc, inst_lvl, dL, blockIdx.y, HWc, W, part, nblk);
+    else cl_dparams_half<T, 1>(prm, red, mask_feats, inst_loc, inst_lvl, dL, blockIdx.y, HWc, W, part, nblk);
 }
 
 template <typename T>
@@ -240,17 +141,8 @@ __global__ __launch_bounds__(CL_FB) void cl_dfeat_kernel(const T* __restrict__ m
     T dmf[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) dmf[c] = (T)0;
-    for (int k = 0; k < cnt; ++k) {
-        const int inst = c0 + k;
-        __syncthreads();
-        for (int i = threadIdx.x; i < CL_NP; i += CL_FB) prm[i] = params[(size_t)inst * ldp + i];
-        __syncthreads();
-        if (valid) {
-            T in[10];
-            cl_inputs(mask_feats, inst_loc, inst_lvl, inst, pix, W, in);
-            cl_mlp_bwd<T, -1>(prm, in, dL[(size_t)inst * HWc + pix], nullptr, dmf);
-        }
-    }
+    for (int inst = c0; inst < c0 + cnt; ++inst)
+        cl_dfeat_instance(prm, params + (size_t)inst * ldp, mask_feats, inst_loc, inst_lvl, dL, inst, pix, valid, HWc, W, dmf);
     if (valid) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) part[((size_t)blockIdx.y * HWc + pix) * 8 + c] = dmf[c];

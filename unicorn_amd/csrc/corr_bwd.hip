@@ -272,13 +272,8 @@ int run_pass(const float* eown, const float* estr, int n_own, int n_str, const f
 }
 
 // ---------------------------------------------------------------- fp64: one wave per output row, FMA loops, fixed summation order
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ double dot128(const double* __restrict__ a, double b0, double b1, int lane) {
-    return wave_sum_d(fma(a[lane], b0, a[lane + 64] * b1));
+    return wave_sum(fma(a[lane], b0, a[lane + 64] * b1));
 }
 
 // wave per (frame, q): lse[q], out[k][q]

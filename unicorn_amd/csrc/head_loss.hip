@@ -48,28 +48,6 @@ __device__ __forceinline__ T hl_bce(T x, T t) { return (x > 0 ? x : (T)0) - x * 
 template <typename T>
 __device__ __forceinline__ T hl_sigmoid(T x) { return (T)1 / ((T)1 + hl_exp(-x)); }
 
-__device__ __forceinline__ double hl_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long hl_wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <typename V>
-__device__ __forceinline__ V hl_block_sum(V v, V* sm) {      // HL_TB threads, summed in a fixed tree; the result in thread 0
-    v = hl_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    V r = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < HL_TB / 64; ++w) r += sm[w];
-    __syncthreads();
-    return r;
-}
-
 // the matched box of a foreground anchor: a matched_gt outside 0..M-1 and a class outside 0..C-1 are clamped
 // The box, IoU and L1 lines of a foreground anchor run in double in both precisions: the foreground is sparse (at most ten anchors per
 // box), so this costs nothing, and the fp32 form then carries only the rounding of its inputs and of its results.
@@ -168,7 +146,7 @@ hl_fwd_kernel(HlIn<T> p, double* __restrict__ part) {
         s_cls += (double)l;
     }
     double* dst = part + ((size_t)b * gridDim.x + blockIdx.x) * 4;
-    const double r0 = hl_block_sum(s_iou, sm), r1 = hl_block_sum(s_obj, sm), r2 = hl_block_sum(s_cls, sm), r3 = hl_block_sum(s_l1, sm);
+    const double r0 = block_sum<HL_TB>(s_iou, sm), r1 = block_sum<HL_TB>(s_obj, sm), r2 = block_sum<HL_TB>(s_cls, sm), r3 = block_sum<HL_TB>(s_l1, sm);
     if (threadIdx.x == 0) {
         dst[0] = r0;
         dst[1] = r1;
@@ -180,7 +158,7 @@ hl_fwd_kernel(HlIn<T> p, double* __restrict__ part) {
 __device__ __forceinline__ long long hl_count(const int* __restrict__ v, int B, int hi, long long* sm) {      // sum of clamp(v[b], 0, hi)
     long long s = 0;
     for (int b = threadIdx.x; b < B; b += HL_TB) s += min(max(v[b], 0), hi);
-    return hl_block_sum(s, sm);
+    return block_sum<HL_TB>(s, sm);
 }
 
 template <typename T>
@@ -194,7 +172,7 @@ hl_final_kernel(const double* __restrict__ part, size_t nblocks, const int* __re
 #pragma unroll
         for (int q = 0; q < 4; ++q) s[q] += part[k * 4 + q];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) s[q] = hl_block_sum(s[q], sm);
+    for (int q = 0; q < 4; ++q) s[q] = block_sum<HL_TB>(s[q], sm);
     const long long nfg = hl_count(num_fg, B, A, si), ngt = hl_count(num_gt, B, M, si);
     if (threadIdx.x == 0) {
         const double n = (double)(nfg > 1 ? nfg : 1);

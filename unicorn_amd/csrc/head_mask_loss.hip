@@ -11,19 +11,23 @@
 // table: slot-strided loops, or S sub-ranges of an image's instances whose partials are added in a fixed order.  5 launches forward and at
 // most 22 backward whatever the data, B, A, M and capacity.  One writer per output element, fixed summation orders, no float atomics.
 //
+// The per-instance arithmetic is NOT written here: the kernels that have a per-image twin in condinst_loss.hip call the same bodies of
+// condinst_dev.h (named on the right) and only choose the slots a block handles and the rows a slot reads (t.row / t.gt / t.img / t.lvl).
+//
 //   forward   hm_table_kernel   the table; more instances than capacity: the overflow flag, counts forced to 0 (nothing is indexed by a slot)
-//             hm_mlp_kernel     logits[slot][HW]                                  block (pixel tile, slot stride)
-//             hm_dice_kernel    block partials of (sum s g, sum s^2, sum g^2)     block (fine-pixel tile, sub-range, image), taps once per thread
-//             hm_dice_final     partials -> sums[slot][3], dice[slot]             block per slot (strided), fixed-order tree
+//             hm_mlp_kernel     block (pixel tile, slot stride)                             cl_inputs, cl_mlp
+//             hm_dice_kernel    block (fine-pixel tile, sub-range, image)                   cl_dice_accum, cl_dice_combine per group of CL_IC slots
+//             hm_dice_final     block per slot (strided)                                    cl_dice_partial, cl_dice_finish
 //             hm_reduce_kernel  out[0] = loss, out[1 + b] = loss_mask[b]; NaN everywhere on overflow
 //   backward  hm_table_kernel, hm_mlp_kernel again (the workspace is scratch between calls)
 //             HM_NC = 8 passes over the instance range (pass c = slots [c per, (c + 1) per), per = ceil(n / 8) from the table), in stream order:
 //               hm_du_kernel      block (fine-pixel tile, image) loops the instances of its image in the pass: d up_masks accumulates in the
-//                                 owning thread's registers (pass c adds to what pass c - 1 left); A[slot - c0][p][t] = sum_sub w_t du
-//               hm_gather_kernel  dL[slot][q] = sum_t A[slot - c0][q - delta_t][t]
-//             hm_dparams_kernel / hm_dparams_final   per slot, two halves of the 169 columns -> partials -> the DENSE grad_params [B][A][169]
+//                                 owning thread's registers (pass c adds to what pass c - 1 left)    cl_du_instance, cl_stage_taps -> A[slot - c0]
+//               hm_gather_kernel  dL[slot][q]                                                cl_gather_pixel
+//             hm_dparams_kernel / hm_dparams_final   per slot (cl_dparams_half) -> partials -> the DENSE grad_params [B][A][169]
 //                               (background rows and everything on overflow: exact zeros) through slot_of[b][a]
-//             hm_dfeat_kernel / hm_dfeat_final       thread = coarse pixel, S sub-ranges of the image's instances -> partials -> grad_mask_feats
+//             hm_dfeat_kernel / hm_dfeat_final       thread = coarse pixel, S sub-ranges of the image's instances (cl_dfeat_instance) -> partials
+//                               -> grad_mask_feats
 //
 // Workspace, in elements of T after the integer table: capacity x H8 W8 x (1 logits + 1 dL) + ceil(capacity / 8) x H8 W8 x 9 (A) + capacity x (3 nblk_d + 169 nblk_p + 3)
 // + B x S x H8 W8 x 8  (hm_layout).
@@ -31,10 +35,7 @@
 
 namespace {
 
-constexpr int HM_IC = 8;        // forward: instances per pass of the dice kernel (cl_dice_kernel's CL_IC)
 constexpr int HM_S = 8;         // sub-ranges an image's instances are split into (dice forward, d mask_feats)
-constexpr int HM_PPT = 4;       // hm_dparams_kernel: coarse pixels per thread
-constexpr int HM_FB = 128;      // hm_dfeat_kernel block
 constexpr int HM_GS = 256;      // most blocks of a slot-strided grid dimension
 constexpr int HM_TB = 1024;     // hm_table_kernel block
 constexpr int HM_CI = 64;       // hm_table_kernel: images counted per round
@@ -44,12 +45,6 @@ constexpr int HM_HDR = 4;       // table header: instances in use (0 on overflow
 struct HMTable {                // device pointers into the integer part of the workspace
     int *hdr, *cnt, *off, *row, *img, *gt, *lvl, *slot_of;
 };
-
-__device__ __forceinline__ int hm_wave_sum_i(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
 
 // number of non-zero bytes of a word
 __device__ __forceinline__ int hm_nz4(unsigned w) {
@@ -84,7 +79,7 @@ __global__ __launch_bounds__(HM_TB) void hm_table_kernel(const unsigned char* __
             } else {
                 for (int a = tid; a < A; a += HM_TB) c += row[a] != 0;
             }
-            c = hm_wave_sum_i(c);
+            c = cl_wave_sum(c);
             if (lane == 0 && c) atomicAdd(&s_cnt[k], c);     // integer: the sum does not depend on the order
         }
         __syncthreads();
@@ -180,7 +175,7 @@ __device__ __forceinline__ void hm_range(const HMTable& t, int b, int z, int& k0
 template <typename T>
 __global__ __launch_bounds__(256) void hm_dice_kernel(const T* __restrict__ up_masks, const T* __restrict__ logits, const T* __restrict__ masks,
                                                       HMTable t, T* __restrict__ part, int H, int W, int r, int PX, int nblk) {
-    __shared__ T red[4][3 * HM_IC];
+    __shared__ T red[4][3 * CL_IC];
     int k0, k1;
     hm_range(t, blockIdx.z, blockIdx.y, k0, k1);
     if (k0 >= k1) return;
@@ -193,28 +188,11 @@ __global__ __launch_bounds__(256) void hm_dice_kernel(const T* __restrict__ up_m
     cl_taps(up_masks + (size_t)blockIdx.z * HWc * 9 * rr, pix, i * r + j, rr, H, W, valid, wt, off);
     const int y = pix / W, x = pix - y * W;
     const size_t fine = (size_t)(r * y + i) * (r * W) + r * x + j, fsz = (size_t)HWc * rr;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int i0 = k0; i0 < k1; i0 += HM_IC) {
-        const int cnt = min(k1 - i0, HM_IC);
-        for (int k = 0; k < cnt; ++k) {
-            T sg = (T)0, ss = (T)0, gg = (T)0;
-            if (valid) {
-                const T* L = logits + (size_t)(i0 + k) * HWc;
-                T u = (T)0;
-#pragma unroll
-                for (int tt = 0; tt < 9; ++tt) u += wt[tt] * (off[tt] >= 0 ? L[off[tt]] : (T)0);
-                const T s = (T)1 / ((T)1 + cl_exp<T>(-u));
-                const T g = masks[(size_t)t.gt[i0 + k] * fsz + fine];
-                sg = s * g; ss = s * s; gg = g * g;
-            }
-            sg = cl_wave_sum(sg); ss = cl_wave_sum(ss); gg = cl_wave_sum(gg);
-            if (lane == 0) { red[wave][3 * k] = sg; red[wave][3 * k + 1] = ss; red[wave][3 * k + 2] = gg; }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < 3 * cnt) {
-            const int e = threadIdx.x;
-            part[((size_t)(i0 + e / 3) * nblk + blockIdx.x) * 3 + e % 3] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-        }
+    const auto g_at = [=](int slot) { return masks[(size_t)t.gt[slot] * fsz + fine]; };
+    for (int i0 = k0; i0 < k1; i0 += CL_IC) {
+        const int cnt = min(k1 - i0, CL_IC);
+        for (int k = 0; k < cnt; ++k) cl_dice_accum(wt, off, valid, logits, HWc, g_at, i0 + k, red, k);
+        cl_dice_combine(i0, cnt, red, part, nblk);
         __syncthreads();
     }
 }
@@ -222,29 +200,12 @@ __global__ __launch_bounds__(256) void hm_dice_kernel(const T* __restrict__ up_m
 template <typename T>
 __global__ __launch_bounds__(256) void hm_dice_final(const T* __restrict__ part, int nblk, HMTable t, T* __restrict__ sums, T* __restrict__ dice) {
     __shared__ T red[3][256];
-    const int n = t.hdr[0], tid = threadIdx.x;
+    const int n = t.hdr[0];
     for (int slot = blockIdx.x; slot < n; slot += gridDim.x) {
-        T a[3] = {(T)0, (T)0, (T)0};
-        for (int b = tid; b < nblk; b += 256) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) a[c] += part[((size_t)slot * nblk + b) * 3 + c];
-        }
+        T a[3];
+        cl_dice_partial(part, slot, nblk, a);
         __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 3; ++c) red[c][tid] = a[c];
-        __syncthreads();
-        for (int d = 128; d >= 1; d >>= 1) {
-            if (tid < d) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) red[c][tid] += red[c][tid + d];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            const T I = red[0][0], U = red[1][0] + red[2][0] + (T)1e-5;
-            sums[slot * 3] = I; sums[slot * 3 + 1] = red[1][0]; sums[slot * 3 + 2] = red[2][0];
-            dice[slot] = (T)1 - (T)2 * I / U;
-        }
+        cl_dice_finish(a, red, slot, sums, dice);
     }
 }
 
@@ -297,40 +258,12 @@ __global__ __launch_bounds__(256) void hm_du_kernel(const T* __restrict__ up_mas
     T* gum = (grad_um && valid) ? grad_um + ((size_t)b * HWc + pix) * 9 * rr + i * r + j : nullptr;
 #pragma unroll
     for (int tt = 0; tt < 9; ++tt) acc[tt] = (gum && pass > 0) ? gum[tt * rr] : (T)0;
-    const int span = PX * r, pix0 = blockIdx.x * PX;
     const T go = n > 0 ? gout[0] / ((T)n * (T)max(t.hdr[1], 1)) : (T)0;      // d loss / d dice of every instance of this image
+    const auto g_at = [=](int slot) { return masks[(size_t)t.gt[slot] * fsz + fine]; };
     for (int slot = k0; slot < k1; ++slot) {
-        const T I = sums[slot * 3], U = sums[slot * 3 + 1] + sums[slot * 3 + 2] + (T)1e-5;
-        const T ca = (T)-2 * go / U, cb = (T)4 * go * I / (U * U);
         T c[9];
-#pragma unroll
-        for (int tt = 0; tt < 9; ++tt) c[tt] = (T)0;
-        if (valid) {
-            const T* L = logits + (size_t)slot * HWc;
-            T Lt[9], u = (T)0;
-#pragma unroll
-            for (int tt = 0; tt < 9; ++tt) { Lt[tt] = off[tt] >= 0 ? L[off[tt]] : (T)0; u += wt[tt] * Lt[tt]; }
-            const T s = (T)1 / ((T)1 + cl_exp<T>(-u));
-            const T g = masks[(size_t)t.gt[slot] * fsz + fine];
-            const T du = (ca * g + cb * s) * (s * ((T)1 - s));
-#pragma unroll
-            for (int tt = 0; tt < 9; ++tt) { c[tt] = wt[tt] * du; acc[tt] += c[tt] * (Lt[tt] - u); }
-        }
-        if (want_dl) {
-#pragma unroll
-            for (int tt = 0; tt < 9; ++tt) cs[tt][threadIdx.x] = c[tt];
-            __syncthreads();
-            for (int o = threadIdx.x; o < PX * 9; o += 256) {
-                const int pl = o / 9, tt = o - pl * 9;
-                if (pix0 + pl < HWc) {
-                    T s = (T)0;
-                    for (int ii = 0; ii < r; ++ii)
-                        for (int jj = 0; jj < r; ++jj) s += cs[tt][ii * span + pl * r + jj];
-                    A[((size_t)(slot - c0) * HWc + pix0 + pl) * 9 + tt] = s;
-                }
-            }
-            __syncthreads();
-        }
+        cl_du_instance(sums, go, wt, off, valid, logits, HWc, g_at, slot, c, acc);
+        if (want_dl) cl_stage_taps(c, cs, A, slot - c0, r, PX, HWc);
     }
     if (gum) {
 #pragma unroll
@@ -345,45 +278,8 @@ __global__ __launch_bounds__(256) void hm_gather_kernel(const T* __restrict__ A,
     int c0, c1;
     hm_pass(t, pass, c0, c1);
     const int y = q / W, x = q - y * W;
-    for (int slot = c0 + blockIdx.y; slot < c1; slot += gridDim.y) {
-        T s = (T)0;
-#pragma unroll
-        for (int tt = 0; tt < 9; ++tt) {      // the coarse pixel p whose tap t reads q: p + delta_t = q
-            const int yy = y - (tt / 3 - 1), xx = x - (tt % 3 - 1);
-            if (yy >= 0 && yy < H && xx >= 0 && xx < W) s += A[((size_t)(slot - c0) * HWc + yy * W + xx) * 9 + tt];
-        }
-        dL[(size_t)slot * HWc + q] = s;
-    }
-}
-
-// cl_dparams_half for one slot
-template <typename T, int HALF>
-__device__ __forceinline__ void hm_dparams_half(const T* prm, T (*red)[CL_NP], const T* __restrict__ mask_feats, const T* __restrict__ loc,
-                                                const int* __restrict__ lvl, const T* __restrict__ dL, int slot, int HWc, int W,
-                                                T* __restrict__ part, int nblk) {
-    const int tid = threadIdx.x;
-    T gp[CL_NP];
-#pragma unroll
-    for (int i = 0; i < CL_NP; ++i) gp[i] = (T)0;
-    for (int k = 0; k < HM_PPT; ++k) {
-        const int pix = (blockIdx.x * HM_PPT + k) * 256 + tid;
-        if (pix < HWc) {
-            T in[10];
-            cl_inputs(mask_feats, loc, lvl, slot, pix, W, in);
-            cl_mlp_bwd<T, HALF>(prm, in, dL[(size_t)slot * HWc + pix], gp, nullptr);
-        }
-    }
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int i = 0; i < CL_NP; ++i) {
-        if (cl_in_half(HALF, i)) {
-            const T v = cl_wave_sum(gp[i]);
-            if (lane == 0) red[wave][i] = v;
-        }
-    }
-    __syncthreads();
-    if (tid < CL_NP && cl_in_half(HALF, tid))
-        part[((size_t)slot * nblk + blockIdx.x) * CL_NP + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    for (int slot = c0 + blockIdx.y; slot < c1; slot += gridDim.y)
+        dL[(size_t)slot * HWc + q] = cl_gather_pixel(A, slot - c0, y, x, H, W);
 }
 
 template <typename T>
@@ -398,8 +294,8 @@ __global__ __launch_bounds__(256) void hm_dparams_kernel(const T* __restrict__ m
         for (int i = threadIdx.x; i < CL_NP; i += 256) prm[i] = params[(size_t)t.row[slot] * ldp + i];
         __syncthreads();
         const T* mf = mask_feats + (size_t)t.img[slot] * HWc * 8;
-        if (blockIdx.z == 0) hm_dparams_half<T, 0>(prm, red, mf, loc, t.lvl, dL, slot, HWc, W, part, nblk);
-        else hm_dparams_half<T, 1>(prm, red, mf, loc, t.lvl, dL, slot, HWc, W, part, nblk);
+        if (blockIdx.z == 0) cl_dparams_half<T, 0>(prm, red, mf, loc, t.lvl, dL, slot, HWc, W, part, nblk);
+        else cl_dparams_half<T, 1>(prm, red, mf, loc, t.lvl, dL, slot, HWc, W, part, nblk);
     }
 }
 
@@ -418,11 +314,11 @@ __global__ __launch_bounds__(256) void hm_dparams_final(const T* __restrict__ pa
 }
 
 template <typename T>
-__global__ __launch_bounds__(HM_FB) void hm_dfeat_kernel(const T* __restrict__ mask_feats, const T* __restrict__ params, int ldp, HMTable t,
+__global__ __launch_bounds__(CL_FB) void hm_dfeat_kernel(const T* __restrict__ mask_feats, const T* __restrict__ params, int ldp, HMTable t,
                                                           const T* __restrict__ loc, const T* __restrict__ dL, int HWc, int W,
                                                           T* __restrict__ part) {
     __shared__ T prm[CL_NP];
-    const int pix = blockIdx.x * HM_FB + threadIdx.x, b = blockIdx.z;
+    const int pix = blockIdx.x * CL_FB + threadIdx.x, b = blockIdx.z;
     const bool valid = pix < HWc;
     int k0, k1;
     hm_range(t, b, blockIdx.y, k0, k1);
@@ -430,16 +326,8 @@ __global__ __launch_bounds__(HM_FB) void hm_dfeat_kernel(const T* __restrict__ m
     T dmf[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) dmf[c] = (T)0;
-    for (int slot = k0; slot < k1; ++slot) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < CL_NP; i += HM_FB) prm[i] = params[(size_t)t.row[slot] * ldp + i];
-        __syncthreads();
-        if (valid) {
-            T in[10];
-            cl_inputs(mf, loc, t.lvl, slot, pix, W, in);
-            cl_mlp_bwd<T, -1>(prm, in, dL[(size_t)slot * HWc + pix], nullptr, dmf);
-        }
-    }
+    for (int slot = k0; slot < k1; ++slot)
+        cl_dfeat_instance(prm, params + (size_t)t.row[slot] * ldp, mf, loc, t.lvl, dL, slot, pix, valid, HWc, W, dmf);
     if (valid) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) part[(((size_t)b * HM_S + blockIdx.y) * HWc + pix) * 8 + c] = dmf[c];
@@ -467,7 +355,7 @@ HMLayout hm_layout(int B, int A, int H, int W, int r, int cap) {
     const size_t hw = (size_t)H * W, c = (size_t)cap;
     l.PX = 256 / (r * r);
     l.nblk_d = cdiv(H * W, l.PX);
-    l.nblk_p = cdiv(H * W, 256 * HM_PPT);
+    l.nblk_p = cdiv(H * W, 256 * CL_PPT);
     size_t o = 0;
     l.hdr = o;     o += HM_HDR;
     l.cnt = o;     o += B;
@@ -571,7 +459,7 @@ int hm_bwd(const HMIn<T>& a, const T* sums, const T* gout, T* gmf, T* gum, T* gp
         hipLaunchKernelGGL(hm_dparams_final<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, f + l.pp, l.nblk_p, t, total, gpar, ldg);
     }
     if (gmf) {
-        hipLaunchKernelGGL(hm_dfeat_kernel<T>, dim3(cdiv(hw, HM_FB), HM_S, a.B), dim3(HM_FB), 0, s, a.mf, a.params, a.ldp, t, f + l.loc, f + l.dL,
+        hipLaunchKernelGGL(hm_dfeat_kernel<T>, dim3(cdiv(hw, CL_FB), HM_S, a.B), dim3(CL_FB), 0, s, a.mf, a.params, a.ldp, t, f + l.loc, f + l.dL,
                            hw, a.W, f + l.pf);
         const size_t per = (size_t)hw * 8, total = per * a.B;
         hipLaunchKernelGGL(hm_dfeat_final<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, f + l.pf, per, total, gmf);

@@ -62,12 +62,6 @@ bool mc_shape_ok(int B, int M, int C) { return B >= 1 && B <= 65535 && M >= 1 &&
 __device__ __forceinline__ float mc_exp(float x) { return expf(x); }
 __device__ __forceinline__ double mc_exp(double x) { return exp(x); }
 template <typename T>
-__device__ __forceinline__ T mc_wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <typename T>
 __device__ __forceinline__ T mc_wave_max(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -255,20 +249,8 @@ mc_lse_kernel(const T* __restrict__ S, const int* __restrict__ meta, int M, doub
     m = mc_wave_max(m);
     double sum = 0;
     for (int k = threadIdx.x; k < no; k += 64) sum += (double)mc_exp(p[k * step] - m);
-    sum = mc_wave_sum(sum);
+    sum = wave_sum(sum);
     if (threadIdx.x == 0) lse[((size_t)b * 2 + dir) * M + i] = (double)m + log(sum);
-}
-
-template <typename T>
-__device__ __forceinline__ T mc_block_sum(T v, T* sm) {      // MC_TB threads, summed in a fixed tree; the result in thread 0
-    v = mc_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T r = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < MC_TB / 64; ++w) r += sm[w];
-    __syncthreads();
-    return r;
 }
 
 template <typename T>
@@ -288,13 +270,13 @@ mc_loss_kernel(const T* __restrict__ S, const double* __restrict__ lse, const in
         const int r = row[i];
         if (r >= 0) ar += l0[i] - Sb[(size_t)i * M + r];
     }
-    ar = mc_block_sum(ar, sm);
+    ar = block_sum<MC_TB>(ar, sm);
     if (flags & 1) {
         for (int j = t; j < n1; j += MC_TB) {
             const int c = col[j];
             if (c >= 0) ac += l1[j] - Sb[(size_t)c * M + j];
         }
-        ac = mc_block_sum(ac, sm);
+        ac = block_sum<MC_TB>(ac, sm);
     }
     if (t == 0) {
         const double cr = ar / (double)meta[b * 4 + 2];                    // 0 / 0 = NaN: no labelled row

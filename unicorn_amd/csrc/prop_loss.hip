@@ -49,12 +49,6 @@ __device__ __forceinline__ PlVec<T, V> pl_load(const T* p) { return *reinterpret
 template <typename T, int V>
 __device__ __forceinline__ void pl_store(T* p, const PlVec<T, V>& x) { *reinterpret_cast<PlVec<T, V>*>(p) = x; }
 
-__device__ __forceinline__ double pl_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(PL_TB)
 pl_match_kernel(const float* __restrict__ targets, int M, int Kc, int sot, int* __restrict__ matched, int* __restrict__ num_matched) {
     __shared__ float s_id1[PL_MAXM];
@@ -241,9 +235,9 @@ pl_fwd_kernel(const T* __restrict__ pred, const T* __restrict__ gt, int H8, int 
         }
         if (by < H32 && bx < W32) p32[((size_t)slot * H32 + by) * W32 + bx] = (T)0.25 * ((x[1][1] + x[1][2]) + (x[2][1] + x[2][2]));
     }
-    si = pl_wave_sum(si);
-    sx = pl_wave_sum(sx);
-    st = pl_wave_sum(st);
+    si = wave_sum(si);
+    sx = wave_sum(sx);
+    st = wave_sum(st);
     if ((t & 63) == 0) { sm[t >> 6][0] = si; sm[t >> 6][1] = sx; sm[t >> 6][2] = st; }
     __syncthreads();
     if (t < 3) {
@@ -267,7 +261,7 @@ pl_final_kernel(const double* __restrict__ partial, int pitch, int nblk, int spa
         a[2] += p[2];
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] = pl_wave_sum(a[k]);
+    for (int k = 0; k < 3; ++k) a[k] = wave_sum(a[k]);
     if (lane == 0) {
         const bool live = !num_matched || g % Kc < num_matched[g / Kc];
         sums[(size_t)g * 3 + 0] = a[0];
