@@ -28,6 +28,72 @@ def test_library_exports_every_declared_symbol():
     assert lib.uni_version() == 1
 
 
+_C_KINDS = {"int": "int", "int32_t": "int", "float": "float", "double": "double", "size_t": "size_t", "void": "void"}
+
+
+def _declared_prototypes():
+    """{name: (return kind, [argument kinds])} of every uni_* declaration of include/unicorn_hip.h; kinds: ptr (uni_stream_t counts as one),
+    int (int / int32_t), float, double, size_t, void (return only).  An argument of any other type is a KeyError."""
+    src = open(os.path.join(ROOT, "include", "unicorn_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+
+    def kind(decl, named):
+        words = decl.replace("*", " * ").split()
+        if "*" in words or "uni_stream_t" in words:
+            return "ptr"
+        words = [w for w in words if w != "const"]
+        return _C_KINDS[words[0] if len(words) == (2 if named else 1) else " ".join(words)]
+
+    out = {}
+    for ret, name, args in re.findall(r"^([A-Za-z_][\w \*]*?)\b(uni_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
+        assert name not in out, "%s is declared twice" % name
+        args = [a.strip() for a in args.split(",")]
+        out[name] = (kind(ret, False), [] if args == ["void"] else [kind(a, True) for a in args])
+    return out
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    return {C.c_int: "int", C.c_float: "float", C.c_double: "double", C.c_size_t: "size_t"}[t]
+
+
+def test_prototypes_match_the_header():
+    """unicorn_amd/_lib.py PROTOS restates every declaration of include/unicorn_hip.h as ctypes types, and ctypes checks nothing against the
+    library: a prototype one argument short, or a float where the header says double, loads and runs.  Hold every entry to the header: the
+    number of arguments and the kind of each one (and of the result)."""
+    from unicorn_amd import _lib
+    decl = _declared_prototypes()
+    assert sorted(decl) == _declared_symbols() and len(decl) >= 103
+    assert set(decl) == set(_lib.PROTOS), set(decl) ^ set(_lib.PROTOS)
+    bad = {}
+    for name, (ret, args) in decl.items():
+        res, argtypes = _lib.PROTOS[name]
+        got = (_ctypes_kind(res), [_ctypes_kind(t) for t in argtypes])
+        if got != (ret, args):
+            bad[name] = "header %s(%s), PROTOS %s(%s)" % (ret, ", ".join(args), got[0], ", ".join(got[1]))
+    assert not bad, bad
+    for name in _lib.F64_TWINS:                     # the derived entries exist and are what the fp32 entry says
+        assert _lib.PROTOS[name + "_f64"] == _lib.PROTOS[name] and decl[name + "_f64"] == decl[name], name
+
+
+def test_ops_entry_resolves_both_precisions_of_a_pair():
+    """unicorn_amd.ops._entry: (base name, dtype) -> the bound function and the exported name; a dtype outside fp32 / fp64 raises."""
+    from unicorn_amd import _lib, ops
+    lib = _lib.lib()
+    for dtype, name in ((torch.float32, "uni_head_loss_fwd"), (torch.float64, "uni_head_loss_fwd_f64")):
+        fn, got = ops._entry("uni_head_loss_fwd", dtype)
+        assert got == name and fn is getattr(lib, name) and fn.argtypes == _lib.PROTOS[name][1]
+    assert ops._ws_factor(torch.float32) == 1 and ops._ws_factor(torch.float64) == 2
+    with pytest.raises(_lib.UnicornHipError, match="uni_head_loss_fwd: dtype torch.float16 unsupported"):
+        ops._entry("uni_head_loss_fwd", torch.float16)
+    with pytest.raises(_lib.UnicornHipError, match="^my own words$"):
+        ops._entry("uni_head_loss_fwd", torch.bfloat16, "my own words")
+
+
 def test_pack_weight_matches_numpy():
     from unicorn_amd import _lib
     lib = _lib.lib()

@@ -41,12 +41,8 @@ PROTOS = {
     "uni_pos_embed": (c_i, [C.c_void_p, c_i, c_i, c_f, C.c_void_p]),
     "uni_msda_fwd": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                            C.c_void_p]),
-    "uni_msda_fwd_f64": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                               C.c_void_p]),
     "uni_msda_bwd": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i,
                            c_i, c_i, C.c_void_p]),
-    "uni_msda_bwd_f64": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
-                               c_i, c_i, c_i, C.c_void_p]),
     "uni_corr_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i]),
     "uni_corr_softmax_pv": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_corr_workspace_bytes_batched": (C.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -73,9 +69,6 @@ PROTOS = {
     "uni_condinst_loss_fwd": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_condinst_loss_bwd": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, C.c_void_p, C.c_size_t,
                                     C.c_void_p]),
-    "uni_condinst_loss_fwd_f64": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "uni_condinst_loss_bwd_f64": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, C.c_void_p, C.c_size_t,
-                                        C.c_void_p]),
     "uni_simota_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i, c_i]),
     "uni_simota_assign": (c_i, [c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, C.c_void_p, C.c_size_t,
                                 C.c_void_p]),
@@ -84,35 +77,20 @@ PROTOS = {
                                 C.c_size_t, C.c_void_p]),
     "uni_head_loss_bwd": (c_i, [c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, C.c_double, c_f, c_i, c_f,
                                 C.c_void_p, C.c_size_t, C.c_void_p]),
-    "uni_head_loss_fwd_f64": (c_i, [c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, C.c_double, c_f,
-                                    C.c_void_p, C.c_size_t, C.c_void_p]),
-    "uni_head_loss_bwd_f64": (c_i, [c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, C.c_double, c_f, c_i,
-                                    c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_head_mask_loss_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "uni_head_mask_loss_fwd": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
     "uni_head_mask_loss_bwd": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f,
                                      c_i, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "uni_head_mask_loss_fwd_f64": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p,
-                                         C.c_size_t, C.c_void_p]),
-    "uni_head_mask_loss_bwd_f64": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f,
-                                         c_f, c_i, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_mot_corr_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i]),
     "uni_mot_corr_loss_fwd": (c_i, [c_f, C.POINTER(C.c_int64), c_f, C.POINTER(C.c_int64), c_f, c_i, c_i, c_i, c_i, c_i, C.c_float, c_i, c_f,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_mot_corr_loss_bwd": (c_i, [c_f, C.POINTER(C.c_int64), c_f, C.POINTER(C.c_int64), c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_float, c_i, c_f,
                                     C.POINTER(C.c_int64), c_f, C.POINTER(C.c_int64), C.c_void_p, C.c_size_t, C.c_void_p]),
-    "uni_mot_corr_loss_fwd_f64": (c_i, [c_f, C.POINTER(C.c_int64), c_f, C.POINTER(C.c_int64), c_f, c_i, c_i, c_i, c_i, c_i, C.c_float, c_i, c_f,
-                                        C.c_void_p, C.c_size_t, C.c_void_p]),
-    "uni_mot_corr_loss_bwd_f64": (c_i, [c_f, C.POINTER(C.c_int64), c_f, C.POINTER(C.c_int64), c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_float, c_i,
-                                        c_f, C.POINTER(C.c_int64), c_f, C.POINTER(C.c_int64), C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_prop_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i]),
     "uni_prop_labels": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, C.c_void_p]),
-    "uni_prop_labels_f64": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, C.c_void_p]),
     "uni_prop_dice_pyramid_fwd": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "uni_prop_dice_pyramid_fwd_f64": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uni_prop_dice_pyramid_bwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
-    "uni_prop_dice_pyramid_bwd_f64": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
     "uni_opt_chunk_elems": (c_i, []),
     "uni_opt_table_bytes": (C.c_size_t, [c_i, c_i]),
     "uni_opt_step": (c_i, [c_f, C.c_size_t, c_f, C.c_size_t, c_i, c_i, c_i, c_f, c_f, c_f, c_f, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -147,6 +125,13 @@ PROTOS = {
     "uni_cast_f32": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, C.c_void_p]),
     "uni_stem": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_f, C.c_void_p]),
 }
+# fp32 / fp64 operator pairs whose two entries take the same arguments (device pointers travel as void*): the `_f64` prototype is the fp32 one.
+# The two correlation twins above are not: the fp64 form has no precision and no workspace.
+F64_TWINS = ("uni_msda_fwd", "uni_msda_bwd", "uni_condinst_loss_fwd", "uni_condinst_loss_bwd", "uni_head_loss_fwd", "uni_head_loss_bwd",
+             "uni_head_mask_loss_fwd", "uni_head_mask_loss_bwd", "uni_mot_corr_loss_fwd", "uni_mot_corr_loss_bwd", "uni_prop_labels",
+             "uni_prop_dice_pyramid_fwd", "uni_prop_dice_pyramid_bwd")
+for _name in F64_TWINS:
+    PROTOS[_name + "_f64"] = PROTOS[_name]
 
 _lib = None
 BUILD_CHECK = None      # outcome of verify_manifest for the loaded library ("verified" / "no-sources" / "skipped")

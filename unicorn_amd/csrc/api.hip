@@ -38,6 +38,30 @@ static int post_launch() {
     if (e != hipSuccess) { uni_set_error("kernel launch failed: %s", hipGetErrorString(e)); return -2; }
     return 0;
 }
+// what uni_condinst_masks and uni_condinst_masks_u8 share: the workspace check and the argument struct up to `out`
+static int condinst_args(CondInstArgs& a, const char* what, const float* mask_feats, const float* up_masks, const float* params, int ldp,
+                         const float* inst_loc, const int32_t* inst_lvl, int n, int H8, int W8, int up_rate, int d_rate, void* workspace,
+                         size_t workspace_bytes) {
+    const size_t need = (size_t)n * H8 * W8 * (1 + up_rate * up_rate) * sizeof(float);
+    UNI_REQUIRE(workspace_bytes >= need, "%s: workspace %zu < %zu", what, workspace_bytes, need);
+    a.mask_feats = mask_feats; a.up_masks = up_masks; a.params = params; a.ldp = ldp; a.inst_loc = inst_loc; a.inst_lvl = inst_lvl;
+    a.n = n; a.H = H8; a.W = W8; a.r = up_rate; a.d_rate = d_rate;
+    a.logits_ws = reinterpret_cast<float*>(workspace);
+    a.coarse_ws = a.logits_ws + (size_t)n * H8 * W8;
+    return 0;
+}
+// conv geometry of the three GEMM entries (1x1 / s1 / p0 => plain GEMM); M must be its number of output pixels
+static int gemm_geometry(GemmArgs& g, const char* what, const void* A, int lda, const void* w_packed, int M, int N, int Hin, int Win, int Cin,
+                         int KH, int KW, int stride, int pad) {
+    g.A = reinterpret_cast<const bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const bf16*>(w_packed);
+    g.N = N; g.K = Cin * KH * KW; g.Kpad = cdiv(g.K, 64) * 64;
+    g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
+    const int Hout = (Hin + 2 * pad - KH) / stride + 1;
+    g.Wout = (Win + 2 * pad - KW) / stride + 1;
+    g.M = Hout * g.Wout;
+    UNI_REQUIRE(g.M == M, "%s: M=%d does not match conv geometry (%d)", what, M, g.M);
+    return 0;
+}
 #define API(expr) do { int _rc = (expr); if (_rc) return _rc; return post_launch(); } while (0)
 
 extern "C" {
@@ -219,32 +243,24 @@ int uni_pos_embed(uni_ctx* ctx, int h, int w, float* out_nhwc, uni_stream_t stre
     API(engine_pos_embed(ctx, h, w, out_nhwc, S(stream)));
 }
 
-int uni_msda_fwd(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const float* sampling_loc,
-                 const float* attn_weight, float* out, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {
-    UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && out, "msda: NULL argument");
-    API(launch_msda<float>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, out, N, S_, M, D, Lq, L, P, S(stream)));
-}
-int uni_msda_fwd_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const double* sampling_loc,
-                     const double* attn_weight, double* out, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {
-    UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && out, "msda: NULL argument");
-    API(launch_msda<double>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, out, N, S_, M, D, Lq, L, P, S(stream)));
-}
-int uni_msda_bwd(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const float* sampling_loc,
-                 const float* attn_weight, const float* grad_output, float* grad_value, float* grad_sampling_loc,
-                 float* grad_attn_weight, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {
-    UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && grad_output && grad_value &&
-                grad_sampling_loc && grad_attn_weight, "msda_bwd: NULL argument");
-    API(launch_msda_bwd<float>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
-                               grad_sampling_loc, grad_attn_weight, N, S_, M, D, Lq, L, P, S(stream)));
-}
-int uni_msda_bwd_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const double* sampling_loc,
-                     const double* attn_weight, const double* grad_output, double* grad_value, double* grad_sampling_loc,
-                     double* grad_attn_weight, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {
-    UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && grad_output && grad_value &&
-                grad_sampling_loc && grad_attn_weight, "msda_bwd: NULL argument");
-    API(launch_msda_bwd<double>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
-                                grad_sampling_loc, grad_attn_weight, N, S_, M, D, Lq, L, P, S(stream)));
-}
+// ---- fp32 / fp64 operator pairs: ONE definition each, expanded for (symbol suffix, element type) = (, float) and (_f64, double).  A body checks
+// for NULL, fills the unit's argument struct (kernels.h) and calls the templated launcher; everything else lives in the unit.
+#define UNI_PAIR(DEF) DEF(, float) DEF(_f64, double)
+#define DEF_MSDA(SFX, T)                                                                                                                 \
+    int uni_msda_fwd##SFX(const T* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const T* sampling_loc,        \
+                          const T* attn_weight, T* out, int N, int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {        \
+        UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && out, "msda: NULL argument");          \
+        API(launch_msda<T>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, out, N, S_, M, D, Lq, L, P, S(stream))); \
+    }                                                                                                                                    \
+    int uni_msda_bwd##SFX(const T* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const T* sampling_loc,        \
+                          const T* attn_weight, const T* grad_output, T* grad_value, T* grad_sampling_loc, T* grad_attn_weight, int N,   \
+                          int S_, int M, int D, int Lq, int L, int P, uni_stream_t stream) {                                             \
+        UNI_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && grad_output && grad_value &&          \
+                    grad_sampling_loc && grad_attn_weight, "msda_bwd: NULL argument");                                                   \
+        API(launch_msda_bwd<T>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value,             \
+                               grad_sampling_loc, grad_attn_weight, N, S_, M, D, Lq, L, P, S(stream)));                                  \
+    }
+UNI_PAIR(DEF_MSDA)
 size_t uni_corr_workspace_bytes(int R, int Q, int K) { return corr_workspace_bytes(R, Q, K); }
 int uni_corr_softmax_pv(const float* e_ref, const float* e_cur, const float* values, float* out, int R, int Q, int D, int K,
                         int precision, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
@@ -325,50 +341,31 @@ int uni_condinst_masks(const float* mask_feats, const float* up_masks, const flo
                        size_t workspace_bytes, uni_stream_t stream) {
     if (n == 0) return 0;
     UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && out && workspace, "condinst: NULL argument");
-    const size_t need = (size_t)n * H8 * W8 * (1 + up_rate * up_rate) * sizeof(float);
-    UNI_REQUIRE(workspace_bytes >= need, "condinst: workspace %zu < %zu", workspace_bytes, need);
     CondInstArgs a;
-    a.mask_feats = mask_feats; a.up_masks = up_masks; a.params = params; a.ldp = ldp; a.inst_loc = inst_loc; a.inst_lvl = inst_lvl;
-    a.n = n; a.H = H8; a.W = W8; a.r = up_rate; a.d_rate = d_rate;
-    a.logits_ws = reinterpret_cast<float*>(workspace);
-    a.coarse_ws = a.logits_ws + (size_t)n * H8 * W8;
+    if (int rc = condinst_args(a, "condinst", mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, n, H8, W8, up_rate, d_rate, workspace,
+                               workspace_bytes)) return rc;
     a.out = out;
     API(launch_condinst(a, S(stream)));
 }
 size_t uni_condinst_loss_workspace_bytes(int n, int H8, int W8, int up_rate) { return condinst_loss_workspace_bytes(n, H8, W8, up_rate); }
-int uni_condinst_loss_fwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const float* inst_loc,
-                          const int32_t* inst_lvl, const float* gt, int n, int H8, int W8, int up_rate, float* loss, float* sums,
-                          void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && loss && sums && workspace, "condinst_loss_fwd: NULL argument");
-    API(launch_condinst_loss_fwd(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, n, H8, W8, up_rate, loss, sums, workspace,
-                                 workspace_bytes, S(stream)));
-}
-int uni_condinst_loss_bwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const float* inst_loc,
-                          const int32_t* inst_lvl, const float* gt, const float* sums, const float* grad_loss, int n, int H8, int W8,
-                          int up_rate, float* grad_mask_feats, float* grad_up_masks, float* grad_params, void* workspace,
-                          size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && sums && grad_loss && workspace,
-                "condinst_loss_bwd: NULL argument");
-    API(launch_condinst_loss_bwd(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, sums, grad_loss, n, H8, W8, up_rate, grad_mask_feats,
-                                 grad_up_masks, grad_params, workspace, workspace_bytes, S(stream)));
-}
-int uni_condinst_loss_fwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const double* inst_loc,
-                              const int32_t* inst_lvl, const double* gt, int n, int H8, int W8, int up_rate, double* loss, double* sums,
-                              void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && loss && sums && workspace,
-                "condinst_loss_fwd_f64: NULL argument");
-    API(launch_condinst_loss_fwd_f64(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, n, H8, W8, up_rate, loss, sums, workspace,
-                                     workspace_bytes, S(stream)));
-}
-int uni_condinst_loss_bwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const double* inst_loc,
-                              const int32_t* inst_lvl, const double* gt, const double* sums, const double* grad_loss, int n, int H8, int W8,
-                              int up_rate, double* grad_mask_feats, double* grad_up_masks, double* grad_params, void* workspace,
-                              size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && sums && grad_loss && workspace,
-                "condinst_loss_bwd_f64: NULL argument");
-    API(launch_condinst_loss_bwd_f64(mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, sums, grad_loss, n, H8, W8, up_rate,
-                                     grad_mask_feats, grad_up_masks, grad_params, workspace, workspace_bytes, S(stream)));
-}
+#define DEF_CONDINST_LOSS(SFX, T)                                                                                                                \
+    int uni_condinst_loss_fwd##SFX(const T* mask_feats, const T* up_masks, const T* params, int ldp, const T* inst_loc, const int32_t* inst_lvl, \
+                                   const T* gt, int n, int H8, int W8, int up_rate, T* loss, T* sums, void* workspace, size_t workspace_bytes,   \
+                                   uni_stream_t stream) {                                                                                        \
+        UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && loss && sums && workspace,                                 \
+                    "condinst_loss_fwd" #SFX ": NULL argument");                                                                                 \
+        const ClArgs<T> a{mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, n, H8, W8, up_rate, workspace, workspace_bytes};            \
+        API(launch_condinst_loss_fwd<T>(a, loss, sums, S(stream)));                                                                              \
+    }                                                                                                                                            \
+    int uni_condinst_loss_bwd##SFX(const T* mask_feats, const T* up_masks, const T* params, int ldp, const T* inst_loc, const int32_t* inst_lvl, \
+                                   const T* gt, const T* sums, const T* grad_loss, int n, int H8, int W8, int up_rate, T* grad_mask_feats,       \
+                                   T* grad_up_masks, T* grad_params, void* workspace, size_t workspace_bytes, uni_stream_t stream) {             \
+        UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && gt && sums && grad_loss && workspace,                            \
+                    "condinst_loss_bwd" #SFX ": NULL argument");                                                                                 \
+        const ClArgs<T> a{mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, gt, n, H8, W8, up_rate, workspace, workspace_bytes};            \
+        API(launch_condinst_loss_bwd<T>(a, sums, grad_loss, grad_mask_feats, grad_up_masks, grad_params, S(stream)));                            \
+    }
+UNI_PAIR(DEF_CONDINST_LOSS)
 size_t uni_simota_workspace_bytes(int B, int A, int Gmax, int C) { return simota_workspace_bytes(B, A, Gmax, C); }
 int uni_simota_assign(const float* outputs, int ld_out, const float* labels, const int32_t* num_gt, int M, const float* x_shifts,
                       const float* y_shifts, const float* strides, int B, int A, int C, int img_h, int img_w, uint8_t* fg_mask,
@@ -384,67 +381,52 @@ static const int64_t mc_no_stride[4] = {0, 0, 0, 0};
 size_t uni_head_mask_loss_workspace_bytes(int B, int A, int H8, int W8, int up_rate, int capacity) {
     return head_mask_loss_workspace_bytes(B, A, H8, W8, up_rate, capacity);
 }
-int uni_head_mask_loss_fwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const int32_t* fpn_levels, const float* masks, int M,
-    const uint8_t* fg_mask, const int32_t* matched_gt, const float* x_shifts, const float* y_shifts, const float* strides, int B, int A, int H8, int W8,
-    int up_rate, int capacity, float* out, float* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides && workspace && out && sums, "head_mask_loss_fwd: NULL argument");
-    API(launch_head_mask_loss_fwd(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, out, sums, workspace, workspace_bytes, S(stream)));
-}
-int uni_head_mask_loss_bwd(const float* mask_feats, const float* up_masks, const float* params, int ldp, const int32_t* fpn_levels, const float* masks, int M,
-    const uint8_t* fg_mask, const int32_t* matched_gt, const float* x_shifts, const float* y_shifts, const float* strides, int B, int A, int H8, int W8,
-    int up_rate, int capacity, const float* sums, const float* grad_out, float* grad_mask_feats, float* grad_up_masks,
-    float* grad_params, int ld_grad, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides && workspace && sums && grad_out, "head_mask_loss_bwd: NULL argument");
-    API(launch_head_mask_loss_bwd(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, sums, grad_out, grad_mask_feats, grad_up_masks, grad_params, ld_grad, workspace,
-                                  workspace_bytes, S(stream)));
-}
-int uni_head_mask_loss_fwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const int32_t* fpn_levels, const double* masks, int M,
-    const uint8_t* fg_mask, const int32_t* matched_gt, const double* x_shifts, const double* y_shifts, const double* strides, int B, int A, int H8, int W8,
-    int up_rate, int capacity, double* out, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides && workspace && out && sums, "head_mask_loss_fwd_f64: NULL argument");
-    API(launch_head_mask_loss_fwd_f64(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, out, sums, workspace, workspace_bytes, S(stream)));
-}
-int uni_head_mask_loss_bwd_f64(const double* mask_feats, const double* up_masks, const double* params, int ldp, const int32_t* fpn_levels, const double* masks, int M,
-    const uint8_t* fg_mask, const int32_t* matched_gt, const double* x_shifts, const double* y_shifts, const double* strides, int B, int A, int H8, int W8,
-    int up_rate, int capacity, const double* sums, const double* grad_out, double* grad_mask_feats, double* grad_up_masks,
-    double* grad_params, int ld_grad, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides && workspace && sums && grad_out, "head_mask_loss_bwd_f64: NULL argument");
-    API(launch_head_mask_loss_bwd_f64(mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, up_rate, capacity, sums, grad_out, grad_mask_feats, grad_up_masks, grad_params, ld_grad, workspace,
-                                  workspace_bytes, S(stream)));
-}
+#define DEF_HEAD_MASK_LOSS(SFX, T)                                                                                                               \
+    int uni_head_mask_loss_fwd##SFX(const T* mask_feats, const T* up_masks, const T* params, int ldp, const int32_t* fpn_levels, const T* masks, \
+                                    int M, const uint8_t* fg_mask, const int32_t* matched_gt, const T* x_shifts, const T* y_shifts,              \
+                                    const T* strides, int B, int A, int H8, int W8, int up_rate, int capacity, T* out, T* sums, void* workspace, \
+                                    size_t workspace_bytes, uni_stream_t stream) {                                                               \
+        UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides &&       \
+                    workspace && out && sums, "head_mask_loss_fwd" #SFX ": NULL argument");                                                      \
+        const HMIn<T> a{mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, \
+                        up_rate, capacity};                                                                                                      \
+        API(launch_head_mask_loss_fwd<T>(a, out, sums, workspace, workspace_bytes, S(stream)));                                                  \
+    }                                                                                                                                            \
+    int uni_head_mask_loss_bwd##SFX(const T* mask_feats, const T* up_masks, const T* params, int ldp, const int32_t* fpn_levels, const T* masks, \
+                                    int M, const uint8_t* fg_mask, const int32_t* matched_gt, const T* x_shifts, const T* y_shifts,              \
+                                    const T* strides, int B, int A, int H8, int W8, int up_rate, int capacity, const T* sums, const T* grad_out, \
+                                    T* grad_mask_feats, T* grad_up_masks, T* grad_params, int ld_grad, void* workspace, size_t workspace_bytes,  \
+                                    uni_stream_t stream) {                                                                                       \
+        UNI_REQUIRE(mask_feats && up_masks && params && fpn_levels && masks && fg_mask && matched_gt && x_shifts && y_shifts && strides &&       \
+                    workspace && sums && grad_out, "head_mask_loss_bwd" #SFX ": NULL argument");                                                 \
+        const HMIn<T> a{mask_feats, up_masks, params, ldp, fpn_levels, masks, M, fg_mask, matched_gt, x_shifts, y_shifts, strides, B, A, H8, W8, \
+                        up_rate, capacity};                                                                                                      \
+        API(launch_head_mask_loss_bwd<T>(a, sums, grad_out, grad_mask_feats, grad_up_masks, grad_params, ld_grad, workspace, workspace_bytes,    \
+                                         S(stream)));                                                                                            \
+    }
+UNI_PAIR(DEF_HEAD_MASK_LOSS)
 size_t uni_prop_workspace_bytes(int B, int Kc, int Q) { return prop_workspace_bytes(B, Kc, Q); }
-int uni_prop_labels(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int mask_rate,
-                    int32_t* matched, int32_t* num_matched, float* gt0, float* gt1, uni_stream_t stream) {
-    UNI_REQUIRE(targets && matched && num_matched && gt0 && gt1, "prop_labels: NULL argument");
-    API(launch_prop_labels(targets, masks, mask_u8, B, M, Kc, sot, H8, W8, mask_rate, matched, num_matched, gt0, gt1, S(stream)));
-}
-int uni_prop_labels_f64(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int mask_rate,
-                        int32_t* matched, int32_t* num_matched, double* gt0, double* gt1, uni_stream_t stream) {
-    UNI_REQUIRE(targets && matched && num_matched && gt0 && gt1, "prop_labels_f64: NULL argument");
-    API(launch_prop_labels_f64(targets, masks, mask_u8, B, M, Kc, sot, H8, W8, mask_rate, matched, num_matched, gt0, gt1, S(stream)));
-}
-int uni_prop_dice_pyramid_fwd(const float* pred, const float* gt1, const int32_t* num_matched, int B, int Kc, int H8, int W8, float* p16, float* p32,
-                              float* loss, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(pred && gt1 && p16 && p32 && loss && sums && workspace, "prop_dice_pyramid_fwd: NULL argument");
-    API(launch_prop_dice_pyramid_fwd(pred, gt1, num_matched, B, Kc, H8, W8, p16, p32, loss, sums, workspace, workspace_bytes, S(stream)));
-}
-int uni_prop_dice_pyramid_fwd_f64(const double* pred, const double* gt1, const int32_t* num_matched, int B, int Kc, int H8, int W8, double* p16,
-                                  double* p32, double* loss, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(pred && gt1 && p16 && p32 && loss && sums && workspace, "prop_dice_pyramid_fwd_f64: NULL argument");
-    API(launch_prop_dice_pyramid_fwd_f64(pred, gt1, num_matched, B, Kc, H8, W8, p16, p32, loss, sums, workspace, workspace_bytes, S(stream)));
-}
-int uni_prop_dice_pyramid_bwd(const float* pred, const float* gt1, const int32_t* num_matched, const double* sums, const float* grad_p8,
-                              const float* grad_p16, const float* grad_p32, const float* grad_loss, int B, int Kc, int H8, int W8, float* grad_pred,
-                              uni_stream_t stream) {
-    UNI_REQUIRE(pred && gt1 && sums && grad_pred, "prop_dice_pyramid_bwd: NULL argument");
-    API(launch_prop_dice_pyramid_bwd(pred, gt1, num_matched, sums, grad_p8, grad_p16, grad_p32, grad_loss, B, Kc, H8, W8, grad_pred, S(stream)));
-}
-int uni_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const int32_t* num_matched, const double* sums, const double* grad_p8,
-                                  const double* grad_p16, const double* grad_p32, const double* grad_loss, int B, int Kc, int H8, int W8,
-                                  double* grad_pred, uni_stream_t stream) {
-    UNI_REQUIRE(pred && gt1 && sums && grad_pred, "prop_dice_pyramid_bwd_f64: NULL argument");
-    API(launch_prop_dice_pyramid_bwd_f64(pred, gt1, num_matched, sums, grad_p8, grad_p16, grad_p32, grad_loss, B, Kc, H8, W8, grad_pred, S(stream)));
-}
+#define DEF_PROP_LOSS(SFX, T)                                                                                                                    \
+    int uni_prop_labels##SFX(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int mask_rate, \
+                             int32_t* matched, int32_t* num_matched, T* gt0, T* gt1, uni_stream_t stream) {                                      \
+        UNI_REQUIRE(targets && matched && num_matched && gt0 && gt1, "prop_labels" #SFX ": NULL argument");                                      \
+        const PlLabelArgs a{targets, masks, mask_u8, B, M, Kc, sot, H8, W8, mask_rate, matched, num_matched};                                    \
+        API(launch_prop_labels<T>(a, gt0, gt1, S(stream)));                                                                                      \
+    }                                                                                                                                            \
+    int uni_prop_dice_pyramid_fwd##SFX(const T* pred, const T* gt1, const int32_t* num_matched, int B, int Kc, int H8, int W8, T* p16, T* p32,   \
+                                       T* loss, double* sums, void* workspace, size_t workspace_bytes, uni_stream_t stream) {                    \
+        UNI_REQUIRE(pred && gt1 && p16 && p32 && loss && sums && workspace, "prop_dice_pyramid_fwd" #SFX ": NULL argument");                     \
+        const PlDiceArgs<T> a{pred, gt1, num_matched, B, Kc, H8, W8};                                                                            \
+        API(launch_prop_dice_pyramid_fwd<T>(a, p16, p32, loss, sums, workspace, workspace_bytes, S(stream)));                                    \
+    }                                                                                                                                            \
+    int uni_prop_dice_pyramid_bwd##SFX(const T* pred, const T* gt1, const int32_t* num_matched, const double* sums, const T* grad_p8,            \
+                                       const T* grad_p16, const T* grad_p32, const T* grad_loss, int B, int Kc, int H8, int W8, T* grad_pred,    \
+                                       uni_stream_t stream) {                                                                                    \
+        UNI_REQUIRE(pred && gt1 && sums && grad_pred, "prop_dice_pyramid_bwd" #SFX ": NULL argument");                                           \
+        const PlDiceArgs<T> a{pred, gt1, num_matched, B, Kc, H8, W8};                                                                            \
+        API(launch_prop_dice_pyramid_bwd<T>(a, sums, grad_p8, grad_p16, grad_p32, grad_loss, grad_pred, S(stream)));                             \
+    }
+UNI_PAIR(DEF_PROP_LOSS)
 int uni_opt_chunk_elems(void) { return opt_chunk_elems(); }
 size_t uni_opt_table_bytes(int n_tensors, int total_chunks) { return opt_table_bytes(n_tensors, total_chunks); }
 int uni_opt_step(const void* table, size_t table_bytes, const void* block_map, size_t map_bytes, int n_tensors, int vec_chunks, int total_chunks,
@@ -455,79 +437,50 @@ int uni_opt_step(const void* table, size_t table_bytes, const void* block_map, s
                         beta2, eps, ema_decay, growth_factor, backoff_factor, growth_interval, S(stream)));
 }
 size_t uni_mot_corr_workspace_bytes(int B, int M, int C) { return mot_corr_workspace_bytes(B, M, C); }
-int uni_mot_corr_loss_fwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
-                          int B, int C, int H, int W, int M, float stride, int flags, float* loss, void* workspace, size_t workspace_bytes,
-                          uni_stream_t stream) {
-    UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && loss && workspace, "mot_corr_loss_fwd: NULL argument");
-    API(launch_mot_corr_fwd(embed_0, mc_stride(strides_0), embed_1, mc_stride(strides_1), targets, B, C, H, W, M, stride, flags, loss, workspace,
-                            workspace_bytes, S(stream)));
-}
-int uni_mot_corr_loss_bwd(const float* embed_0, const int64_t* strides_0, const float* embed_1, const int64_t* strides_1, const float* targets,
-                          const float* grad_loss, int B, int C, int H, int W, int M, float stride, int flags, float* grad_embed_0,
-                          const int64_t* grad_strides_0, float* grad_embed_1, const int64_t* grad_strides_1, void* workspace,
-                          size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && grad_loss && workspace && (!grad_embed_0 || grad_strides_0) &&
-                (!grad_embed_1 || grad_strides_1), "mot_corr_loss_bwd: NULL argument");
-    API(launch_mot_corr_bwd(embed_0, mc_stride(strides_0), embed_1, mc_stride(strides_1), targets, grad_loss, B, C, H, W, M, stride, flags,
-                            grad_embed_0, mc_stride(grad_embed_0 ? grad_strides_0 : mc_no_stride), grad_embed_1,
-                            mc_stride(grad_embed_1 ? grad_strides_1 : mc_no_stride), workspace, workspace_bytes, S(stream)));
-}
-int uni_mot_corr_loss_fwd_f64(const double* embed_0, const int64_t* strides_0, const double* embed_1, const int64_t* strides_1,
-                              const float* targets, int B, int C, int H, int W, int M, float stride, int flags, double* loss, void* workspace,
-                              size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && loss && workspace, "mot_corr_loss_fwd_f64: NULL argument");
-    API(launch_mot_corr_fwd_f64(embed_0, mc_stride(strides_0), embed_1, mc_stride(strides_1), targets, B, C, H, W, M, stride, flags, loss,
-                                workspace, workspace_bytes, S(stream)));
-}
-int uni_mot_corr_loss_bwd_f64(const double* embed_0, const int64_t* strides_0, const double* embed_1, const int64_t* strides_1,
-                              const float* targets, const double* grad_loss, int B, int C, int H, int W, int M, float stride, int flags,
-                              double* grad_embed_0, const int64_t* grad_strides_0, double* grad_embed_1, const int64_t* grad_strides_1,
-                              void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && grad_loss && workspace && (!grad_embed_0 || grad_strides_0) &&
-                (!grad_embed_1 || grad_strides_1), "mot_corr_loss_bwd_f64: NULL argument");
-    API(launch_mot_corr_bwd_f64(embed_0, mc_stride(strides_0), embed_1, mc_stride(strides_1), targets, grad_loss, B, C, H, W, M, stride, flags,
-                                grad_embed_0, mc_stride(grad_embed_0 ? grad_strides_0 : mc_no_stride), grad_embed_1,
-                                mc_stride(grad_embed_1 ? grad_strides_1 : mc_no_stride), workspace, workspace_bytes, S(stream)));
-}
+#define DEF_MOT_CORR_LOSS(SFX, T)                                                                                                                \
+    int uni_mot_corr_loss_fwd##SFX(const T* embed_0, const int64_t* strides_0, const T* embed_1, const int64_t* strides_1, const float* targets, \
+                                   int B, int C, int H, int W, int M, float stride, int flags, T* loss, void* workspace, size_t workspace_bytes, \
+                                   uni_stream_t stream) {                                                                                        \
+        UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && loss && workspace, "mot_corr_loss_fwd" #SFX ": NULL argument");   \
+        const McArgs a{embed_0, embed_1, mc_stride(strides_0), mc_stride(strides_1), targets, B, C, H, W, M, stride, flags, workspace,           \
+                       workspace_bytes};                                                                                                         \
+        API(launch_mot_corr_fwd<T>(a, loss, S(stream)));                                                                                         \
+    }                                                                                                                                            \
+    int uni_mot_corr_loss_bwd##SFX(const T* embed_0, const int64_t* strides_0, const T* embed_1, const int64_t* strides_1, const float* targets, \
+                                   const T* grad_loss, int B, int C, int H, int W, int M, float stride, int flags, T* grad_embed_0,              \
+                                   const int64_t* grad_strides_0, T* grad_embed_1, const int64_t* grad_strides_1, void* workspace,               \
+                                   size_t workspace_bytes, uni_stream_t stream) {                                                                \
+        UNI_REQUIRE(embed_0 && strides_0 && embed_1 && strides_1 && targets && grad_loss && workspace && (!grad_embed_0 || grad_strides_0) &&    \
+                    (!grad_embed_1 || grad_strides_1), "mot_corr_loss_bwd" #SFX ": NULL argument");                                              \
+        const McArgs a{embed_0, embed_1, mc_stride(strides_0), mc_stride(strides_1), targets, B, C, H, W, M, stride, flags, workspace,           \
+                       workspace_bytes};                                                                                                         \
+        API(launch_mot_corr_bwd<T>(a, grad_loss, grad_embed_0, mc_stride(grad_embed_0 ? grad_strides_0 : mc_no_stride), grad_embed_1,            \
+                                   mc_stride(grad_embed_1 ? grad_strides_1 : mc_no_stride), S(stream)));                                         \
+    }
+UNI_PAIR(DEF_MOT_CORR_LOSS)
 size_t uni_head_loss_workspace_bytes(int B, int A, int C) { return head_loss_workspace_bytes(B, A, C); }
-int uni_head_loss_fwd(const float* outputs, int ld_out, const float* origin_preds, int ld_org, const float* labels, int M, const uint8_t* fg_mask,
-                      const int32_t* matched_gt, const float* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const float* x_shifts,
-                      const float* y_shifts, const float* strides, int B, int A, int C, double reg_weight, float* out, void* workspace,
-                      size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts && strides &&
-                out && workspace, "head_loss_fwd: NULL argument");
-    API(launch_head_loss_fwd(outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, num_fg, num_gt, x_shifts,
-                             y_shifts, strides, B, A, C, reg_weight, out, workspace, workspace_bytes, S(stream)));
-}
-int uni_head_loss_bwd(const float* outputs, int ld_out, const float* origin_preds, int ld_org, const float* labels, int M, const uint8_t* fg_mask,
-                      const int32_t* matched_gt, const float* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const float* x_shifts,
-                      const float* y_shifts, const float* strides, const float* grad_out, int B, int A, int C, double reg_weight,
-                      float* grad_outputs, int ld_grad, float* grad_origin, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts && strides &&
-                grad_out && workspace, "head_loss_bwd: NULL argument");
-    API(launch_head_loss_bwd(outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, num_fg, num_gt, x_shifts,
-                             y_shifts, strides, grad_out, B, A, C, reg_weight, grad_outputs, ld_grad, grad_origin, workspace, workspace_bytes,
-                             S(stream)));
-}
-int uni_head_loss_fwd_f64(const double* outputs, int ld_out, const double* origin_preds, int ld_org, const double* labels, int M, const uint8_t* fg_mask,
-                      const int32_t* matched_gt, const double* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const double* x_shifts,
-                      const double* y_shifts, const double* strides, int B, int A, int C, double reg_weight, double* out, void* workspace,
-                      size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts && strides &&
-                out && workspace, "head_loss_fwd_f64: NULL argument");
-    API(launch_head_loss_fwd_f64(outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, num_fg, num_gt, x_shifts,
-                             y_shifts, strides, B, A, C, reg_weight, out, workspace, workspace_bytes, S(stream)));
-}
-int uni_head_loss_bwd_f64(const double* outputs, int ld_out, const double* origin_preds, int ld_org, const double* labels, int M, const uint8_t* fg_mask,
-                      const int32_t* matched_gt, const double* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const double* x_shifts,
-                      const double* y_shifts, const double* strides, const double* grad_out, int B, int A, int C, double reg_weight,
-                      double* grad_outputs, int ld_grad, double* grad_origin, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
-    UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts && strides &&
-                grad_out && workspace, "head_loss_bwd_f64: NULL argument");
-    API(launch_head_loss_bwd_f64(outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, num_fg, num_gt, x_shifts,
-                             y_shifts, strides, grad_out, B, A, C, reg_weight, grad_outputs, ld_grad, grad_origin, workspace, workspace_bytes,
-                             S(stream)));
-}
+#define DEF_HEAD_LOSS(SFX, T)                                                                                                                      \
+    int uni_head_loss_fwd##SFX(const T* outputs, int ld_out, const T* origin_preds, int ld_org, const T* labels, int M, const uint8_t* fg_mask,    \
+                               const int32_t* matched_gt, const T* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const T* x_shifts,   \
+                               const T* y_shifts, const T* strides, int B, int A, int C, double reg_weight, T* out, void* workspace,               \
+                               size_t workspace_bytes, uni_stream_t stream) {                                                                      \
+        UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts &&           \
+                    strides && out && workspace, "head_loss_fwd" #SFX ": NULL argument");                                                          \
+        const HlArgs<T> a{{outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, x_shifts, y_shifts, strides, A, C}, \
+                          num_fg, num_gt, B, reg_weight, workspace, workspace_bytes};                                                              \
+        API(launch_head_loss_fwd<T>(a, out, S(stream)));                                                                                           \
+    }                                                                                                                                              \
+    int uni_head_loss_bwd##SFX(const T* outputs, int ld_out, const T* origin_preds, int ld_org, const T* labels, int M, const uint8_t* fg_mask,    \
+                               const int32_t* matched_gt, const T* matched_iou, const int32_t* num_fg, const int32_t* num_gt, const T* x_shifts,   \
+                               const T* y_shifts, const T* strides, const T* grad_out, int B, int A, int C, double reg_weight, T* grad_outputs,    \
+                               int ld_grad, T* grad_origin, void* workspace, size_t workspace_bytes, uni_stream_t stream) {                        \
+        UNI_REQUIRE(outputs && (labels || M == 0) && fg_mask && matched_gt && matched_iou && num_fg && num_gt && x_shifts && y_shifts &&           \
+                    strides && grad_out && workspace, "head_loss_bwd" #SFX ": NULL argument");                                                     \
+        const HlArgs<T> a{{outputs, ld_out, origin_preds, ld_org, labels, M, fg_mask, matched_gt, matched_iou, x_shifts, y_shifts, strides, A, C}, \
+                          num_fg, num_gt, B, reg_weight, workspace, workspace_bytes};                                                              \
+        API(launch_head_loss_bwd<T>(a, grad_out, grad_outputs, ld_grad, grad_origin, S(stream)));                                                  \
+    }
+UNI_PAIR(DEF_HEAD_LOSS)
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {
@@ -548,14 +501,9 @@ int uni_condinst_masks_u8(const float* mask_feats, const float* up_masks, const 
                           float* out_prob, uint8_t* out_bin, void* workspace, size_t workspace_bytes, uni_stream_t stream) {
     if (n == 0) return 0;
     UNI_REQUIRE(mask_feats && up_masks && params && inst_loc && inst_lvl && (out_prob || out_bin) && workspace && r > 0, "condinst_u8: bad argument");
-    const size_t need = (size_t)n * H8 * W8 * (1 + up_rate * up_rate) * sizeof(float);
-    UNI_REQUIRE(workspace_bytes >= need, "condinst_u8: workspace %zu < %zu", workspace_bytes, need);
-    CondInstArgs a;
-    a.mask_feats = mask_feats; a.up_masks = up_masks; a.params = params; a.ldp = ldp; a.inst_loc = inst_loc; a.inst_lvl = inst_lvl;
-    a.n = n; a.H = H8; a.W = W8; a.r = up_rate; a.d_rate = d_rate;
-    a.logits_ws = reinterpret_cast<float*>(workspace);
-    a.coarse_ws = a.logits_ws + (size_t)n * H8 * W8;
-    a.out = nullptr;                                   // stop after the convex upsample: coarse_ws holds (n, r H8, r W8) sigmoid scores
+    CondInstArgs a;      // a.out stays NULL: stop after the convex upsample, coarse_ws holds (n, r H8, r W8) sigmoid scores
+    if (int rc = condinst_args(a, "condinst_u8", mask_feats, up_masks, params, ldp, inst_loc, inst_lvl, n, H8, W8, up_rate, d_rate, workspace,
+                               workspace_bytes)) return rc;
     int rc = launch_condinst(a, S(stream));
     if (rc) return rc;
     int ho, wo; float rs;
@@ -590,13 +538,7 @@ int uni_gemm_bf16(const uint16_t* A, int lda, const uint16_t* w_packed, int M, i
                   uint16_t* outB, int ldb, double* gn_stats, int cpg, int force_cfg, uni_stream_t stream) {
     UNI_REQUIRE(A && w_packed && (outF || outB), "gemm: NULL argument");
     GemmArgs g;
-    g.A = reinterpret_cast<const bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const bf16*>(w_packed);
-    g.N = N; g.K = Cin * KH * KW; g.Kpad = cdiv(g.K, 64) * 64;
-    g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-    const int Hout = (Hin + 2 * pad - KH) / stride + 1;
-    g.Wout = (Win + 2 * pad - KW) / stride + 1;
-    g.M = Hout * g.Wout;
-    UNI_REQUIRE(g.M == M, "gemm: M=%d does not match conv geometry (%d)", M, g.M);
+    if (int rc = gemm_geometry(g, "gemm", A, lda, w_packed, M, N, Hin, Win, Cin, KH, KW, stride, pad)) return rc;
     g.bias = bias; g.act = act; g.res = residual; g.ldr = ldr; g.outF = outF; g.ldf = ldf;
     g.outB = reinterpret_cast<bf16*>(outB); g.ldb = ldb; g.stats = gn_stats; g.cpg = cpg; g.force_cfg = force_cfg; g.dbg = force_cfg / 1000;
     API(launch_gemm(g, S(stream)));
@@ -608,13 +550,7 @@ int uni_gemm_ex(const void* A, int lda, const void* w_packed, float wscale, int 
     UNI_REQUIRE(fmt >= 0 && fmt <= 2 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && Cin > 0 && N > 0, "gemm_ex: fmt=%d / bad geometry", fmt);
     UNI_REQUIRE(act_col0 >= 0 && act_col0 <= N && force_cfg >= 0 && force_cfg < 1000, "gemm_ex: act_col0=%d force_cfg=%d (tile configuration only)", act_col0, force_cfg);
     GemmArgs g;
-    g.A = reinterpret_cast<const bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const bf16*>(w_packed);
-    g.N = N; g.K = Cin * KH * KW; g.Kpad = cdiv(g.K, 64) * 64;
-    g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-    const int Hout = (Hin + 2 * pad - KH) / stride + 1;
-    g.Wout = (Win + 2 * pad - KW) / stride + 1;
-    g.M = Hout * g.Wout;
-    UNI_REQUIRE(g.M == M, "gemm_ex: M=%d does not match conv geometry (%d)", M, g.M);
+    if (int rc = gemm_geometry(g, "gemm_ex", A, lda, w_packed, M, N, Hin, Win, Cin, KH, KW, stride, pad)) return rc;
     g.Mper = g.M;
     g.bias = bias; g.act = act; g.act_col0 = act_col0; g.res = residual; g.ldr = ldr; g.outF = outF; g.ldf = ldf;
     g.outB = reinterpret_cast<bf16*>(outB); g.ldb = ldb; g.stats = gn_stats; g.cpg = cpg; g.force_cfg = force_cfg; g.b32 = fmt;
@@ -635,13 +571,7 @@ int uni_gemm_h2(const void* A, int lda, const void* w_packed, float wscale, int 
                 void* outB, int ldb, double* gn_stats, int cpg, int force_cfg, uni_stream_t stream) {
     UNI_REQUIRE(A && w_packed && (outF || outB), "gemm_h2: NULL argument");
     GemmArgs g;
-    g.A = reinterpret_cast<const bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const bf16*>(w_packed);
-    g.N = N; g.K = Cin * KH * KW; g.Kpad = cdiv(g.K, 64) * 64;
-    g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-    const int Hout = (Hin + 2 * pad - KH) / stride + 1;
-    g.Wout = (Win + 2 * pad - KW) / stride + 1;
-    g.M = Hout * g.Wout;
-    UNI_REQUIRE(g.M == M, "gemm_h2: M=%d does not match conv geometry (%d)", M, g.M);
+    if (int rc = gemm_geometry(g, "gemm_h2", A, lda, w_packed, M, N, Hin, Win, Cin, KH, KW, stride, pad)) return rc;
     g.bias = bias; g.act = act; g.res = residual; g.ldr = ldr; g.outF = outF; g.ldf = ldf;
     g.outB = reinterpret_cast<bf16*>(outB); g.ldb = ldb; g.stats = gn_stats; g.cpg = cpg; g.force_cfg = force_cfg;
     // tests / tools: force_cfg = tile cfg (< 1000) + 1000 * ablation bits (0..255: gemm_epi.h `dbg & 128`, gemm.hip `& 64`, ...) + 1000000 * K ranges

@@ -181,55 +181,15 @@ CLLayout cl_layout(int n, int H, int W, int r) {
     return l;
 }
 
-int cl_check(const char* what, int n, int H, int W, int r, int ldp, const void* ws, size_t ws_bytes, size_t esize) {
-    UNI_REQUIRE(n > 0 && H > 0 && W > 0, "%s: empty problem n=%d H8=%d W8=%d", what, n, H, W);
-    UNI_REQUIRE(r >= 1 && r <= 16, "%s: up_rate %d unsupported (1..16)", what, r);
-    UNI_REQUIRE(ldp >= CL_NP, "%s: ldp %d < 169", what, ldp);
-    UNI_REQUIRE(n <= 65535, "%s: more than 65535 instances", what);
-    UNI_REQUIRE((size_t)H * W * r * r < (size_t)1 << 30, "%s: map too large", what);
-    const size_t need = cl_layout(n, H, W, r).total * esize;
-    UNI_REQUIRE(ws && ((uintptr_t)ws & 7) == 0 && ws_bytes >= need, "%s: workspace %zu < %zu bytes or misaligned", what, ws_bytes, need);
-    return 0;
-}
-
 template <typename T>
-int cl_fwd(const T* mf, const T* um, const T* params, int ldp, const T* loc, const int* lvl, const T* gt, int n, int H, int W, int r, T* loss,
-           T* sums, void* workspace, size_t ws_bytes, hipStream_t s) {
-    if (int rc = cl_check("condinst_loss_fwd", n, H, W, r, ldp, workspace, ws_bytes, sizeof(T))) return rc;
-    const CLLayout l = cl_layout(n, H, W, r);
-    T* ws = reinterpret_cast<T*>(workspace);
-    const int hw = H * W;
-    hipLaunchKernelGGL(cl_mlp_kernel<T>, dim3(cdiv(hw, 256), n), dim3(256), 0, s, mf, params, ldp, loc, lvl, hw, W, ws + l.logits);
-    hipLaunchKernelGGL(cl_dice_kernel<T>, dim3(l.nblk_d, cdiv(n, CL_IC)), dim3(256), 0, s, um, ws + l.logits, gt, ws + l.dice, n, H, W, r, l.PX,
-                       l.nblk_d);
-    hipLaunchKernelGGL(cl_dice_final<T>, dim3(n), dim3(256), 0, s, ws + l.dice, l.nblk_d, sums, loss);
-    return 0;
-}
-
-template <typename T>
-int cl_bwd(const T* mf, const T* um, const T* params, int ldp, const T* loc, const int* lvl, const T* gt, const T* sums, const T* gout, int n,
-           int H, int W, int r, T* gmf, T* gum, T* gpar, void* workspace, size_t ws_bytes, hipStream_t s) {
-    if (int rc = cl_check("condinst_loss_bwd", n, H, W, r, ldp, workspace, ws_bytes, sizeof(T))) return rc;
-    if (!gmf && !gum && !gpar) return 0;
-    const CLLayout l = cl_layout(n, H, W, r);
-    T* ws = reinterpret_cast<T*>(workspace);
-    const int hw = H * W, want_dl = (gmf || gpar) ? 1 : 0;
-    hipLaunchKernelGGL(cl_mlp_kernel<T>, dim3(cdiv(hw, 256), n), dim3(256), 0, s, mf, params, ldp, loc, lvl, hw, W, ws + l.logits);
-    for (int c0 = 0; c0 < n; c0 += CL_CH) {
-        const int cnt = n - c0 < CL_CH ? n - c0 : CL_CH;
-        hipLaunchKernelGGL(cl_du_kernel<T>, dim3(l.nblk_d), dim3(256), 0, s, um, ws + l.logits, gt, sums, gout, ws + l.A, gum, c0, cnt, H, W, r, l.PX,
-                           want_dl);
-        if (want_dl) hipLaunchKernelGGL(cl_gather_kernel<T>, dim3(cdiv(hw, 256), cnt), dim3(256), 0, s, ws + l.A, ws + l.dL, c0, H, W);
-    }
-    if (gpar) {
-        hipLaunchKernelGGL(cl_dparams_kernel<T>, dim3(l.nblk_p, n, 2), dim3(256), 0, s, mf, params, ldp, loc, lvl, ws + l.dL, hw, W, ws + l.pp, l.nblk_p);
-        hipLaunchKernelGGL(cl_dparams_final<T>, dim3(n), dim3(256), 0, s, ws + l.pp, l.nblk_p, gpar, ldp);
-    }
-    if (gmf) {
-        hipLaunchKernelGGL(cl_dfeat_kernel<T>, dim3(cdiv(hw, CL_FB), l.nchunk), dim3(CL_FB), 0, s, mf, params, ldp, loc, lvl, ws + l.dL, n, hw, W,
-                           ws + l.pf);
-        hipLaunchKernelGGL(cl_dfeat_final<T>, dim3(cdiv(hw * 8, 256)), dim3(256), 0, s, ws + l.pf, l.nchunk, hw, gmf);
-    }
+int cl_check(const char* what, const ClArgs<T>& a) {
+    UNI_REQUIRE(a.n > 0 && a.H > 0 && a.W > 0, "%s: empty problem n=%d H8=%d W8=%d", what, a.n, a.H, a.W);
+    UNI_REQUIRE(a.r >= 1 && a.r <= 16, "%s: up_rate %d unsupported (1..16)", what, a.r);
+    UNI_REQUIRE(a.ldp >= CL_NP, "%s: ldp %d < 169", what, a.ldp);
+    UNI_REQUIRE(a.n <= 65535, "%s: more than 65535 instances", what);
+    UNI_REQUIRE((size_t)a.H * a.W * a.r * a.r < (size_t)1 << 30, "%s: map too large", what);
+    const size_t need = cl_layout(a.n, a.H, a.W, a.r).total * sizeof(T);
+    UNI_REQUIRE(a.ws && ((uintptr_t)a.ws & 7) == 0 && a.ws_bytes >= need, "%s: workspace %zu < %zu bytes or misaligned", what, a.ws_bytes, need);
     return 0;
 }
 
@@ -240,22 +200,48 @@ size_t condinst_loss_workspace_bytes(int n, int H, int W, int r) {
     if ((size_t)H * W * r * r >= (size_t)1 << 30) return 0;          // the shapes cl_check refuses: H * W stays inside int below
     return cl_layout(n, H, W, r).total * sizeof(float);
 }
-int launch_condinst_loss_fwd(const float* mf, const float* um, const float* params, int ldp, const float* loc, const int* lvl, const float* gt,
-                             int n, int H, int W, int r, float* loss, float* sums, void* ws, size_t ws_bytes, hipStream_t s) {
-    return cl_fwd<float>(mf, um, params, ldp, loc, lvl, gt, n, H, W, r, loss, sums, ws, ws_bytes, s);
+
+template <typename T>
+int launch_condinst_loss_fwd(const ClArgs<T>& a, T* loss, T* sums, hipStream_t s) {
+    if (int rc = cl_check("condinst_loss_fwd", a)) return rc;
+    const CLLayout l = cl_layout(a.n, a.H, a.W, a.r);
+    T* ws = reinterpret_cast<T*>(a.ws);
+    const int hw = a.H * a.W;
+    hipLaunchKernelGGL(cl_mlp_kernel<T>, dim3(cdiv(hw, 256), a.n), dim3(256), 0, s, a.mf, a.params, a.ldp, a.loc, a.lvl, hw, a.W, ws + l.logits);
+    hipLaunchKernelGGL(cl_dice_kernel<T>, dim3(l.nblk_d, cdiv(a.n, CL_IC)), dim3(256), 0, s, a.um, ws + l.logits, a.gt, ws + l.dice, a.n, a.H, a.W,
+                       a.r, l.PX, l.nblk_d);
+    hipLaunchKernelGGL(cl_dice_final<T>, dim3(a.n), dim3(256), 0, s, ws + l.dice, l.nblk_d, sums, loss);
+    return 0;
 }
-int launch_condinst_loss_bwd(const float* mf, const float* um, const float* params, int ldp, const float* loc, const int* lvl, const float* gt,
-                             const float* sums, const float* gout, int n, int H, int W, int r, float* gmf, float* gum, float* gpar, void* ws,
-                             size_t ws_bytes, hipStream_t s) {
-    return cl_bwd<float>(mf, um, params, ldp, loc, lvl, gt, sums, gout, n, H, W, r, gmf, gum, gpar, ws, ws_bytes, s);
+
+template <typename T>
+int launch_condinst_loss_bwd(const ClArgs<T>& a, const T* sums, const T* gout, T* gmf, T* gum, T* gpar, hipStream_t s) {
+    if (int rc = cl_check("condinst_loss_bwd", a)) return rc;
+    if (!gmf && !gum && !gpar) return 0;
+    const CLLayout l = cl_layout(a.n, a.H, a.W, a.r);
+    T* ws = reinterpret_cast<T*>(a.ws);
+    const int n = a.n, hw = a.H * a.W, want_dl = (gmf || gpar) ? 1 : 0;
+    hipLaunchKernelGGL(cl_mlp_kernel<T>, dim3(cdiv(hw, 256), n), dim3(256), 0, s, a.mf, a.params, a.ldp, a.loc, a.lvl, hw, a.W, ws + l.logits);
+    for (int c0 = 0; c0 < n; c0 += CL_CH) {
+        const int cnt = n - c0 < CL_CH ? n - c0 : CL_CH;
+        hipLaunchKernelGGL(cl_du_kernel<T>, dim3(l.nblk_d), dim3(256), 0, s, a.um, ws + l.logits, a.gt, sums, gout, ws + l.A, gum, c0, cnt, a.H, a.W,
+                           a.r, l.PX, want_dl);
+        if (want_dl) hipLaunchKernelGGL(cl_gather_kernel<T>, dim3(cdiv(hw, 256), cnt), dim3(256), 0, s, ws + l.A, ws + l.dL, c0, a.H, a.W);
+    }
+    if (gpar) {
+        hipLaunchKernelGGL(cl_dparams_kernel<T>, dim3(l.nblk_p, n, 2), dim3(256), 0, s, a.mf, a.params, a.ldp, a.loc, a.lvl, ws + l.dL, hw, a.W,
+                           ws + l.pp, l.nblk_p);
+        hipLaunchKernelGGL(cl_dparams_final<T>, dim3(n), dim3(256), 0, s, ws + l.pp, l.nblk_p, gpar, a.ldp);
+    }
+    if (gmf) {
+        hipLaunchKernelGGL(cl_dfeat_kernel<T>, dim3(cdiv(hw, CL_FB), l.nchunk), dim3(CL_FB), 0, s, a.mf, a.params, a.ldp, a.loc, a.lvl, ws + l.dL, n,
+                           hw, a.W, ws + l.pf);
+        hipLaunchKernelGGL(cl_dfeat_final<T>, dim3(cdiv(hw * 8, 256)), dim3(256), 0, s, ws + l.pf, l.nchunk, hw, gmf);
+    }
+    return 0;
 }
-int launch_condinst_loss_fwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
-                                 const double* gt, int n, int H, int W, int r, double* loss, double* sums, void* ws, size_t ws_bytes,
-                                 hipStream_t s) {
-    return cl_fwd<double>(mf, um, params, ldp, loc, lvl, gt, n, H, W, r, loss, sums, ws, ws_bytes, s);
-}
-int launch_condinst_loss_bwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
-                                 const double* gt, const double* sums, const double* gout, int n, int H, int W, int r, double* gmf, double* gum,
-                                 double* gpar, void* ws, size_t ws_bytes, hipStream_t s) {
-    return cl_bwd<double>(mf, um, params, ldp, loc, lvl, gt, sums, gout, n, H, W, r, gmf, gum, gpar, ws, ws_bytes, s);
-}
+
+template int launch_condinst_loss_fwd<float>(const ClArgs<float>&, float*, float*, hipStream_t);
+template int launch_condinst_loss_fwd<double>(const ClArgs<double>&, double*, double*, hipStream_t);
+template int launch_condinst_loss_bwd<float>(const ClArgs<float>&, const float*, const float*, float*, float*, float*, hipStream_t);
+template int launch_condinst_loss_bwd<double>(const ClArgs<double>&, const double*, const double*, double*, double*, double*, hipStream_t);

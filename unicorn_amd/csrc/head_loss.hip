@@ -94,16 +94,6 @@ __device__ __forceinline__ void hl_l1_target(const HlBox& q, double s, double xs
 }
 
 template <typename T>
-struct HlIn {
-    const T* outputs; int ld;
-    const T* origin; int ldo;
-    const T* labels; int M;
-    const unsigned char* fg; const int* mg; const T* miou;
-    const T *xs, *ys, *st;
-    int A, C;
-};
-
-template <typename T>
 __global__ void __launch_bounds__(HL_TB)
 hl_fwd_kernel(HlIn<T> p, double* __restrict__ part) {
     __shared__ double sm[HL_TB / 64];
@@ -267,16 +257,6 @@ hl_bwd_kernel(HlIn<T> p, const T* __restrict__ gout, const long long* __restrict
 }
 
 template <typename T>
-struct HlArgs {
-    HlIn<T> in;
-    const int *num_fg, *num_gt;
-    int B;
-    double reg_weight;
-    void* ws;
-    size_t ws_bytes;
-};
-
-template <typename T>
 int hl_check(const HlArgs<T>& a, const char* what) {
     const HlIn<T>& p = a.in;
     UNI_REQUIRE(hl_shape_ok(a.B, p.A, p.M, p.C), "%s: shape B=%d A=%d M=%d C=%d outside 1 <= B <= 65535, 1 <= A < 2^24, 0 <= M <= 1024, 1 <= C <= 256",
@@ -289,8 +269,15 @@ int hl_check(const HlArgs<T>& a, const char* what) {
     return 0;
 }
 
+}  // namespace
+
+size_t head_loss_workspace_bytes(int B, int A, int C) {
+    if (!hl_shape_ok(B, A, 0, C)) return 0;
+    return hl_ws_bytes(B, A);
+}
+
 template <typename T>
-int hl_fwd(const HlArgs<T>& a, T* out, hipStream_t s) {
+int launch_head_loss_fwd(const HlArgs<T>& a, T* out, hipStream_t s) {
     if (int rc = hl_check<T>(a, "head_loss_fwd")) return rc;
     const int ax = cdiv(a.in.A, HL_TB);
     double* part = reinterpret_cast<double*>(a.ws);
@@ -300,7 +287,7 @@ int hl_fwd(const HlArgs<T>& a, T* out, hipStream_t s) {
 }
 
 template <typename T>
-int hl_bwd(const HlArgs<T>& a, const T* gout, T* g_out, int ldg, T* g_org, hipStream_t s) {
+int launch_head_loss_bwd(const HlArgs<T>& a, const T* gout, T* g_out, int ldg, T* g_org, hipStream_t s) {
     if (int rc = hl_check<T>(a, "head_loss_bwd")) return rc;
     UNI_REQUIRE(!g_out || ldg >= 5 + a.in.C, "head_loss_bwd: ld_grad %d < 5 + C = %d", ldg, 5 + a.in.C);
     UNI_REQUIRE(!g_org || a.in.origin, "head_loss_bwd: grad_origin without origin_preds");
@@ -311,35 +298,7 @@ int hl_bwd(const HlArgs<T>& a, const T* gout, T* g_out, int ldg, T* g_org, hipSt
     return 0;
 }
 
-}  // namespace
-
-size_t head_loss_workspace_bytes(int B, int A, int C) {
-    if (!hl_shape_ok(B, A, 0, C)) return 0;
-    return hl_ws_bytes(B, A);
-}
-
-#define HL_ARGS(T)                                                                                                                        \
-    HlArgs<T> { HlIn<T>{outputs, ld, origin, ldo, labels, M, fg, mg, miou, xs, ys, st, A, C}, num_fg, num_gt, B, reg_weight, ws, ws_bytes }
-
-int launch_head_loss_fwd(const float* outputs, int ld, const float* origin, int ldo, const float* labels, int M, const unsigned char* fg,
-                         const int* mg, const float* miou, const int* num_fg, const int* num_gt, const float* xs, const float* ys,
-                         const float* st, int B, int A, int C, double reg_weight, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
-    return hl_fwd<float>(HL_ARGS(float), out, s);
-}
-int launch_head_loss_bwd(const float* outputs, int ld, const float* origin, int ldo, const float* labels, int M, const unsigned char* fg,
-                         const int* mg, const float* miou, const int* num_fg, const int* num_gt, const float* xs, const float* ys,
-                         const float* st, const float* gout, int B, int A, int C, double reg_weight, float* g_out, int ldg, float* g_org,
-                         void* ws, size_t ws_bytes, hipStream_t s) {
-    return hl_bwd<float>(HL_ARGS(float), gout, g_out, ldg, g_org, s);
-}
-int launch_head_loss_fwd_f64(const double* outputs, int ld, const double* origin, int ldo, const double* labels, int M, const unsigned char* fg,
-                             const int* mg, const double* miou, const int* num_fg, const int* num_gt, const double* xs, const double* ys,
-                             const double* st, int B, int A, int C, double reg_weight, double* out, void* ws, size_t ws_bytes, hipStream_t s) {
-    return hl_fwd<double>(HL_ARGS(double), out, s);
-}
-int launch_head_loss_bwd_f64(const double* outputs, int ld, const double* origin, int ldo, const double* labels, int M, const unsigned char* fg,
-                             const int* mg, const double* miou, const int* num_fg, const int* num_gt, const double* xs, const double* ys,
-                             const double* st, const double* gout, int B, int A, int C, double reg_weight, double* g_out, int ldg,
-                             double* g_org, void* ws, size_t ws_bytes, hipStream_t s) {
-    return hl_bwd<double>(HL_ARGS(double), gout, g_out, ldg, g_org, s);
-}
+template int launch_head_loss_fwd<float>(const HlArgs<float>&, float*, hipStream_t);
+template int launch_head_loss_fwd<double>(const HlArgs<double>&, double*, hipStream_t);
+template int launch_head_loss_bwd<float>(const HlArgs<float>&, const float*, float*, int, float*, hipStream_t);
+template int launch_head_loss_bwd<double>(const HlArgs<double>&, const double*, double*, int, double*, hipStream_t);

@@ -401,19 +401,6 @@ HMTable hm_table(const HMLayout& l, void* ws) {
     return HMTable{p + l.hdr, p + l.cnt, p + l.off, p + l.row, p + l.img, p + l.gt, p + l.lvl, p + l.slot_of};
 }
 
-template <typename T>
-struct HMIn {
-    const T *mf, *um, *params;
-    int ldp;
-    const int* lvl;
-    const T* masks;
-    int M;
-    const unsigned char* fg;
-    const int* mg;
-    const T *xs, *ys, *st;
-    int B, A, H, W, r, cap;
-};
-
 // the two launches both directions start with: the table and the coarse logits
 template <typename T>
 void hm_prepare(const HMIn<T>& a, const HMLayout& l, const HMTable& t, T* f, hipStream_t s) {
@@ -422,8 +409,16 @@ void hm_prepare(const HMIn<T>& a, const HMLayout& l, const HMTable& t, T* f, hip
     hipLaunchKernelGGL(hm_mlp_kernel<T>, dim3(cdiv(hw, 256), gs), dim3(256), 0, s, a.mf, a.params, a.ldp, t, f + l.loc, hw, a.W, f + l.logits);
 }
 
+}  // namespace
+
+size_t head_mask_loss_workspace_bytes(int B, int A, int H, int W, int r, int cap) {
+    if (!hm_shape_ok(B, A, H, W, r, cap)) return 0;
+    const HMLayout l = hm_layout(B, A, H, W, r, cap);
+    return l.fbase + l.ftotal * sizeof(float);
+}
+
 template <typename T>
-int hm_fwd(const HMIn<T>& a, T* out, T* sums, void* workspace, size_t ws_bytes, hipStream_t s) {
+int launch_head_mask_loss_fwd(const HMIn<T>& a, T* out, T* sums, void* workspace, size_t ws_bytes, hipStream_t s) {
     if (int rc = hm_check("head_mask_loss_fwd", a.B, a.A, a.M, a.H, a.W, a.r, a.cap, a.ldp, workspace, ws_bytes, sizeof(T))) return rc;
     const HMLayout l = hm_layout(a.B, a.A, a.H, a.W, a.r, a.cap);
     const HMTable t = hm_table(l, workspace);
@@ -437,7 +432,8 @@ int hm_fwd(const HMIn<T>& a, T* out, T* sums, void* workspace, size_t ws_bytes, 
 }
 
 template <typename T>
-int hm_bwd(const HMIn<T>& a, const T* sums, const T* gout, T* gmf, T* gum, T* gpar, int ldg, void* workspace, size_t ws_bytes, hipStream_t s) {
+int launch_head_mask_loss_bwd(const HMIn<T>& a, const T* sums, const T* gout, T* gmf, T* gum, T* gpar, int ldg, void* workspace,
+                              size_t ws_bytes, hipStream_t s) {
     if (int rc = hm_check("head_mask_loss_bwd", a.B, a.A, a.M, a.H, a.W, a.r, a.cap, a.ldp, workspace, ws_bytes, sizeof(T))) return rc;
     UNI_REQUIRE(!gpar || ldg >= CL_NP, "head_mask_loss_bwd: ld_grad %d < 169", ldg);
     if (!gmf && !gum && !gpar) return 0;
@@ -467,28 +463,8 @@ int hm_bwd(const HMIn<T>& a, const T* sums, const T* gout, T* gmf, T* gum, T* gp
     return 0;
 }
 
-}  // namespace
-
-size_t head_mask_loss_workspace_bytes(int B, int A, int H, int W, int r, int cap) {
-    if (!hm_shape_ok(B, A, H, W, r, cap)) return 0;
-    const HMLayout l = hm_layout(B, A, H, W, r, cap);
-    return l.fbase + l.ftotal * sizeof(float);
-}
-#define HM_ARGS(T)                                                                                                                           \
-    const T *mf, const T *um, const T *params, int ldp, const int *lvl, const T *masks, int M, const unsigned char *fg, const int *mg,       \
-        const T *xs, const T *ys, const T *st, int B, int A, int H, int W, int r, int cap
-#define HM_IN(T) HMIn<T>{mf, um, params, ldp, lvl, masks, M, fg, mg, xs, ys, st, B, A, H, W, r, cap}
-int launch_head_mask_loss_fwd(HM_ARGS(float), float* out, float* sums, void* ws, size_t ws_bytes, hipStream_t s) {
-    return hm_fwd<float>(HM_IN(float), out, sums, ws, ws_bytes, s);
-}
-int launch_head_mask_loss_bwd(HM_ARGS(float), const float* sums, const float* gout, float* gmf, float* gum, float* gpar, int ldg, void* ws,
-                              size_t ws_bytes, hipStream_t s) {
-    return hm_bwd<float>(HM_IN(float), sums, gout, gmf, gum, gpar, ldg, ws, ws_bytes, s);
-}
-int launch_head_mask_loss_fwd_f64(HM_ARGS(double), double* out, double* sums, void* ws, size_t ws_bytes, hipStream_t s) {
-    return hm_fwd<double>(HM_IN(double), out, sums, ws, ws_bytes, s);
-}
-int launch_head_mask_loss_bwd_f64(HM_ARGS(double), const double* sums, const double* gout, double* gmf, double* gum, double* gpar, int ldg,
-                                  void* ws, size_t ws_bytes, hipStream_t s) {
-    return hm_bwd<double>(HM_IN(double), sums, gout, gmf, gum, gpar, ldg, ws, ws_bytes, s);
-}
+template int launch_head_mask_loss_fwd<float>(const HMIn<float>&, float*, float*, void*, size_t, hipStream_t);
+template int launch_head_mask_loss_fwd<double>(const HMIn<double>&, double*, double*, void*, size_t, hipStream_t);
+template int launch_head_mask_loss_bwd<float>(const HMIn<float>&, const float*, const float*, float*, float*, float*, int, void*, size_t, hipStream_t);
+template int launch_head_mask_loss_bwd<double>(const HMIn<double>&, const double*, const double*, double*, double*, double*, int, void*, size_t,
+                                               hipStream_t);

@@ -208,17 +208,17 @@ int launch_label_map_s8(const float* box_xyxy, float* out, int H, int W, hipStre
 // sum g^2).  The backward writes gmf [H][W][8], gum [H][W][9 r r], gpar [n][ldp] (169 columns); each may be NULL (not computed).
 // Workspace: condinst_loss_workspace_bytes for fp32, twice that for fp64; scratch between calls (the backward recomputes the logits).
 size_t condinst_loss_workspace_bytes(int n, int H, int W, int r);
-int launch_condinst_loss_fwd(const float* mf, const float* um, const float* params, int ldp, const float* loc, const int* lvl, const float* gt,
-                             int n, int H, int W, int r, float* loss, float* sums, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_condinst_loss_bwd(const float* mf, const float* um, const float* params, int ldp, const float* loc, const int* lvl, const float* gt,
-                             const float* sums, const float* gout, int n, int H, int W, int r, float* gmf, float* gum, float* gpar, void* ws,
-                             size_t ws_bytes, hipStream_t s);
-int launch_condinst_loss_fwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
-                                 const double* gt, int n, int H, int W, int r, double* loss, double* sums, void* ws, size_t ws_bytes,
-                                 hipStream_t s);
-int launch_condinst_loss_bwd_f64(const double* mf, const double* um, const double* params, int ldp, const double* loc, const int* lvl,
-                                 const double* gt, const double* sums, const double* gout, int n, int H, int W, int r, double* gmf, double* gum,
-                                 double* gpar, void* ws, size_t ws_bytes, hipStream_t s);
+template <typename T>
+struct ClArgs {
+    const T *mf, *um, *params; int ldp;
+    const T* loc; const int* lvl; const T* gt;
+    int n, H, W, r;
+    void* ws; size_t ws_bytes;
+};
+template <typename T>
+int launch_condinst_loss_fwd(const ClArgs<T>& a, T* loss, T* sums, hipStream_t s);
+template <typename T>
+int launch_condinst_loss_bwd(const ClArgs<T>& a, const T* sums, const T* gout, T* gmf, T* gum, T* gpar, hipStream_t s);
 // simota.hip: SimOTA label assignment of the head loss (unicorn_head_mask.py:754-983) for a batch, four launches, no host read-back.
 // outputs [B][A][ld >= 5 + C] (cx, cy, w, h, obj, cls logits), labels [B][M][5] (class, cx, cy, w, h), num_gt [B] device,
 // xs / ys / st [A] -> fg_mask [B][A], matched_gt [B][A] (-1 = background), matched_iou [B][A], num_fg [B], all completely written.
@@ -232,16 +232,20 @@ int launch_simota_assign(const float* outputs, int ld, const float* labels, cons
 // that for fp64; scratch between the calls (the backward recomputes).  flags: 1 = bidirect, 2 = grid_sample.
 struct McStride { long long b, c, y, x; };      // element strides of a (B, C, H, W) map
 size_t mot_corr_workspace_bytes(int B, int M, int C);
-int launch_mot_corr_fwd(const float* e0, McStride s0, const float* e1, McStride s1, const float* targets, int B, int C, int H, int W, int M,
-                        float stride, int flags, float* loss, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_mot_corr_bwd(const float* e0, McStride s0, const float* e1, McStride s1, const float* targets, const float* gout, int B, int C, int H,
-                        int W, int M, float stride, int flags, float* g0, McStride gs0, float* g1, McStride gs1, void* ws, size_t ws_bytes,
-                        hipStream_t s);
-int launch_mot_corr_fwd_f64(const double* e0, McStride s0, const double* e1, McStride s1, const float* targets, int B, int C, int H, int W, int M,
-                            float stride, int flags, double* loss, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_mot_corr_bwd_f64(const double* e0, McStride s0, const double* e1, McStride s1, const float* targets, const double* gout, int B, int C,
-                            int H, int W, int M, float stride, int flags, double* g0, McStride gs0, double* g1, McStride gs1, void* ws,
-                            size_t ws_bytes, hipStream_t s);
+struct McArgs {                                 // e0 / e1 hold T (the launcher's type)
+    const void *e0, *e1;
+    McStride s0, s1;
+    const float* targets;
+    int B, C, H, W, M;
+    float stride;
+    int flags;
+    void* ws;
+    size_t ws_bytes;
+};
+template <typename T>
+int launch_mot_corr_fwd(const McArgs& a, T* loss, hipStream_t s);
+template <typename T>
+int launch_mot_corr_bwd(const McArgs& a, const T* gout, T* g0, McStride gs0, T* g1, McStride gs1, hipStream_t s);
 // prop_loss.hip: what stands around the label propagation in the SOT / VOS training losses (unicorn.py:315-390), fp32 and fp64, no host read.
 // launch_prop_labels: targets [B][2][M][6] fp32 (+ masks [B][2][M][r H8][r W8] fp32 / uint8, or NULL: boxes) -> matched [B][Kc][2],
 // num_matched [B], gt0 / gt1 [B][Kc][H8 W8], all completely written; sot: one slot (0, 0) per sample.  launch_prop_dice_pyramid_fwd: pred, gt1
@@ -249,19 +253,23 @@ int launch_mot_corr_bwd_f64(const double* e0, McStride s0, const double* e1, McS
 // (I, X2, T2).  _bwd: g_pred [B][Kc][H8][W8] completely written from the upstream gradients (each may be NULL).  Workspace (forward only):
 // prop_workspace_bytes in both precisions.
 size_t prop_workspace_bytes(int B, int Kc, int Q);
-int launch_prop_labels(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int r, int* matched,
-                       int* num_matched, float* gt0, float* gt1, hipStream_t s);
-int launch_prop_labels_f64(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int r, int* matched,
-                           int* num_matched, double* gt0, double* gt1, hipStream_t s);
-int launch_prop_dice_pyramid_fwd(const float* pred, const float* gt1, const int* num_matched, int B, int Kc, int H8, int W8, float* p16, float* p32,
-                                 float* loss, double* sums, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_prop_dice_pyramid_fwd_f64(const double* pred, const double* gt1, const int* num_matched, int B, int Kc, int H8, int W8, double* p16,
-                                     double* p32, double* loss, double* sums, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_prop_dice_pyramid_bwd(const float* pred, const float* gt1, const int* num_matched, const double* sums, const float* g8, const float* g16,
-                                 const float* g32, const float* gl, int B, int Kc, int H8, int W8, float* gpred, hipStream_t s);
-int launch_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const int* num_matched, const double* sums, const double* g8,
-                                     const double* g16, const double* g32, const double* gl, int B, int Kc, int H8, int W8, double* gpred,
-                                     hipStream_t s);
+struct PlLabelArgs {
+    const float* targets; const void* masks;
+    int mask_u8, B, M, Kc, sot, H8, W8, r;
+    int *matched, *num_matched;
+};
+template <typename T>
+struct PlDiceArgs {
+    const T *pred, *gt1; const int* num_matched;
+    int B, Kc, H8, W8;
+};
+template <typename T>
+int launch_prop_labels(const PlLabelArgs& a, T* gt0, T* gt1, hipStream_t s);
+template <typename T>
+int launch_prop_dice_pyramid_fwd(const PlDiceArgs<T>& a, T* p16, T* p32, T* loss, double* sums, void* ws, size_t ws_bytes, hipStream_t s);
+template <typename T>
+int launch_prop_dice_pyramid_bwd(const PlDiceArgs<T>& a, const double* sums, const T* g8, const T* g16, const T* g32, const T* gl, T* gpred,
+                                 hipStream_t s);
 // opt_step.hip: GradScaler.step + torch.optim.AdamW + GradScaler.update + ModelEMA.update (trainer.py:260-275, utils/ema.py:50-63) over a list of
 // fp32 tensors through a tensor table and a block map in device memory (layouts: include/unicorn_hip.h), at most three launches, no host read.
 int opt_chunk_elems();
@@ -275,20 +283,28 @@ int launch_opt_step(const void* table, size_t table_bytes, const void* block_map
 // out[5] = reg_weight x iou, obj, cls, l1 losses and max(sum num_fg, 1) / max(sum num_gt, 1); the backward writes g_out [B][A][ldg >= 5 + C]
 // (columns 0 .. 4 + C) and g_org [B][A][4] completely (NULL: not computed).  Workspace: head_loss_workspace_bytes in both precisions.
 size_t head_loss_workspace_bytes(int B, int A, int C);
-int launch_head_loss_fwd(const float* outputs, int ld, const float* origin, int ldo, const float* labels, int M, const unsigned char* fg,
-                         const int* mg, const float* miou, const int* num_fg, const int* num_gt, const float* xs, const float* ys,
-                         const float* st, int B, int A, int C, double reg_weight, float* out, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_head_loss_bwd(const float* outputs, int ld, const float* origin, int ldo, const float* labels, int M, const unsigned char* fg,
-                         const int* mg, const float* miou, const int* num_fg, const int* num_gt, const float* xs, const float* ys,
-                         const float* st, const float* gout, int B, int A, int C, double reg_weight, float* g_out, int ldg, float* g_org,
-                         void* ws, size_t ws_bytes, hipStream_t s);
-int launch_head_loss_fwd_f64(const double* outputs, int ld, const double* origin, int ldo, const double* labels, int M, const unsigned char* fg,
-                             const int* mg, const double* miou, const int* num_fg, const int* num_gt, const double* xs, const double* ys,
-                             const double* st, int B, int A, int C, double reg_weight, double* out, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_head_loss_bwd_f64(const double* outputs, int ld, const double* origin, int ldo, const double* labels, int M, const unsigned char* fg,
-                             const int* mg, const double* miou, const int* num_fg, const int* num_gt, const double* xs, const double* ys,
-                             const double* st, const double* gout, int B, int A, int C, double reg_weight, double* g_out, int ldg,
-                             double* g_org, void* ws, size_t ws_bytes, hipStream_t s);
+template <typename T>
+struct HlIn {                                   // passed by value to the kernels
+    const T* outputs; int ld;
+    const T* origin; int ldo;
+    const T* labels; int M;
+    const unsigned char* fg; const int* mg; const T* miou;
+    const T *xs, *ys, *st;
+    int A, C;
+};
+template <typename T>
+struct HlArgs {
+    HlIn<T> in;
+    const int *num_fg, *num_gt;
+    int B;
+    double reg_weight;
+    void* ws;
+    size_t ws_bytes;
+};
+template <typename T>
+int launch_head_loss_fwd(const HlArgs<T>& a, T* out, hipStream_t s);
+template <typename T>
+int launch_head_loss_bwd(const HlArgs<T>& a, const T* gout, T* g_out, int ldg, T* g_org, hipStream_t s);
 // head_mask_loss.hip: the CondInst mask loss of get_losses (unicorn_head_mask.py:568-569, :675-694, :731-732) for a batch from the device-side
 // results of launch_simota_assign, forward + recomputing backward, fp32 and fp64, 5 launches forward and at most 22 backward, no host read-back.
 // mf [B][H][W][8], um [B][H][W][9 r r], params [B][A][ldp >= 169], lvl [B][A], masks [B][M][rH][rW] (read in place through mg), fg / mg [B][A],
@@ -296,20 +312,23 @@ int launch_head_loss_bwd_f64(const double* outputs, int ld, const double* origin
 // gum [B][H][W][9 r r], gpar [B][A][ldg >= 169] (169 columns) completely; each may be NULL.  More foreground anchors than cap: NaN losses, zero
 // gradients.  Workspace: head_mask_loss_workspace_bytes for fp32, twice that for fp64; scratch between calls.
 size_t head_mask_loss_workspace_bytes(int B, int A, int H, int W, int r, int cap);
-int launch_head_mask_loss_fwd(const float* mf, const float* um, const float* params, int ldp, const int* lvl, const float* masks, int M,
-                              const unsigned char* fg, const int* mg, const float* xs, const float* ys, const float* st, int B, int A, int H,
-                              int W, int r, int cap, float* out, float* sums, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_head_mask_loss_bwd(const float* mf, const float* um, const float* params, int ldp, const int* lvl, const float* masks, int M,
-                              const unsigned char* fg, const int* mg, const float* xs, const float* ys, const float* st, int B, int A, int H,
-                              int W, int r, int cap, const float* sums, const float* gout, float* gmf, float* gum, float* gpar, int ldg,
-                              void* ws, size_t ws_bytes, hipStream_t s);
-int launch_head_mask_loss_fwd_f64(const double* mf, const double* um, const double* params, int ldp, const int* lvl, const double* masks, int M,
-                                  const unsigned char* fg, const int* mg, const double* xs, const double* ys, const double* st, int B, int A,
-                                  int H, int W, int r, int cap, double* out, double* sums, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_head_mask_loss_bwd_f64(const double* mf, const double* um, const double* params, int ldp, const int* lvl, const double* masks, int M,
-                                  const unsigned char* fg, const int* mg, const double* xs, const double* ys, const double* st, int B, int A,
-                                  int H, int W, int r, int cap, const double* sums, const double* gout, double* gmf, double* gum,
-                                  double* gpar, int ldg, void* ws, size_t ws_bytes, hipStream_t s);
+template <typename T>
+struct HMIn {
+    const T *mf, *um, *params;
+    int ldp;
+    const int* lvl;
+    const T* masks;
+    int M;
+    const unsigned char* fg;
+    const int* mg;
+    const T *xs, *ys, *st;
+    int B, A, H, W, r, cap;
+};
+template <typename T>
+int launch_head_mask_loss_fwd(const HMIn<T>& a, T* out, T* sums, void* ws, size_t ws_bytes, hipStream_t s);
+template <typename T>
+int launch_head_mask_loss_bwd(const HMIn<T>& a, const T* sums, const T* gout, T* gmf, T* gum, T* gpar, int ldg, void* ws, size_t ws_bytes,
+                              hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

@@ -359,17 +359,6 @@ mc_scatter_kernel(const T* __restrict__ dE, const int* __restrict__ meta, const 
     }
 }
 
-struct McArgs {
-    const void *e0, *e1;
-    McStride s0, s1;
-    const float* targets;
-    int B, C, H, W, M;
-    float stride;
-    int flags;
-    void* ws;
-    size_t ws_bytes;
-};
-
 // the elements of a gradient map are distinct addresses: in the order of the strides, each stride covers the extent of the one before
 bool mc_disjoint(McStride s, int B, int C, int H, int W) {
     std::pair<long long, long long> d[4] = {{s.b, B}, {s.c, C}, {s.y, H}, {s.x, W}};
@@ -412,8 +401,15 @@ void mc_common(const McArgs& a, const McLayout& l, hipStream_t s) {
     mc_lse_kernel<T><<<dim3(a.M, (a.flags & 1) ? 2 : 1, a.B), 64, 0, s>>>(S, meta, a.M, lse);
 }
 
+}  // namespace
+
+size_t mot_corr_workspace_bytes(int B, int M, int C) {
+    if (!mc_shape_ok(B, M, C)) return 0;
+    return mc_layout(B, M, C, 4).total;
+}
+
 template <typename T>
-int mc_fwd(const McArgs& a, T* loss, hipStream_t s) {
+int launch_mot_corr_fwd(const McArgs& a, T* loss, hipStream_t s) {
     if (int rc = mc_check<T>(a, "mot_corr_loss_fwd")) return rc;
     const McLayout l = mc_layout(a.B, a.M, a.C, sizeof(T));
     mc_common<T>(a, l, s);
@@ -424,7 +420,7 @@ int mc_fwd(const McArgs& a, T* loss, hipStream_t s) {
 }
 
 template <typename T>
-int mc_bwd(const McArgs& a, const T* gout, T* g0, McStride gs0, T* g1, McStride gs1, hipStream_t s) {
+int launch_mot_corr_bwd(const McArgs& a, const T* gout, T* g0, McStride gs0, T* g1, McStride gs1, hipStream_t s) {
     if (int rc = mc_check<T>(a, "mot_corr_loss_bwd")) return rc;
     if (!g0 && !g1) return 0;
     UNI_REQUIRE(!g0 || mc_disjoint(gs0, a.B, a.C, a.H, a.W), "mot_corr_loss_bwd: strides of grad_embed_0 must be >= 1 and must not overlap");
@@ -446,28 +442,7 @@ int mc_bwd(const McArgs& a, const T* gout, T* g0, McStride gs0, T* g1, McStride 
     return 0;
 }
 
-}  // namespace
-
-size_t mot_corr_workspace_bytes(int B, int M, int C) {
-    if (!mc_shape_ok(B, M, C)) return 0;
-    return mc_layout(B, M, C, 4).total;
-}
-
-int launch_mot_corr_fwd(const float* e0, McStride s0, const float* e1, McStride s1, const float* targets, int B, int C, int H, int W, int M,
-                        float stride, int flags, float* loss, void* ws, size_t ws_bytes, hipStream_t s) {
-    return mc_fwd<float>(McArgs{e0, e1, s0, s1, targets, B, C, H, W, M, stride, flags, ws, ws_bytes}, loss, s);
-}
-int launch_mot_corr_bwd(const float* e0, McStride s0, const float* e1, McStride s1, const float* targets, const float* gout, int B, int C, int H,
-                        int W, int M, float stride, int flags, float* g0, McStride gs0, float* g1, McStride gs1, void* ws, size_t ws_bytes,
-                        hipStream_t s) {
-    return mc_bwd<float>(McArgs{e0, e1, s0, s1, targets, B, C, H, W, M, stride, flags, ws, ws_bytes}, gout, g0, gs0, g1, gs1, s);
-}
-int launch_mot_corr_fwd_f64(const double* e0, McStride s0, const double* e1, McStride s1, const float* targets, int B, int C, int H, int W, int M,
-                            float stride, int flags, double* loss, void* ws, size_t ws_bytes, hipStream_t s) {
-    return mc_fwd<double>(McArgs{e0, e1, s0, s1, targets, B, C, H, W, M, stride, flags, ws, ws_bytes}, loss, s);
-}
-int launch_mot_corr_bwd_f64(const double* e0, McStride s0, const double* e1, McStride s1, const float* targets, const double* gout, int B, int C,
-                            int H, int W, int M, float stride, int flags, double* g0, McStride gs0, double* g1, McStride gs1, void* ws,
-                            size_t ws_bytes, hipStream_t s) {
-    return mc_bwd<double>(McArgs{e0, e1, s0, s1, targets, B, C, H, W, M, stride, flags, ws, ws_bytes}, gout, g0, gs0, g1, gs1, s);
-}
+template int launch_mot_corr_fwd<float>(const McArgs&, float*, hipStream_t);
+template int launch_mot_corr_fwd<double>(const McArgs&, double*, hipStream_t);
+template int launch_mot_corr_bwd<float>(const McArgs&, const float*, float*, McStride, float*, McStride, hipStream_t);
+template int launch_mot_corr_bwd<double>(const McArgs&, const double*, double*, McStride, double*, McStride, hipStream_t);

@@ -343,23 +343,31 @@ int pl_pitch(long long Q) { return (int)((Q + 1023) / 1024); }      // >= the th
 
 bool pl_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
+}  // namespace
+
+size_t prop_workspace_bytes(int B, int Kc, int Q) {
+    if (!pl_shape_ok(B, Kc, Q)) return 0;
+    return ((size_t)B * Kc * pl_pitch(Q) * 3 * sizeof(double) + 255) & ~(size_t)255;
+}
+
 template <typename T>
-int pl_labels(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int r, int* matched,
-              int* num_matched, T* gt0, T* gt1, hipStream_t s) {
+int launch_prop_labels(const PlLabelArgs& a, T* gt0, T* gt1, hipStream_t s) {
+    const int B = a.B, M = a.M, Kc = a.Kc, H8 = a.H8, W8 = a.W8, r = a.r;
     const long long Q = (long long)H8 * W8;
     UNI_REQUIRE(H8 >= 4 && W8 >= 4 && pl_shape_ok(B, Kc, Q), "prop_labels: shape B=%d Kc=%d H8=%d W8=%d outside H8, W8 >= 4, 1 <= Kc <= 1024, B Kc <= 32767, B Kc H8 W8 < 2^31",
                 B, Kc, H8, W8);
     UNI_REQUIRE(M >= 1 && M <= PL_MAXM && Kc <= M, "prop_labels: M=%d outside 1 .. 1024 or Kc=%d > M", M, Kc);
-    UNI_REQUIRE(!sot || (Kc == 1 && !masks), "prop_labels: the SOT form has one slot per sample and no masks");
-    UNI_REQUIRE(!masks || r == 1 || r == 2 || r == 4, "prop_labels: mask rate r=%d is not 1, 2 or 4", r);
+    UNI_REQUIRE(!a.sot || (Kc == 1 && !a.masks), "prop_labels: the SOT form has one slot per sample and no masks");
+    UNI_REQUIRE(!a.masks || r == 1 || r == 2 || r == 4, "prop_labels: mask rate r=%d is not 1, 2 or 4", r);
     UNI_REQUIRE(H8 <= (1 << 27) && W8 <= (1 << 27), "prop_labels: map too large");
     const int V = (Q % 4 == 0 && pl_aligned(gt0, 4 * sizeof(T)) && pl_aligned(gt1, 4 * sizeof(T))) ? 4 : 1;
-    const int kind = !masks ? 0 : mask_u8 ? 2 : 1;
-    uni_variant_note("prop_labels %s kind=%s vec=%d sot=%d", sizeof(T) == 8 ? "f64" : "f32", kind == 0 ? "box" : kind == 1 ? "mask_f32" : "mask_u8", V, sot);
-    pl_match_kernel<<<B, PL_TB, 0, s>>>(targets, M, Kc, sot, matched, num_matched);
+    const int kind = !a.masks ? 0 : a.mask_u8 ? 2 : 1;
+    uni_variant_note("prop_labels %s kind=%s vec=%d sot=%d", sizeof(T) == 8 ? "f64" : "f32", kind == 0 ? "box" : kind == 1 ? "mask_f32" : "mask_u8", V, a.sot);
+    pl_match_kernel<<<B, PL_TB, 0, s>>>(a.targets, M, Kc, a.sot, a.matched, a.num_matched);
     const dim3 grid(cdiv(cdiv((int)Q, V), PL_TB), 2 * B * Kc);
     const int H = 8 * H8, W = 8 * W8;
-#define PL_LABEL(MT, VV) pl_label_kernel<T, MT, VV><<<grid, PL_TB, 0, s>>>(targets, (const MT*)masks, matched, num_matched, M, Kc, H, W, H8, W8, r, gt0, gt1)
+#define PL_LABEL(MT, VV) \
+    pl_label_kernel<T, MT, VV><<<grid, PL_TB, 0, s>>>(a.targets, (const MT*)a.masks, a.matched, a.num_matched, M, Kc, H, W, H8, W8, r, gt0, gt1)
     if (kind == 0) { if (V == 4) PL_LABEL(void, 4); else PL_LABEL(void, 1); }
     else if (kind == 1) { if (V == 4) PL_LABEL(float, 4); else PL_LABEL(float, 1); }
     else { if (V == 4) PL_LABEL(unsigned char, 4); else PL_LABEL(unsigned char, 1); }
@@ -368,8 +376,8 @@ int pl_labels(const float* targets, const void* masks, int mask_u8, int B, int M
 }
 
 template <typename T>
-int pl_fwd(const T* pred, const T* gt1, const int* num_matched, int B, int Kc, int H8, int W8, T* p16, T* p32, T* loss, double* sums, void* ws,
-           size_t ws_bytes, hipStream_t s) {
+int launch_prop_dice_pyramid_fwd(const PlDiceArgs<T>& a, T* p16, T* p32, T* loss, double* sums, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int B = a.B, Kc = a.Kc, H8 = a.H8, W8 = a.W8;
     const long long Q = (long long)H8 * W8;
     UNI_REQUIRE(H8 >= 4 && W8 >= 4 && pl_shape_ok(B, Kc, Q), "prop_dice_pyramid_fwd: shape B=%d Kc=%d H8=%d W8=%d outside H8, W8 >= 4, 1 <= Kc <= 1024, B Kc <= 32767, B Kc H8 W8 < 2^31",
                 B, Kc, H8, W8);
@@ -378,62 +386,39 @@ int pl_fwd(const T* pred, const T* gt1, const int* num_matched, int B, int Kc, i
     const int slots = B * Kc, pitch = pl_pitch(Q);
     const int nblk = cdiv(cdiv(H8, 4) * cdiv(W8, 4), PL_TB);
     UNI_REQUIRE(nblk <= pitch, "prop_dice_pyramid_fwd: internal: %d partial blocks > pitch %d", nblk, pitch);
-    const bool vec = W8 % 4 == 0 && pl_aligned(pred, 4 * sizeof(T)) && pl_aligned(gt1, 4 * sizeof(T)) && pl_aligned(p16, 2 * sizeof(T));
-    uni_variant_note("prop_dice_pyramid_fwd %s vec=%d sot=%d", sizeof(T) == 8 ? "f64" : "f32", vec, num_matched == nullptr);
+    const bool vec = W8 % 4 == 0 && pl_aligned(a.pred, 4 * sizeof(T)) && pl_aligned(a.gt1, 4 * sizeof(T)) && pl_aligned(p16, 2 * sizeof(T));
+    uni_variant_note("prop_dice_pyramid_fwd %s vec=%d sot=%d", sizeof(T) == 8 ? "f64" : "f32", vec, a.num_matched == nullptr);
     double* partial = reinterpret_cast<double*>(ws);
-    if (vec) pl_fwd_kernel<T, true><<<dim3(nblk, slots), PL_TB, 0, s>>>(pred, gt1, H8, W8, p16, p32, partial, pitch);
-    else pl_fwd_kernel<T, false><<<dim3(nblk, slots), PL_TB, 0, s>>>(pred, gt1, H8, W8, p16, p32, partial, pitch);
-    if (num_matched) pl_final_kernel<T><<<slots, 64, 0, s>>>(partial, pitch, nblk, 1, num_matched, Kc, loss, sums);
+    if (vec) pl_fwd_kernel<T, true><<<dim3(nblk, slots), PL_TB, 0, s>>>(a.pred, a.gt1, H8, W8, p16, p32, partial, pitch);
+    else pl_fwd_kernel<T, false><<<dim3(nblk, slots), PL_TB, 0, s>>>(a.pred, a.gt1, H8, W8, p16, p32, partial, pitch);
+    if (a.num_matched) pl_final_kernel<T><<<slots, 64, 0, s>>>(partial, pitch, nblk, 1, a.num_matched, Kc, loss, sums);
     else pl_final_kernel<T><<<1, 64, 0, s>>>(partial, pitch, nblk, slots, nullptr, Kc, loss, sums);
     return 0;
 }
 
 template <typename T>
-int pl_bwd(const T* pred, const T* gt1, const int* num_matched, const double* sums, const T* g8, const T* g16, const T* g32, const T* gl, int B,
-           int Kc, int H8, int W8, T* gpred, hipStream_t s) {
+int launch_prop_dice_pyramid_bwd(const PlDiceArgs<T>& a, const double* sums, const T* g8, const T* g16, const T* g32, const T* gl, T* gpred,
+                                 hipStream_t s) {
+    const int B = a.B, Kc = a.Kc, H8 = a.H8, W8 = a.W8;
     const long long Q = (long long)H8 * W8;
     UNI_REQUIRE(H8 >= 4 && W8 >= 4 && pl_shape_ok(B, Kc, Q), "prop_dice_pyramid_bwd: shape B=%d Kc=%d H8=%d W8=%d outside H8, W8 >= 4, 1 <= Kc <= 1024, B Kc <= 32767, B Kc H8 W8 < 2^31",
                 B, Kc, H8, W8);
     UNI_REQUIRE(pl_aligned(sums, 8), "prop_dice_pyramid_bwd: sums must be 8-byte aligned");
-    const size_t a = 4 * sizeof(T);
-    const bool vec = W8 % 4 == 0 && pl_aligned(pred, a) && pl_aligned(gt1, a) && pl_aligned(gpred, a) && (!g8 || pl_aligned(g8, a));
-    uni_variant_note("prop_dice_pyramid_bwd %s vec=%d sot=%d", sizeof(T) == 8 ? "f64" : "f32", vec, num_matched == nullptr);
+    const size_t al = 4 * sizeof(T);
+    const bool vec = W8 % 4 == 0 && pl_aligned(a.pred, al) && pl_aligned(a.gt1, al) && pl_aligned(gpred, al) && (!g8 || pl_aligned(g8, al));
+    uni_variant_note("prop_dice_pyramid_bwd %s vec=%d sot=%d", sizeof(T) == 8 ? "f64" : "f32", vec, a.num_matched == nullptr);
     const int V = vec ? 4 : 1;
     const dim3 grid(cdiv(cdiv(W8, V) * H8, PL_TB), B * Kc);
-    if (vec) pl_bwd_kernel<T, 4><<<grid, PL_TB, 0, s>>>(pred, gt1, num_matched, sums, g8, g16, g32, gl, Kc, H8, W8, gpred);
-    else pl_bwd_kernel<T, 1><<<grid, PL_TB, 0, s>>>(pred, gt1, num_matched, sums, g8, g16, g32, gl, Kc, H8, W8, gpred);
+    if (vec) pl_bwd_kernel<T, 4><<<grid, PL_TB, 0, s>>>(a.pred, a.gt1, a.num_matched, sums, g8, g16, g32, gl, Kc, H8, W8, gpred);
+    else pl_bwd_kernel<T, 1><<<grid, PL_TB, 0, s>>>(a.pred, a.gt1, a.num_matched, sums, g8, g16, g32, gl, Kc, H8, W8, gpred);
     return 0;
 }
 
-}  // namespace
-
-size_t prop_workspace_bytes(int B, int Kc, int Q) {
-    if (!pl_shape_ok(B, Kc, Q)) return 0;
-    return ((size_t)B * Kc * pl_pitch(Q) * 3 * sizeof(double) + 255) & ~(size_t)255;
-}
-
-int launch_prop_labels(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int r, int* matched,
-                       int* num_matched, float* gt0, float* gt1, hipStream_t s) {
-    return pl_labels<float>(targets, masks, mask_u8, B, M, Kc, sot, H8, W8, r, matched, num_matched, gt0, gt1, s);
-}
-int launch_prop_labels_f64(const float* targets, const void* masks, int mask_u8, int B, int M, int Kc, int sot, int H8, int W8, int r, int* matched,
-                           int* num_matched, double* gt0, double* gt1, hipStream_t s) {
-    return pl_labels<double>(targets, masks, mask_u8, B, M, Kc, sot, H8, W8, r, matched, num_matched, gt0, gt1, s);
-}
-int launch_prop_dice_pyramid_fwd(const float* pred, const float* gt1, const int* num_matched, int B, int Kc, int H8, int W8, float* p16, float* p32,
-                                 float* loss, double* sums, void* ws, size_t ws_bytes, hipStream_t s) {
-    return pl_fwd<float>(pred, gt1, num_matched, B, Kc, H8, W8, p16, p32, loss, sums, ws, ws_bytes, s);
-}
-int launch_prop_dice_pyramid_fwd_f64(const double* pred, const double* gt1, const int* num_matched, int B, int Kc, int H8, int W8, double* p16,
-                                     double* p32, double* loss, double* sums, void* ws, size_t ws_bytes, hipStream_t s) {
-    return pl_fwd<double>(pred, gt1, num_matched, B, Kc, H8, W8, p16, p32, loss, sums, ws, ws_bytes, s);
-}
-int launch_prop_dice_pyramid_bwd(const float* pred, const float* gt1, const int* num_matched, const double* sums, const float* g8, const float* g16,
-                                 const float* g32, const float* gl, int B, int Kc, int H8, int W8, float* gpred, hipStream_t s) {
-    return pl_bwd<float>(pred, gt1, num_matched, sums, g8, g16, g32, gl, B, Kc, H8, W8, gpred, s);
-}
-int launch_prop_dice_pyramid_bwd_f64(const double* pred, const double* gt1, const int* num_matched, const double* sums, const double* g8,
-                                     const double* g16, const double* g32, const double* gl, int B, int Kc, int H8, int W8, double* gpred,
-                                     hipStream_t s) {
-    return pl_bwd<double>(pred, gt1, num_matched, sums, g8, g16, g32, gl, B, Kc, H8, W8, gpred, s);
-}
+template int launch_prop_labels<float>(const PlLabelArgs&, float*, float*, hipStream_t);
+template int launch_prop_labels<double>(const PlLabelArgs&, double*, double*, hipStream_t);
+template int launch_prop_dice_pyramid_fwd<float>(const PlDiceArgs<float>&, float*, float*, float*, double*, void*, size_t, hipStream_t);
+template int launch_prop_dice_pyramid_fwd<double>(const PlDiceArgs<double>&, double*, double*, double*, double*, void*, size_t, hipStream_t);
+template int launch_prop_dice_pyramid_bwd<float>(const PlDiceArgs<float>&, const double*, const float*, const float*, const float*, const float*,
+                                                 float*, hipStream_t);
+template int launch_prop_dice_pyramid_bwd<double>(const PlDiceArgs<double>&, const double*, const double*, const double*, const double*,
+                                                  const double*, double*, hipStream_t);

@@ -22,7 +22,30 @@ def empty_nhwc(c, h, w, device, b=1):
     return torch.empty((b, c, h, w), device=device, dtype=torch.float32, memory_format=torch.channels_last)
 
 
-_MSDA_ENTRY = {torch.float32: ("uni_msda_fwd", "uni_msda_bwd"), torch.float64: ("uni_msda_fwd_f64", "uni_msda_bwd_f64")}
+_F64_SFX = {torch.float32: "", torch.float64: "_f64"}      # the dtypes of the fp32 / fp64 operator pairs -> suffix of the exported name
+
+
+def _entry(base, dtype, err=None):
+    """(bound library function, exported name) of the fp32 / fp64 operator pair `base` for `dtype`; the name is what L.check reports.
+    Any other dtype raises `err`, the caller's own message."""
+    if dtype not in _F64_SFX:
+        raise L.UnicornHipError(err or "%s: dtype %s unsupported (fp32 / fp64)" % (base, dtype))
+    name = base + _F64_SFX[dtype]
+    return getattr(L.lib(), name), name
+
+
+def _ws_factor(dtype):
+    """the workspace size functions count fp32 elements: the fp64 forms need twice that"""
+    return torch.finfo(dtype).bits // 32
+
+
+def _stream_scratch(cache, dev, need):
+    """grow-only byte scratch of at least `need` bytes, one per (device, current stream), kept in the dict `cache`"""
+    key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = cache[key] = torch.empty(max(need, 1), device=dev, dtype=torch.uint8)
+    return ws
 
 
 def _msda_args(what, value, spatial_shapes, level_start_index, loc, attn, *more):
@@ -30,8 +53,7 @@ def _msda_args(what, value, spatial_shapes, level_start_index, loc, attn, *more)
     AT_DISPATCH_FLOATING_TYPES on value.type()), contiguous copies, the host int64 shape arrays and the sizes."""
     ts = (value, loc, attn) + more
     _need_cuda(*ts)
-    if value.dtype not in _MSDA_ENTRY:
-        raise L.UnicornHipError("%s: dtype %s unsupported (fp32 / fp64, like the reference's dispatch)" % (what, value.dtype))
+    _entry("uni_msda_fwd", value.dtype, "%s: dtype %s unsupported (fp32 / fp64, like the reference's dispatch)" % (what, value.dtype))
     if any(t.dtype != value.dtype for t in ts):
         raise L.UnicornHipError("%s: mixed dtypes %s (every floating tensor must have value's dtype)" % (what, [str(t.dtype) for t in ts]))
     if value.dim() != 4 or loc.dim() != 6 or attn.dim() != 5 or loc.shape[-1] != 2 or tuple(loc.shape[:5]) != tuple(attn.shape) \
@@ -55,9 +77,8 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_locations, a
     out = torch.empty((N, Lq, M * D), device=value.device, dtype=value.dtype)
     if out.numel() == 0:
         return out
-    name = _MSDA_ENTRY[value.dtype][0]
-    L.check(getattr(L.lib(), name)(L.ptr(value), shp, lsi, L.ptr(loc), L.ptr(attn), L.ptr(out), N, S, M, D, Lq, Ln, P,
-                                   L.stream_ptr()), name)
+    fn, name = _entry("uni_msda_fwd", value.dtype)
+    L.check(fn(L.ptr(value), shp, lsi, L.ptr(loc), L.ptr(attn), L.ptr(out), N, S, M, D, Lq, Ln, P, L.stream_ptr()), name)
     return out
 
 
@@ -74,9 +95,9 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_locations, 
     gvalue, gloc, gattn = torch.empty_like(value), torch.empty_like(loc), torch.empty_like(attn)
     if value.numel() == 0 or attn.numel() == 0:       # no query / empty batch: nothing to scatter (empty tensors have no device pointer)
         return gvalue.zero_(), gloc, gattn
-    name = _MSDA_ENTRY[value.dtype][1]
-    L.check(getattr(L.lib(), name)(L.ptr(value), shp, lsi, L.ptr(loc), L.ptr(attn), L.ptr(gout), L.ptr(gvalue), L.ptr(gloc),
-                                   L.ptr(gattn), N, S, M, D, Lq, Ln, P, L.stream_ptr()), name)
+    fn, name = _entry("uni_msda_bwd", value.dtype)
+    L.check(fn(L.ptr(value), shp, lsi, L.ptr(loc), L.ptr(attn), L.ptr(gout), L.ptr(gvalue), L.ptr(gloc), L.ptr(gattn), N, S, M, D, Lq, Ln, P,
+               L.stream_ptr()), name)
     return gvalue, gloc, gattn
 
 
@@ -119,12 +140,7 @@ def corr_softmax_pv(embed_ref, embed_cur, values, precision=0):
     Q = ec.shape[0]
     K = v.shape[0]
     out = torch.empty((K, Q), device=er.device, dtype=torch.float32)
-    need = L.lib().uni_corr_workspace_bytes(R, Q, K)
-    key = (er.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _corr_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), device=er.device, dtype=torch.uint8)
-        _corr_ws[key] = ws
+    ws = _stream_scratch(_corr_ws, er.device, L.lib().uni_corr_workspace_bytes(R, Q, K))
     L.check(L.lib().uni_corr_softmax_pv(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(out), R, Q, D, K, precision, L.ptr(ws),
                                         ws.numel(), L.stream_ptr()), "uni_corr_softmax_pv")
     return out
@@ -148,24 +164,10 @@ def corr_softmax_pv_batched(embed_ref, embed_cur, values, precision=2, values_pe
     if ec.shape[0] != B or v.shape[-1] != R:
         raise ValueError("corr_softmax_pv_batched: shape mismatch")
     out = torch.empty((B, K, Q), device=er.device, dtype=torch.float32)
-    need = L.lib().uni_corr_workspace_bytes_batched(B, R, Q, K)
-    key = (er.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _corr_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), device=er.device, dtype=torch.uint8)
-        _corr_ws[key] = ws
+    ws = _stream_scratch(_corr_ws, er.device, L.lib().uni_corr_workspace_bytes_batched(B, R, Q, K))
     L.check(L.lib().uni_corr_softmax_pv_batched(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(out), B, R, Q, D, K, 1 if values_per_frame else 0,
                                                 precision, L.ptr(ws), ws.numel(), L.stream_ptr()), "uni_corr_softmax_pv_batched")
     return out
-
-
-def _corr_scratch(dev, need):
-    key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    ws = _corr_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), device=dev, dtype=torch.uint8)
-        _corr_ws[key] = ws
-    return ws
 
 
 def _corr_train_args(what, embed_ref, embed_cur, values, *more):
@@ -204,7 +206,7 @@ def corr_softmax_pv_lse(embed_ref, embed_cur, values, precision=0):
             L.check(L.lib().uni_corr_softmax_pv_lse_f64(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(out), L.ptr(lse), B, R, Q, D, K, 0 if shared else 1,
                                                         L.stream_ptr()), "uni_corr_softmax_pv_lse_f64")
         else:
-            ws = _corr_scratch(er.device, L.lib().uni_corr_bwd_workspace_bytes(B, R, Q, K))
+            ws = _stream_scratch(_corr_ws, er.device, L.lib().uni_corr_bwd_workspace_bytes(B, R, Q, K))
             L.check(L.lib().uni_corr_softmax_pv_lse(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(out), L.ptr(lse), B, R, Q, D, K, 0 if shared else 1,
                                                     int(precision), L.ptr(ws), ws.numel(), L.stream_ptr()), "uni_corr_softmax_pv_lse")
     return out, lse
@@ -234,7 +236,7 @@ def corr_softmax_pv_backward(embed_ref, embed_cur, values, out, lse, grad_out, n
             L.check(L.lib().uni_corr_softmax_pv_bwd_f64(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(o), L.ptr(lse), L.ptr(g), L.ptr(ger), L.ptr(gec),
                                                         L.ptr(gv), B, R, Q, D, K, 0 if shared else 1, L.stream_ptr()), "uni_corr_softmax_pv_bwd_f64")
         else:
-            ws = _corr_scratch(er.device, L.lib().uni_corr_bwd_workspace_bytes(B, R, Q, K))
+            ws = _stream_scratch(_corr_ws, er.device, L.lib().uni_corr_bwd_workspace_bytes(B, R, Q, K))
             L.check(L.lib().uni_corr_softmax_pv_bwd(L.ptr(er), L.ptr(ec), L.ptr(v), L.ptr(o), L.ptr(lse), L.ptr(g), L.ptr(ger), L.ptr(gec),
                                                     L.ptr(gv), B, R, Q, D, K, 0 if shared else 1, int(precision), L.ptr(ws), ws.numel(), L.stream_ptr()),
                     "uni_corr_softmax_pv_bwd")
@@ -308,30 +310,34 @@ def sample_embeddings(embed, boxes_xyxy, stride=8.0):
     return out
 
 
-def condinst_masks(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate, d_rate):
-    """-> (N,1,d_rate*up_rate*H8, d_rate*up_rate*W8) sigmoid scores"""
+def _condinst_inputs(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate):
+    """what condinst_masks and condinst_masks_resized hand to the library: the NHWC maps, fp32 parameter rows, and for n > 0 instances
+    their locations / int32 levels on the maps' device and the fp32 workspace -> (mf, um, p, loc, lvl, ws)"""
     _need_cuda(mask_feats, up_masks, params)
     mf, um = nhwc(mask_feats), nhwc(up_masks)
-    _, _, H8, W8 = mf.shape
     p = params.float().contiguous()
-    n = p.shape[0]
+    if p.shape[0] == 0:
+        return mf, um, p, None, None, None
     loc = inst_loc.float().contiguous().to(mf.device)
     lvl = inst_lvl.to(device=mf.device, dtype=torch.int32).contiguous()
+    ws = torch.empty(p.shape[0] * mf.shape[2] * mf.shape[3] * (1 + up_rate * up_rate), device=mf.device, dtype=torch.float32)
+    return mf, um, p, loc, lvl, ws
+
+
+def condinst_masks(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate, d_rate):
+    """-> (N,1,d_rate*up_rate*H8, d_rate*up_rate*W8) sigmoid scores"""
+    mf, um, p, loc, lvl, ws = _condinst_inputs(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate)
+    (_, _, H8, W8), n = mf.shape, p.shape[0]
     out = torch.empty((n, 1, d_rate * up_rate * H8, d_rate * up_rate * W8), device=mf.device, dtype=torch.float32)
     if n:
-        ws = torch.empty(n * H8 * W8 * (1 + up_rate * up_rate), device=mf.device, dtype=torch.float32)
         L.check(L.lib().uni_condinst_masks(L.ptr(mf), L.ptr(um), L.ptr(p), p.shape[1], L.ptr(loc), L.ptr(lvl), n, H8, W8,
                                            up_rate, d_rate, L.ptr(out), L.ptr(ws), ws.numel() * 4, L.stream_ptr()),
                 "uni_condinst_masks")
     return out
 
 
-_CL_ENTRY = {torch.float32: ("uni_condinst_loss_fwd", "uni_condinst_loss_bwd", 1),
-             torch.float64: ("uni_condinst_loss_fwd_f64", "uni_condinst_loss_bwd_f64", 2)}
-
-
 def _condinst_loss_ws(dev, dtype, n, H8, W8, r):
-    need = L.lib().uni_condinst_loss_workspace_bytes(n, H8, W8, r) * _CL_ENTRY[dtype][2]        # the fp64 forms need twice the fp32 size
+    need = L.lib().uni_condinst_loss_workspace_bytes(n, H8, W8, r) * _ws_factor(dtype)
     return torch.empty(max(need, 8), device=dev, dtype=torch.uint8)
 
 
@@ -345,13 +351,13 @@ class CondInstDiceFunction(torch.autograd.Function):
     def forward(ctx, mask_feats, up_masks, params, inst_loc, inst_lvl, gt, up_rate):
         H8, W8, _ = mask_feats.shape
         n, r = params.shape[0], int(up_rate)
-        fwd = _CL_ENTRY[params.dtype][0]
+        fn, fwd = _entry("uni_condinst_loss_fwd", params.dtype)
         loss = torch.empty((n,), device=params.device, dtype=params.dtype)
         sums = torch.empty((n, 3), device=params.device, dtype=params.dtype)
         with torch.cuda.device(params.device):
             ws = _condinst_loss_ws(params.device, params.dtype, n, H8, W8, r)
-            L.check(getattr(L.lib(), fwd)(L.ptr(mask_feats), L.ptr(up_masks), L.ptr(params), params.stride(0), L.ptr(inst_loc), L.ptr(inst_lvl),
-                                          L.ptr(gt), n, H8, W8, r, L.ptr(loss), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
+            L.check(fn(L.ptr(mask_feats), L.ptr(up_masks), L.ptr(params), params.stride(0), L.ptr(inst_loc), L.ptr(inst_lvl), L.ptr(gt), n, H8, W8, r,
+                       L.ptr(loss), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
         ctx.save_for_backward(mask_feats, up_masks, params, inst_loc, inst_lvl, gt, sums)
         ctx.up_rate = r
         return loss
@@ -362,7 +368,7 @@ class CondInstDiceFunction(torch.autograd.Function):
         mf, um, p, loc, lvl, gt, sums = ctx.saved_tensors
         H8, W8, _ = mf.shape
         n, r = p.shape[0], ctx.up_rate
-        bwd = _CL_ENTRY[p.dtype][1]
+        fn, bwd = _entry("uni_condinst_loss_bwd", p.dtype)
         g = grad_loss.contiguous()
         gmf = torch.empty_like(mf) if ctx.needs_input_grad[0] else None
         gum = torch.empty_like(um) if ctx.needs_input_grad[1] else None
@@ -370,8 +376,8 @@ class CondInstDiceFunction(torch.autograd.Function):
         if gmf is not None or gum is not None or gp is not None:
             with torch.cuda.device(p.device):
                 ws = _condinst_loss_ws(p.device, p.dtype, n, H8, W8, r)
-                L.check(getattr(L.lib(), bwd)(L.ptr(mf), L.ptr(um), L.ptr(p), p.stride(0), L.ptr(loc), L.ptr(lvl), L.ptr(gt), L.ptr(sums), L.ptr(g),
-                                              n, H8, W8, r, L.ptr(gmf), L.ptr(gum), L.ptr(gp), L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
+                L.check(fn(L.ptr(mf), L.ptr(um), L.ptr(p), p.stride(0), L.ptr(loc), L.ptr(lvl), L.ptr(gt), L.ptr(sums), L.ptr(g), n, H8, W8, r,
+                           L.ptr(gmf), L.ptr(gum), L.ptr(gp), L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
         return gmf, gum, gp, None, None, None, None
 
 
@@ -394,7 +400,7 @@ def condinst_dice_loss(mask_feats, up_masks, params, inst_loc, inst_lvl, gt_bitm
     if tuple(gt_bitmasks.shape) not in ((n, 1, r * H8, r * W8), (n, r * H8, r * W8)):
         raise L.UnicornHipError("condinst_dice_loss: gt_bitmasks %s do not fit (N,1,r H8,r W8) = (%d, 1, %d, %d): the ground truth must be exactly "
                                 "up_rate x the feature map" % (tuple(gt_bitmasks.shape), n, r * H8, r * W8))
-    if params.dtype not in _CL_ENTRY or any(t.dtype != params.dtype for t in ts):
+    if params.dtype not in _F64_SFX or any(t.dtype != params.dtype for t in ts):
         raise L.UnicornHipError("condinst_dice_loss: dtypes %s unsupported (all fp32 or all fp64)" % [str(t.dtype) for t in ts])
     if inst_lvl.dtype.is_floating_point or inst_lvl.dtype == torch.bool:
         raise L.UnicornHipError("condinst_dice_loss: inst_lvl must be an integer tensor, got %s" % inst_lvl.dtype)
@@ -537,9 +543,6 @@ def simota_assign(bboxes_preds_per_image, obj_preds_b, cls_preds_b, gt_bboxes_pe
         return gtc[inds], fg, iou[0][anchors], inds, n
 
 
-_HL_ENTRY = {torch.float32: ("uni_head_loss_fwd", "uni_head_loss_bwd"), torch.float64: ("uni_head_loss_fwd_f64", "uni_head_loss_bwd_f64")}
-
-
 def _hl_ws(dev, B, A, Cn):
     need = L.lib().uni_head_loss_workspace_bytes(B, A, Cn)
     if need == 0:
@@ -571,11 +574,11 @@ class HeadLossFunction(torch.autograd.Function):
         ctx.save_for_backward(*ins)
         ctx.reg_weight, ctx.dims = float(reg_weight), (B, A, Cn, M)
         res = torch.empty((5,), device=dev, dtype=outputs.dtype)
-        fwd = _HL_ENTRY[outputs.dtype][0]
+        fn, fwd = _entry("uni_head_loss_fwd", outputs.dtype)
         with torch.cuda.device(dev):
             ws = _hl_ws(dev, B, A, Cn)
-            L.check(getattr(L.lib(), fwd)(L.ptr(out_), out_.stride(1), L.ptr(org_), 0 if org_ is None else org_.stride(1), L.ptr(ins[2]), M,
-                                          *map(L.ptr, ins[3:]), B, A, Cn, ctx.reg_weight, L.ptr(res), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
+            L.check(fn(L.ptr(out_), out_.stride(1), L.ptr(org_), 0 if org_ is None else org_.stride(1), L.ptr(ins[2]), M, *map(L.ptr, ins[3:]), B, A,
+                       Cn, ctx.reg_weight, L.ptr(res), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
         return res
 
     @staticmethod
@@ -588,13 +591,12 @@ class HeadLossFunction(torch.autograd.Function):
         g_out = torch.empty((B, A, 5 + Cn), device=out_.device, dtype=out_.dtype) if ctx.needs_input_grad[0] else None
         g_org = torch.empty((B, A, 4), device=out_.device, dtype=out_.dtype) if org_ is not None and ctx.needs_input_grad[1] else None
         if g_out is not None or g_org is not None:
-            bwd = _HL_ENTRY[out_.dtype][1]
+            fn, bwd = _entry("uni_head_loss_bwd", out_.dtype)
             g = grad_res[:4].contiguous()
             with torch.cuda.device(out_.device):
                 ws = _hl_ws(out_.device, B, A, Cn)
-                L.check(getattr(L.lib(), bwd)(L.ptr(out_), out_.stride(1), L.ptr(org_), 0 if org_ is None else org_.stride(1), L.ptr(ins[2]), M,
-                                              *map(L.ptr, ins[3:]), L.ptr(g), B, A, Cn, ctx.reg_weight, L.ptr(g_out), 5 + Cn, L.ptr(g_org),
-                                              L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
+                L.check(fn(L.ptr(out_), out_.stride(1), L.ptr(org_), 0 if org_ is None else org_.stride(1), L.ptr(ins[2]), M, *map(L.ptr, ins[3:]),
+                           L.ptr(g), B, A, Cn, ctx.reg_weight, L.ptr(g_out), 5 + Cn, L.ptr(g_org), L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
         return (g_out, g_org) + (None,) * 10
 
 
@@ -664,16 +666,12 @@ def head_det_loss(outputs, origin_preds, labels, x_shifts, y_shifts, expanded_st
     return losses, assignment
 
 
-_HM_ENTRY = {torch.float32: ("uni_head_mask_loss_fwd", "uni_head_mask_loss_bwd", 1),
-             torch.float64: ("uni_head_mask_loss_fwd_f64", "uni_head_mask_loss_bwd_f64", 2)}
-
-
 def _hm_ws(dev, dtype, B, A, H8, W8, r, cap):
     need = L.lib().uni_head_mask_loss_workspace_bytes(B, A, H8, W8, r, cap)
     if need == 0:
         raise L.UnicornHipError("head_mask_loss: shape B=%d A=%d H8=%d W8=%d up_rate=%d capacity=%d is outside the limits of "
                                 "uni_head_mask_loss_fwd (include/unicorn_hip.h)" % (B, A, H8, W8, r, cap))
-    return torch.empty(need * _HM_ENTRY[dtype][2], device=dev, dtype=torch.uint8)      # the fp64 forms need twice the fp32 size
+    return torch.empty(need * _ws_factor(dtype), device=dev, dtype=torch.uint8)
 
 
 class HeadMaskLossFunction(torch.autograd.Function):
@@ -690,14 +688,14 @@ class HeadMaskLossFunction(torch.autograd.Function):
         B, H8, W8, _ = mask_feats.shape
         A, M, r, cap = params.shape[1], masks.shape[1], int(up_rate), int(capacity)
         dev, dt = params.device, params.dtype
-        fwd = _HM_ENTRY[dt][0]
+        fn, fwd = _entry("uni_head_mask_loss_fwd", dt)
         out = torch.empty((1 + B,), device=dev, dtype=dt)
         sums = torch.empty((cap, 3), device=dev, dtype=dt)
         with torch.cuda.device(dev):
             ws = _hm_ws(dev, dt, B, A, H8, W8, r, cap)
-            L.check(getattr(L.lib(), fwd)(L.ptr(mask_feats), L.ptr(up_masks), L.ptr(params), params.stride(1), L.ptr(fpn_levels), L.ptr(masks), M,
-                                          L.ptr(fg), L.ptr(matched), L.ptr(xs), L.ptr(ys), L.ptr(st), B, A, H8, W8, r, cap, L.ptr(out),
-                                          L.ptr(sums), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
+            L.check(fn(L.ptr(mask_feats), L.ptr(up_masks), L.ptr(params), params.stride(1), L.ptr(fpn_levels), L.ptr(masks), M, L.ptr(fg),
+                       L.ptr(matched), L.ptr(xs), L.ptr(ys), L.ptr(st), B, A, H8, W8, r, cap, L.ptr(out), L.ptr(sums), L.ptr(ws), ws.numel(),
+                       L.stream_ptr()), fwd)
         ctx.save_for_backward(mask_feats, up_masks, params, fpn_levels, masks, fg, matched, xs, ys, st, sums)
         ctx.up_rate, ctx.capacity = r, cap
         return out
@@ -708,7 +706,7 @@ class HeadMaskLossFunction(torch.autograd.Function):
         mf, um, p, lvl, masks, fg, matched, xs, ys, st, sums = ctx.saved_tensors
         B, H8, W8, _ = mf.shape
         A, M, r, cap = p.shape[1], masks.shape[1], ctx.up_rate, ctx.capacity
-        bwd = _HM_ENTRY[p.dtype][1]
+        fn, bwd = _entry("uni_head_mask_loss_bwd", p.dtype)
         # all three are written completely by the call
         gmf = torch.empty_like(mf) if ctx.needs_input_grad[0] else None
         gum = torch.empty_like(um) if ctx.needs_input_grad[1] else None
@@ -717,9 +715,9 @@ class HeadMaskLossFunction(torch.autograd.Function):
             g = grad_out[:1].contiguous()                    # the per-image losses are returned detached
             with torch.cuda.device(p.device):
                 ws = _hm_ws(p.device, p.dtype, B, A, H8, W8, r, cap)
-                L.check(getattr(L.lib(), bwd)(L.ptr(mf), L.ptr(um), L.ptr(p), p.stride(1), L.ptr(lvl), L.ptr(masks), M, L.ptr(fg), L.ptr(matched),
-                                              L.ptr(xs), L.ptr(ys), L.ptr(st), B, A, H8, W8, r, cap, L.ptr(sums), L.ptr(g), L.ptr(gmf), L.ptr(gum),
-                                              L.ptr(gp), 169, L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
+                L.check(fn(L.ptr(mf), L.ptr(um), L.ptr(p), p.stride(1), L.ptr(lvl), L.ptr(masks), M, L.ptr(fg), L.ptr(matched), L.ptr(xs), L.ptr(ys),
+                           L.ptr(st), B, A, H8, W8, r, cap, L.ptr(sums), L.ptr(g), L.ptr(gmf), L.ptr(gum), L.ptr(gp), 169, L.ptr(ws), ws.numel(),
+                           L.stream_ptr()), bwd)
         return (gmf, gum, gp) + (None,) * 9
 
 
@@ -759,7 +757,7 @@ def head_mask_loss(mask_feats, up_masks, dynamic_params, fpn_levels, masks, assi
         raise L.UnicornHipError("head_mask_loss: fpn_levels %s, fg_masks %s, matched_gt_inds %s do not fit (B, A) = (%d, %d)"
                                 % (tuple(fpn_levels.shape), tuple(fg.shape), tuple(matched.shape), B, A))
     dt = dynamic_params.dtype
-    if dt not in _HM_ENTRY or any(t.dtype != dt for t in ts[:7]):
+    if dt not in _F64_SFX or any(t.dtype != dt for t in ts[:7]):
         raise L.UnicornHipError("head_mask_loss: dtypes %s unsupported (all fp32 or all fp64; no fp16 / bf16)" % [str(t.dtype) for t in ts[:7]])
     if fpn_levels.dtype.is_floating_point or fpn_levels.dtype == torch.bool or matched.dtype.is_floating_point or matched.dtype == torch.bool \
             or fg.dtype.is_floating_point:
@@ -795,10 +793,6 @@ def head_mask_loss(mask_feats, up_masks, dynamic_params, fpn_levels, masks, assi
     return out[0], out[1:].detach()
 
 
-_MC_ENTRY = {torch.float32: ("uni_mot_corr_loss_fwd", "uni_mot_corr_loss_bwd", 1),
-             torch.float64: ("uni_mot_corr_loss_fwd_f64", "uni_mot_corr_loss_bwd_f64", 2)}
-
-
 def _mc_strides(t):
     return (C.c_int64 * 4)(*t.stride())
 
@@ -808,7 +802,7 @@ def _mc_ws(dev, dtype, B, M, Cc):
     if need == 0:
         raise L.UnicornHipError("mot_corr_loss: shape B=%d M=%d C=%d is outside the limits of uni_mot_corr_loss_fwd (include/unicorn_hip.h)"
                                 % (B, M, Cc))
-    return torch.empty(need * _MC_ENTRY[dtype][2], device=dev, dtype=torch.uint8)      # the fp64 forms need twice the fp32 size
+    return torch.empty(need * _ws_factor(dtype), device=dev, dtype=torch.uint8)
 
 
 class MotCorrLossFunction(torch.autograd.Function):
@@ -826,11 +820,11 @@ class MotCorrLossFunction(torch.autograd.Function):
         loss = torch.empty((B,), device=embed_0.device, dtype=embed_0.dtype)
         if B == 0 or M == 0:
             return loss.fill_(float("nan"))
-        fwd = _MC_ENTRY[embed_0.dtype][0]
+        fn, fwd = _entry("uni_mot_corr_loss_fwd", embed_0.dtype)
         with torch.cuda.device(embed_0.device):
             ws = _mc_ws(embed_0.device, embed_0.dtype, B, M, Cc)
-            L.check(getattr(L.lib(), fwd)(L.ptr(embed_0), _mc_strides(embed_0), L.ptr(embed_1), _mc_strides(embed_1), L.ptr(targets), B, Cc, H, W, M,
-                                          ctx.s, ctx.flags, L.ptr(loss), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
+            L.check(fn(L.ptr(embed_0), _mc_strides(embed_0), L.ptr(embed_1), _mc_strides(embed_1), L.ptr(targets), B, Cc, H, W, M, ctx.s, ctx.flags,
+                       L.ptr(loss), L.ptr(ws), ws.numel(), L.stream_ptr()), fwd)
         return loss
 
     @staticmethod
@@ -846,13 +840,13 @@ class MotCorrLossFunction(torch.autograd.Function):
         g0 = torch.empty_like(e0) if ctx.needs_input_grad[0] else None
         g1 = torch.empty_like(e1) if ctx.needs_input_grad[1] else None
         if g0 is not None or g1 is not None:
-            bwd = _MC_ENTRY[e0.dtype][1]
+            fn, bwd = _entry("uni_mot_corr_loss_bwd", e0.dtype)
             g = grad_loss.contiguous()
             with torch.cuda.device(e0.device):
                 ws = _mc_ws(e0.device, e0.dtype, B, M, Cc)
-                L.check(getattr(L.lib(), bwd)(L.ptr(e0), _mc_strides(e0), L.ptr(e1), _mc_strides(e1), L.ptr(targets), L.ptr(g), B, Cc, H, W, M,
-                                              ctx.s, ctx.flags, L.ptr(g0), None if g0 is None else _mc_strides(g0), L.ptr(g1),
-                                              None if g1 is None else _mc_strides(g1), L.ptr(ws), ws.numel(), L.stream_ptr()), bwd)
+                L.check(fn(L.ptr(e0), _mc_strides(e0), L.ptr(e1), _mc_strides(e1), L.ptr(targets), L.ptr(g), B, Cc, H, W, M, ctx.s, ctx.flags,
+                           L.ptr(g0), None if g0 is None else _mc_strides(g0), L.ptr(g1), None if g1 is None else _mc_strides(g1), L.ptr(ws),
+                           ws.numel(), L.stream_ptr()), bwd)
         return g0, g1, None, None, None
 
 
@@ -871,7 +865,7 @@ def mot_corr_loss(embed_0, embed_1, targets, s=8, bidirect=True, grid_sample=Tru
             or targets.shape[1] != 2 or targets.shape[3] != 6:
         raise L.UnicornHipError("mot_corr_loss: shapes %s, %s, %s do not fit embed_0 (B,C,H,W), embed_1 (B,C,H,W), targets (B,2,M,6)"
                                 % (tuple(embed_0.shape), tuple(embed_1.shape), tuple(targets.shape)))
-    if embed_0.dtype not in _MC_ENTRY or embed_1.dtype != embed_0.dtype:
+    if embed_0.dtype not in _F64_SFX or embed_1.dtype != embed_0.dtype:
         raise L.UnicornHipError("mot_corr_loss: embedding dtypes %s / %s unsupported (both fp32 or both fp64; no fp16 / autocast input: the "
                                 "reference computes the embeddings under autocast(enabled=False))" % (embed_0.dtype, embed_1.dtype))
     _need_cuda(embed_0, embed_1, targets)
@@ -886,9 +880,6 @@ def mot_corr_loss(embed_0, embed_1, targets, s=8, bidirect=True, grid_sample=Tru
                                 "with C H W < 2^31" % (B, Cc, H, W, M))
     flags = (1 if bidirect else 0) | (2 if grid_sample else 0)
     return MotCorrLossFunction.apply(embed_0, embed_1, targets.detach().float().contiguous(), float(s), flags)
-
-
-_PL_SFX = {torch.float32: "", torch.float64: "_f64"}
 
 
 def _prop_ws(dev, B, Kc, Q):
@@ -909,10 +900,10 @@ def prop_labels(targets, H8, W8, Kc, dtype=torch.float32, masks=None, sot=False)
     gt0 = torch.empty((B, Kc, H8 * W8), device=dev, dtype=dtype)
     gt1 = torch.empty_like(gt0)
     r = 0 if masks is None else masks.shape[3] // H8
-    name = "uni_prop_labels" + _PL_SFX[dtype]
+    fn, name = _entry("uni_prop_labels", dtype)
     with torch.cuda.device(dev):
-        L.check(getattr(L.lib(), name)(L.ptr(targets), L.ptr(masks), 1 if masks is not None and masks.dtype == torch.uint8 else 0, B, M, Kc,
-                                       1 if sot else 0, H8, W8, r, L.ptr(matched), L.ptr(num), L.ptr(gt0), L.ptr(gt1), L.stream_ptr()), name)
+        L.check(fn(L.ptr(targets), L.ptr(masks), 1 if masks is not None and masks.dtype == torch.uint8 else 0, B, M, Kc, 1 if sot else 0, H8, W8, r,
+                   L.ptr(matched), L.ptr(num), L.ptr(gt0), L.ptr(gt1), L.stream_ptr()), name)
     return matched, num, gt0, gt1
 
 
@@ -934,11 +925,11 @@ class PropDiceFunction(torch.autograd.Function):
         p32 = torch.empty((B, Kc, H8 // 4, W8 // 4), device=dev, dtype=dt)
         loss = torch.empty(() if num_matched is None else (B, Kc), device=dev, dtype=dt)
         sums = torch.empty((groups, 3), device=dev, dtype=torch.float64)
-        name = "uni_prop_dice_pyramid_fwd" + _PL_SFX[dt]
+        fn, name = _entry("uni_prop_dice_pyramid_fwd", dt)
         with torch.cuda.device(dev):
             ws = _prop_ws(dev, B, Kc, H8 * W8)
-            L.check(getattr(L.lib(), name)(L.ptr(pred_), L.ptr(gt_), L.ptr(num_matched), B, Kc, H8, W8, L.ptr(p16), L.ptr(p32), L.ptr(loss), L.ptr(sums),
-                                           L.ptr(ws), ws.numel(), L.stream_ptr()), name)
+            L.check(fn(L.ptr(pred_), L.ptr(gt_), L.ptr(num_matched), B, Kc, H8, W8, L.ptr(p16), L.ptr(p32), L.ptr(loss), L.ptr(sums), L.ptr(ws),
+                       ws.numel(), L.stream_ptr()), name)
         ctx.save_for_backward(pred_, gt_, num_matched, sums)
         ctx.set_materialize_grads(False)
         return loss, pred, p16, p32
@@ -952,10 +943,9 @@ class PropDiceFunction(torch.autograd.Function):
         B, Kc, H8, W8 = pred.shape
         gs = [None if g is None else g.contiguous() for g in (g_p8, g_p16, g_p32, g_loss)]
         g_pred = torch.empty_like(pred)                   # written completely by the call
-        name = "uni_prop_dice_pyramid_bwd" + _PL_SFX[pred.dtype]
+        fn, name = _entry("uni_prop_dice_pyramid_bwd", pred.dtype)
         with torch.cuda.device(pred.device):
-            L.check(getattr(L.lib(), name)(L.ptr(pred), L.ptr(gt1), L.ptr(num_matched), L.ptr(sums), *map(L.ptr, gs), B, Kc, H8, W8, L.ptr(g_pred),
-                                           L.stream_ptr()), name)
+            L.check(fn(L.ptr(pred), L.ptr(gt1), L.ptr(num_matched), L.ptr(sums), *map(L.ptr, gs), B, Kc, H8, W8, L.ptr(g_pred), L.stream_ptr()), name)
         return g_pred, None, None
 
 
@@ -975,7 +965,7 @@ def _prop_args(what, embed_0, embed_1, targets, img_size):
     B, Cc, H8, W8 = embed_0.shape
     if H != 8 * H8 or W != 8 * W8 or H8 < 4 or W8 < 4:
         raise L.UnicornHipError("%s: img_size (%d, %d) is not 8 x the %d x %d maps, or a map side is below 4" % (what, H, W, H8, W8))
-    if embed_0.dtype not in _PL_SFX or embed_1.dtype != embed_0.dtype:
+    if embed_0.dtype not in _F64_SFX or embed_1.dtype != embed_0.dtype:
         raise L.UnicornHipError("%s: embedding dtypes %s / %s unsupported (both fp32 or both fp64; no fp16 / autocast input: the reference "
                                 "computes the embeddings under autocast(enabled=False))" % (what, embed_0.dtype, embed_1.dtype))
     if Cc > 128 or (embed_0.dtype == torch.float32 and Cc != 128):
@@ -1052,16 +1042,10 @@ def condinst_masks_resized(mask_feats, up_masks, params, inst_loc, inst_lvl, up_
     """condinst_masks + mask_resize in ONE call (uni_condinst_masks_u8): the CondInst scores of `params` resized by 1/r and pasted into
     (N, H, W) maps -- `> thr` bytes (mot_evaluator.py:804-805) or, with thr=None, fp32 probabilities (unicorn_vos.py:141-152) -- without the
     (N, 1, Hn, Wn) network-size maps ever reaching HBM.  Bit-identical to mask_resize(condinst_masks(...)[:, 0], r, H, W, thr)."""
-    _need_cuda(mask_feats, up_masks, params)
-    mf, um = nhwc(mask_feats), nhwc(up_masks)
-    _, _, H8, W8 = mf.shape
-    p = params.float().contiguous()
-    n = p.shape[0]
+    mf, um, p, loc, lvl, ws = _condinst_inputs(mask_feats, up_masks, params, inst_loc, inst_lvl, up_rate)
+    (_, _, H8, W8), n = mf.shape, p.shape[0]
     out = torch.empty((n, int(H), int(W)), device=mf.device, dtype=torch.float32 if thr is None else torch.uint8)
     if n:
-        loc = inst_loc.float().contiguous().to(mf.device)
-        lvl = inst_lvl.to(device=mf.device, dtype=torch.int32).contiguous()
-        ws = torch.empty(n * H8 * W8 * (1 + up_rate * up_rate), device=mf.device, dtype=torch.float32)
         L.check(L.lib().uni_condinst_masks_u8(L.ptr(mf), L.ptr(um), L.ptr(p), p.shape[1], L.ptr(loc), L.ptr(lvl), n, H8, W8, up_rate, d_rate,
                                               float(r), int(H), int(W), 0.0 if thr is None else float(thr), L.ptr(out) if thr is None else None,
                                               None if thr is None else L.ptr(out), L.ptr(ws), ws.numel() * 4, L.stream_ptr()),
@@ -1086,12 +1070,7 @@ def postprocess_launch(image_pred, num_classes, conf_thre, nms_thre, class_agnos
         raise L.UnicornHipError("postprocess_image: needs a float32 (A, 5+nc) tensor with unit inner stride")
     A, ld = image_pred.shape[0], image_pred.stride(0) if image_pred.shape[0] > 1 else image_pred.shape[1]
     dev = image_pred.device
-    need = L.lib().uni_postprocess_workspace_bytes(A)
-    key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    ws = _post_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), device=dev, dtype=torch.uint8)
-        _post_ws[key] = ws
+    ws = _stream_scratch(_post_ws, dev, L.lib().uni_postprocess_workspace_bytes(A))
     t = PostTicket()
     t.A = A
     t.det = torch.empty((max(A, 1), 7), device=dev, dtype=torch.float32)
@@ -1191,22 +1170,30 @@ def mots_overlap_free(masks):
     return out
 
 
-def rle_encode_launch(masks, max_runs=1 << 14):
-    """enqueue uni_rle_encode + async copies of the string lengths and characters into pinned host memory; -> ticket"""
-    _need_cuda(masks)
-    m = masks.to(torch.uint8).contiguous()
+def _rle_call(m, max_runs):
+    """one uni_rle_encode over (N, H, W) uint8 masks -> (chars (N, max_chars) uint8, lens (N,) int32) on the device; a length < 0 = more than
+    max_runs runs"""
     N, H, W = m.shape
-    if N == 0:
-        return {"N": 0}
     max_chars = 6 * (max_runs + 1)
     ws = torch.empty(L.lib().uni_rle_workspace_bytes(N, H, W, max_runs), device=m.device, dtype=torch.uint8)
     chars = torch.empty((N, max_chars), device=m.device, dtype=torch.uint8)
     lens = torch.empty((N,), device=m.device, dtype=torch.int32)
     L.check(L.lib().uni_rle_encode(L.ptr(m), N, H, W, max_runs, max_chars, L.ptr(chars), L.ptr(lens), None, None, L.ptr(ws),
                                    ws.numel(), L.stream_ptr()), "uni_rle_encode")
+    return chars, lens
+
+
+def rle_encode_launch(masks, max_runs=1 << 14):
+    """enqueue uni_rle_encode + async copies of the string lengths and characters into pinned host memory; -> ticket"""
+    _need_cuda(masks)
+    m = masks.to(torch.uint8).contiguous()
+    N = m.shape[0]
+    if N == 0:
+        return {"N": 0}
+    chars, lens = _rle_call(m, max_runs)
     # the strings of real masks are short (a few hundred characters): the first `head` characters of every row travel with the
     # lengths; a longer string (or an overflow of max_runs, length < 0) is fetched / re-encoded by rle_encode_collect
-    head = min(max_chars, 4096)
+    head = min(chars.shape[1], 4096)
     lens_h = torch.empty((N,), dtype=torch.int32).pin_memory()
     chars_h = torch.empty((N, head), dtype=torch.uint8).pin_memory()
     lens_h.copy_(lens, non_blocking=True)
@@ -1236,16 +1223,11 @@ def rle_encode(masks, max_runs=1 << 14):
     read-back of lengths + chars."""
     _need_cuda(masks)
     m = masks.to(torch.uint8).contiguous()
-    N, H, W = m.shape
+    N = m.shape[0]
     if N == 0:
         return []
     while True:
-        max_chars = 6 * (max_runs + 1)
-        ws = torch.empty(L.lib().uni_rle_workspace_bytes(N, H, W, max_runs), device=m.device, dtype=torch.uint8)
-        chars = torch.empty((N, max_chars), device=m.device, dtype=torch.uint8)
-        lens = torch.empty((N,), device=m.device, dtype=torch.int32)
-        L.check(L.lib().uni_rle_encode(L.ptr(m), N, H, W, max_runs, max_chars, L.ptr(chars), L.ptr(lens), None, None, L.ptr(ws),
-                                       ws.numel(), L.stream_ptr()), "uni_rle_encode")
+        chars, lens = _rle_call(m, max_runs)
         ln = lens.cpu().tolist()
         if min(ln) >= 0:
             break
