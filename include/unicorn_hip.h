@@ -419,6 +419,40 @@ int uni_mot_corr_loss_bwd_f64(const double* embed_0, const int64_t* strides_0, c
                               double* grad_embed_0, const int64_t* grad_strides_0, double* grad_embed_1, const int64_t* grad_strides_1,
                               void* workspace, size_t workspace_bytes, uni_stream_t stream);
 
+/* The opening of a ConvNeXt block for TRAINING (unicorn/models/backbone/convnext.py:32-33,43-45: dwconv = Conv2d(dim, dim, 7, padding=3,
+ * groups=dim), permute to (N, H, W, C), LayerNorm over C with eps inside the square root), forward and recomputing backward for a whole
+ * batch: one launch forward, at most four backward whatever the shape, no host synchronisation, no read-back, no allocation.  Operator
+ * only: the model-level engine stays inference only.
+ *   x, y, grad_y, grad_x  dense [B][H][W][C] (channels-last memory of an (B, C, H, W) tensor)
+ *   weight, grad_weight   [49][C], tap t = ky * 7 + kx: the layout uni_dwconv7_ln_ex takes (the module's (C, 1, 7, 7) transposed)
+ *   bias, ln_weight, ln_bias and their gradients  [C]
+ *   stats                 [B H W][2] = mean and 1 / sqrt(var + eps) of every pixel, written by the forward, read by the backward
+ *   uni_dwln_train_fwd  y = (u - mean) * rstd * ln_weight + ln_bias with u = conv7x7(x, zero padding 3) + bias; the variance is the mean of
+ *                       (u - mean)^2 (two passes over registers).  Writes y and stats COMPLETELY.
+ *   uni_dwln_train_bwd  recomputes u from x, then writes grad_x, grad_weight + grad_bias, grad_ln_weight + grad_ln_bias COMPLETELY.  grad_x,
+ *                       the pair grad_weight / grad_bias and the pair grad_ln_weight / grad_ln_bias may each be NULL: that gradient is not
+ *                       computed (a pair is given or left out as a whole), and the convolution passes over the workspace are skipped when neither
+ *                       grad_x nor grad_weight is wanted.
+ * One writer per element, fixed summation orders (partials of a block in ascending wave order, blocks in ascending order in double), no
+ * float atomics: two calls give the same bits.  A map may be smaller than the window; nothing of a neighbouring image enters a halo.
+ * Limits: B, H, W >= 1, C % 4 == 0, 4 <= C <= 2048, B H W < 2^31 (element offsets are 64-bit), pointers 16-byte aligned; other shapes are
+ * refused with an error string and uni_dwln_train_workspace_bytes returns 0 for them.
+ * workspace (backward only): 16-byte aligned device scratch of >= uni_dwln_train_workspace_bytes(B, H, W, C) bytes (fp32; the _f64 forms need
+ * twice that) = 4 (up(B H W C) + up(2 C RA) + up(50 C RB)), up = round up to 64, RA = min(ceil(B H ceil(W / 2) / NS), 1024) with
+ * NS = 512 / (64 ceil(C / 256)) rounded down, RB = ceil(B H ceil(W / slen) / 4) with slen = ceil(W / ceil(W / 128)): du, the per-block partials of
+ * grad_ln_weight / grad_ln_bias and of grad_weight / grad_bias.  Nothing is kept in it between calls. */
+size_t uni_dwln_train_workspace_bytes(int B, int H, int W, int C);
+int uni_dwln_train_fwd(const float* x, const float* weight, const float* bias, const float* ln_weight, const float* ln_bias, double eps, int B,
+                       int H, int W, int C, float* y, float* stats, uni_stream_t stream);
+int uni_dwln_train_bwd(const float* x, const float* weight, const float* bias, const float* ln_weight, const float* stats, const float* grad_y,
+                       int B, int H, int W, int C, float* grad_x, float* grad_weight, float* grad_bias, float* grad_ln_weight,
+                       float* grad_ln_bias, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_dwln_train_fwd_f64(const double* x, const double* weight, const double* bias, const double* ln_weight, const double* ln_bias, double eps,
+                           int B, int H, int W, int C, double* y, double* stats, uni_stream_t stream);
+int uni_dwln_train_bwd_f64(const double* x, const double* weight, const double* bias, const double* ln_weight, const double* stats,
+                           const double* grad_y, int B, int H, int W, int C, double* grad_x, double* grad_weight, double* grad_bias,
+                           double* grad_ln_weight, double* grad_ln_bias, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+
 /* What stands around the label propagation in the SOT / VOS TRAINING losses (unicorn/models/unicorn.py:315-337 compute_loss_sot, :339-390
  * compute_loss_vos) for a whole BATCH, without a host synchronisation, a read-back or an allocation; the number of launches does not
  * depend on the data.  The propagation itself is uni_corr_softmax_pv_lse / _bwd on the label rows these entries produce.

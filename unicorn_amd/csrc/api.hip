@@ -481,6 +481,23 @@ size_t uni_head_loss_workspace_bytes(int B, int A, int C) { return head_loss_wor
         API(launch_head_loss_bwd<T>(a, grad_out, grad_outputs, ld_grad, grad_origin, S(stream)));                                                  \
     }
 UNI_PAIR(DEF_HEAD_LOSS)
+size_t uni_dwln_train_workspace_bytes(int B, int H, int W, int C) { return dwln_train_workspace_bytes(B, H, W, C); }
+#define DEF_DWLN_TRAIN(SFX, T)                                                                                                                     \
+    int uni_dwln_train_fwd##SFX(const T* x, const T* weight, const T* bias, const T* ln_weight, const T* ln_bias, double eps, int B, int H, int W, \
+                                int C, T* y, T* stats, uni_stream_t stream) {                                                                      \
+        UNI_REQUIRE(x && weight && bias && ln_weight && ln_bias && y && stats, "dwln_train_fwd" #SFX ": NULL argument");                           \
+        const DwlnArgs<T> a{x, weight, bias, ln_weight, ln_bias, eps, B, H, W, C};                                                                 \
+        API(launch_dwln_train_fwd<T>(a, y, stats, S(stream)));                                                                                     \
+    }                                                                                                                                              \
+    int uni_dwln_train_bwd##SFX(const T* x, const T* weight, const T* bias, const T* ln_weight, const T* stats, const T* grad_y, int B, int H,     \
+                                int W, int C, T* grad_x, T* grad_weight, T* grad_bias, T* grad_ln_weight, T* grad_ln_bias, void* workspace,        \
+                                size_t workspace_bytes, uni_stream_t stream) {                                                                     \
+        UNI_REQUIRE(x && weight && bias && ln_weight && stats && grad_y && workspace, "dwln_train_bwd" #SFX ": NULL argument");                    \
+        const DwlnArgs<T> a{x, weight, bias, ln_weight, nullptr, 0.0, B, H, W, C};                                                                 \
+        API(launch_dwln_train_bwd<T>(a, stats, grad_y, grad_x, grad_weight, grad_bias, grad_ln_weight, grad_ln_bias, workspace, workspace_bytes,   \
+                                     S(stream)));                                                                                                  \
+    }
+UNI_PAIR(DEF_DWLN_TRAIN)
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

@@ -329,6 +329,23 @@ int launch_head_mask_loss_fwd(const HMIn<T>& a, T* out, T* sums, void* ws, size_
 template <typename T>
 int launch_head_mask_loss_bwd(const HMIn<T>& a, const T* sums, const T* gout, T* gmf, T* gum, T* gpar, int ldg, void* ws, size_t ws_bytes,
                               hipStream_t s);
+// dwln_train.hip: the opening of a ConvNeXt block for TRAINING (convnext.py:32-33,43-45): y = LN_C(dwconv7x7(x) + bias) * gamma + beta, forward +
+// recomputing backward, fp32 and fp64, one launch forward and at most four backward, no host read-back, no atomics.  x, y, gy, gx dense
+// [B][H][W][C], w [49][C], stats [B H W][2] (mean, rstd) written by the forward for the backward.  The backward writes gx [B][H][W][C], gw [49][C] +
+// gb [C], ggamma [C] + gbeta [C] completely; gx, the pair gw / gb and the pair ggamma / gbeta may each be NULL (not computed).  C % 4 == 0,
+// C <= 2048, B H W < 2^31.  Workspace (backward only): dwln_train_workspace_bytes for fp32, twice that for fp64; scratch between calls.
+size_t dwln_train_workspace_bytes(int B, int H, int W, int C);
+template <typename T>
+struct DwlnArgs {
+    const T *x, *w, *bias, *gamma, *beta;       // beta: forward only
+    double eps;                                 // forward only (the backward reads rstd)
+    int B, H, W, C;
+};
+template <typename T>
+int launch_dwln_train_fwd(const DwlnArgs<T>& a, T* y, T* stats, hipStream_t s);
+template <typename T>
+int launch_dwln_train_bwd(const DwlnArgs<T>& a, const T* stats, const T* gy, T* gx, T* gw, T* gb, T* ggamma, T* gbeta, void* ws, size_t ws_bytes,
+                          hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

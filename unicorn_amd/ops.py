@@ -882,6 +882,115 @@ def mot_corr_loss(embed_0, embed_1, targets, s=8, bidirect=True, grid_sample=Tru
     return MotCorrLossFunction.apply(embed_0, embed_1, targets.detach().float().contiguous(), float(s), flags)
 
 
+DWLN_MAX_C = 2048
+
+
+def _dwln_ws(dev, dtype, N, H, W, Cc):
+    need = L.lib().uni_dwln_train_workspace_bytes(N, H, W, Cc)
+    if need == 0:
+        raise L.UnicornHipError("dwconv7_ln: shape N=%d C=%d H=%d W=%d is outside the limits of uni_dwln_train_bwd (include/unicorn_hip.h)"
+                                % (N, Cc, H, W))
+    return torch.empty(need * _ws_factor(dtype), device=dev, dtype=torch.uint8)
+
+
+class DwConv7LNFunction(torch.autograd.Function):
+    """The opening of a ConvNeXt block (convnext.py:43-45), differentiable in all five tensors:
+    apply(x (N,C,H,W), weight (C,1,7,7), bias, ln_weight, ln_bias (C,), eps) -> y (N,H,W,C) contiguous; device tensors, all fp32 or all fp64
+    (dwconv7_ln checks).  Channels-last memory of x is read in place, any other layout is converted once; grad_x is channels-last.  Saves x, the
+    four parameters and the (N H W, 2) statistics; neither y nor the convolution output.  The backward recomputes the convolution and writes only
+    the gradients autograd asks for.  No host synchronisation in either direction, one writer per gradient element: bitwise reproducible.
+    Under autocast the inputs are cast to fp32 and y is fp32, as F.layer_norm's result is there; grad_x then has the dtype of x."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, weight, bias, ln_weight, ln_bias, eps):
+        N, Cc, H, W = x.shape
+        ctx.dims = (N, Cc, H, W)
+        y = torch.empty((N, H, W, Cc), device=x.device, dtype=x.dtype)
+        if N == 0:
+            ctx.save_for_backward(x, weight, bias, ln_weight, ln_bias)
+            return y
+        xc = x.contiguous(memory_format=torch.channels_last)
+        wt = weight.reshape(Cc, 49).t().contiguous()                      # [49][C], the layout of uni_dwconv7_ln_ex
+        stats = torch.empty((N * H * W, 2), device=x.device, dtype=x.dtype)
+        fn, name = _entry("uni_dwln_train_fwd", x.dtype)
+        with torch.cuda.device(x.device):
+            L.check(fn(L.ptr(xc), L.ptr(wt), L.ptr(bias.contiguous()), L.ptr(ln_weight.contiguous()), L.ptr(ln_bias.contiguous()), float(eps),
+                       N, H, W, Cc, L.ptr(y), L.ptr(stats), L.stream_ptr()), name)
+        ctx.save_for_backward(xc, weight, bias, ln_weight, ln_bias, stats)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y):
+        N, Cc, H, W = ctx.dims
+        need = ctx.needs_input_grad
+        need_x, need_w, need_g = need[0], need[1] or need[2], need[3] or need[4]
+        if N == 0:
+            x, weight, bias, ln_weight, ln_bias = ctx.saved_tensors
+            z = torch.zeros_like
+            return (z(x) if need[0] else None, z(weight) if need[1] else None, z(bias) if need[2] else None, z(ln_weight) if need[3] else None,
+                    z(ln_bias) if need[4] else None, None)
+        xc, weight, bias, ln_weight, ln_bias, stats = ctx.saved_tensors
+        gx = torch.empty_like(xc) if need_x else None                     # channels-last like xc; the call writes it completely
+        gwt = torch.empty((49, Cc), device=xc.device, dtype=xc.dtype) if need_w else None
+        gb = torch.empty_like(bias, memory_format=torch.contiguous_format) if need_w else None
+        gg = torch.empty_like(ln_weight, memory_format=torch.contiguous_format) if need_g else None
+        gbe = torch.empty_like(ln_bias, memory_format=torch.contiguous_format) if need_g else None
+        if need_x or need_w or need_g:
+            fn, name = _entry("uni_dwln_train_bwd", xc.dtype)
+            g = grad_y.contiguous()
+            wt = weight.reshape(Cc, 49).t().contiguous()
+            with torch.cuda.device(xc.device):
+                ws = _dwln_ws(xc.device, xc.dtype, N, H, W, Cc)
+                L.check(fn(L.ptr(xc), L.ptr(wt), L.ptr(bias.contiguous()), L.ptr(ln_weight.contiguous()), L.ptr(stats), L.ptr(g), N, H, W, Cc,
+                           L.ptr(gx), L.ptr(gwt), L.ptr(gb), L.ptr(gg), L.ptr(gbe), L.ptr(ws), ws.numel(), L.stream_ptr()), name)
+        gw = gwt.t().reshape(Cc, 1, 7, 7).contiguous() if need[1] else None
+        return gx, gw, gb if need[2] else None, gg if need[3] else None, gbe if need[4] else None, None
+
+
+def dwconv7_ln(x, weight, bias, ln_weight, ln_bias, eps=1e-6):
+    """`norm(dwconv(x).permute(0, 2, 3, 1))` of a ConvNeXt block (convnext.py:32-33,43-45) as one operator, equal in value and in all five
+    gradients: x (N, C, H, W), weight (C, 1, 7, 7) and bias (C,) of the depthwise Conv2d(C, C, 7, padding=3, groups=C), ln_weight / ln_bias
+    (C,) and eps of the channels-last LayerNorm -> y (N, H, W, C), contiguous.  All tensors fp32, or all fp64 for checks; under
+    torch.autocast("cuda") they are cast to fp32 and y is fp32 (what F.layer_norm returns there), x.grad keeps the dtype of x.  x in
+    channels-last memory is read in place; any other layout (NCHW-contiguous included) is converted ONCE with
+    .contiguous(memory_format=torch.channels_last), and x.grad comes back channels-last.  C % 4 == 0, 4 <= C <= 2048.  Autograd keeps x, the
+    parameters and two numbers per pixel; neither y nor the convolution output.  N == 0 returns an empty tensor without a library call."""
+    names = ("x", "weight", "bias", "ln_weight", "ln_bias")
+    ts = (x, weight, bias, ln_weight, ln_bias)
+    for n, t in zip(names, ts):
+        if not isinstance(t, torch.Tensor):
+            raise L.UnicornHipError("dwconv7_ln: %s is not a tensor" % n)
+    if x.dim() != 4:
+        raise L.UnicornHipError("dwconv7_ln: x of shape %s is not (N, C, H, W)" % (tuple(x.shape),))
+    N, Cc, H, W = x.shape
+    if tuple(weight.shape) != (Cc, 1, 7, 7):
+        raise L.UnicornHipError("dwconv7_ln: weight of shape %s is not the depthwise 7x7 weight (%d, 1, 7, 7) of x's %d channels"
+                                % (tuple(weight.shape), Cc, Cc))
+    for n, t in zip(names[2:], ts[2:]):
+        if tuple(t.shape) != (Cc,):
+            raise L.UnicornHipError("dwconv7_ln: %s of shape %s is not (%d,)" % (n, tuple(t.shape), Cc))
+    if Cc % 4 or not 4 <= Cc <= DWLN_MAX_C:
+        raise L.UnicornHipError("dwconv7_ln: C = %d is outside C %% 4 == 0, 4 <= C <= %d" % (Cc, DWLN_MAX_C))
+    if N and (H == 0 or W == 0 or N * H * W >= 1 << 31):
+        raise L.UnicornHipError("dwconv7_ln: shape N=%d H=%d W=%d is outside a non-empty map with N H W < 2^31" % (N, H, W))
+    if not float(eps) > 0:
+        raise L.UnicornHipError("dwconv7_ln: eps = %r is not positive" % (eps,))
+    autocast = x.is_cuda and torch.is_autocast_enabled("cuda")
+    if autocast:
+        if not all(t.is_floating_point() for t in ts):
+            raise L.UnicornHipError("dwconv7_ln: dtypes %s: floating-point tensors are needed" % ", ".join(str(t.dtype) for t in ts))
+    elif x.dtype not in _F64_SFX or any(t.dtype != x.dtype for t in ts):
+        raise L.UnicornHipError("dwconv7_ln: dtypes %s unsupported (all fp32 or all fp64; half inputs only under torch.autocast)"
+                                % ", ".join(str(t.dtype) for t in ts))
+    _need_cuda(*ts)
+    if len({t.device for t in ts}) != 1:
+        raise L.UnicornHipError("dwconv7_ln: tensors on different devices")
+    return DwConv7LNFunction.apply(x, weight, bias, ln_weight, ln_bias, float(eps))
+
+
 def _prop_ws(dev, B, Kc, Q):
     need = L.lib().uni_prop_workspace_bytes(B, Kc, Q)
     if need == 0:
