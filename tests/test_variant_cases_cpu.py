@@ -21,7 +21,6 @@ def test_every_case_names_a_declared_entry_point_and_a_reference():
     for c in vc.CASE_LIST:
         assert c["entry"] in PROTOS, (c["tag"], c["entry"])
         assert c["ref"] and "fp64" in c["ref"], c["tag"]
-        assert isinstance(c["env"], dict) and all(k.startswith("UNI_") for k in c["env"]), c["tag"]
 
 
 def test_every_bound_is_restated_from_an_existing_test():

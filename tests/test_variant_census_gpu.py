@@ -6,18 +6,9 @@ answer into checks:
      (tests/guard.py results_dir, where parity_metrics.json goes);
   3. one kernel-level parity case per tag (tests/variant_cases.py CASES): the traced call must emit the tag -- the shape really reaches the
      variant -- and match its fp64 CPU reference under the bound restated from the existing parity tables;
-  4. closure: every census tag has a case or is one of the context-only launchers of CTX_ONLY.
-Cases that need an environment switch (read once per process) run in a fresh child process: `python tests/test_variant_census_gpu.py TAG`."""
+  4. closure: every census tag has a case or is one of the context-only launchers of CTX_ONLY."""
 import json
 import os
-import subprocess
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if __name__ == "__main__":
-    for p in (ROOT, os.path.join(ROOT, "oracle")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
 
 import pytest
 import torch
@@ -562,16 +553,4 @@ def test_census_closure_every_dispatched_variant_has_a_parity_case(census):
 # ------------------------------------------------------------------------------------------------ 3. one parity case per tag
 @pytest.mark.parametrize("tag", sorted(vc.CASES))
 def test_case_reaches_its_variant_and_matches_fp64(L, tag):
-    case = vc.CASES[tag]
-    if not case["env"]:
-        run_case(L, tag)
-        return
-    # the switch is read once per process: a fresh child, under its own time limit
-    cp = subprocess.run([sys.executable, os.path.abspath(__file__), tag], env=dict(os.environ, **case["env"]), cwd=ROOT, capture_output=True, text=True,
-                        timeout=120)
-    print(cp.stdout[-4000:])
-    assert cp.returncode == 0, (cp.returncode, cp.stdout[-2000:], cp.stderr[-4000:])
-
-
-if __name__ == "__main__":
-    run_case(_lib(), sys.argv[1])
+    run_case(L, tag)

@@ -34,15 +34,15 @@ B_H2_ROWS = 2e-5                                    # f16x2 operand rows decoded
 B_BF16_ROWS = 8e-3                                  # bf16 operand rows: test_layernorm
 
 
-def _dw(kernel, C, B, H, W, fmt, env=None):
+def _dw(kernel, C, B, H, W, fmt):
     f = ("bf16", "f32", "h2")[fmt]
     return dict(tag="dwconv7_ln %s fmt=%s batched=%d" % (kernel, f, B > 1), entry="uni_dwconv7_ln_ex", args=dict(C=C, B=B, H=H, W=W, fmt=fmt),
-                env=env or {}, ref="torch fp64: F.conv2d(groups=C, padding=3) + F.layer_norm", bound=B_DWLN[fmt],
+                ref="torch fp64: F.conv2d(groups=C, padding=3) + F.layer_norm", bound=B_DWLN[fmt],
                 bound_from="test_dwconv7_ln_batched_all_formats")
 
 
 def _lnb(C, rows, nw, pack):
-    return "lnb<C=%d,ROWS=%d,DBG=0,NW=%d,PACK=%d>" % (C, rows, nw, pack)
+    return "lnb<C=%d,ROWS=%d,NW=%d,PACK=%d>" % (C, rows, nw, pack)
 
 
 def _ln(mode, C, fmt, outF, outB, **kw):
@@ -52,7 +52,7 @@ def _ln(mode, C, fmt, outF, outB, **kw):
     tag = "layernorm NI=%d fmt=%s ps=%d pair=%d outF=%d outB=%d" % (ni, f, mode == "ps", mode == "pair", outF, outB)
     ref = {"rows": "torch fp64: F.layer_norm", "ps": "torch fp64: F.pixel_shuffle(F.layer_norm, 2)",
            "pair": "torch fp64: F.layer_norm, odd frames of [B][2][hw] tokens -> second output"}[mode]
-    return dict(tag=tag, entry="uni_layernorm_ex", args=dict(mode=mode, C=C, fmt=fmt, outF=outF, outB=outB, **kw), env={}, ref=ref,
+    return dict(tag=tag, entry="uni_layernorm_ex", args=dict(mode=mode, C=C, fmt=fmt, outF=outF, outB=outB, **kw), ref=ref,
                 bound={0: B_BF16_ROWS, 1: B_LN_F32, 2: B_H2_ROWS}[fmt], bound_from="test_layernorm" if fmt != 2 else "test_dwconv7_ln_batched_all_formats")
 
 
@@ -62,7 +62,7 @@ def _gn(C, G, act, B, M, fmt, prior=False, up_w=0, outF=False, outB=False, ldu=0
     tag = "gn_apply ACT=%d FAST=%d fmt=%s batched=%d prior=%d outUp=%d outF=%d outB=%d" % (
         act_t, fmt != 1 and act_t >= 0, f, B > 1, prior, up_w > 0, outF, outB)
     return dict(tag=tag, entry="uni_groupnorm_act_ex", args=dict(C=C, G=G, act=act, B=B, M=M, fmt=fmt, prior=prior, up_w=up_w, outF=outF, outB=outB, ldu=ldu),
-                env={}, ref="torch fp64: per-sample F.group_norm + activation (+ prior[m] * prior_beta[c])",
+                ref="torch fp64: per-sample F.group_norm + activation (+ prior[m] * prior_beta[c])",
                 bound=bound if bound is not None else {0: B_BF16_ROWS, 1: B_GN_F32, 2: B_H2_ROWS}[fmt],
                 bound_from={0: "test_layernorm", 1: "test_groupnorm_act", 2: "test_dwconv7_ln_batched_all_formats"}[fmt])
 
@@ -193,7 +193,7 @@ def _gemm(fam, kernel, code, force, conv, stats, splitk, outF, outB, res, act, b
     return dict(tag=tag, entry="uni_gemm_ex" if fam == "f32" or win else "uni_gemm_h2",
                 args=dict(fam=fam, geo=geo, act=act, act_col0=win, bias=bias and not stats, res=bool(res), G=16 if stats else 0, outF=bool(outF), outB=bool(outB),
                           cfg=force + (2000000 if splitk else 0)),
-                env={}, ref="torch fp64: F.conv2d of the unrounded fp32 operands + activation + residual", bound=B_GEMM, bound_from="test_gemm_h2")
+                ref="torch fp64: F.conv2d of the unrounded fp32 operands + activation + residual", bound=B_GEMM, bound_from="test_gemm_h2")
 
 
 def _reduce(bias, res, stats, conv):
@@ -239,7 +239,7 @@ CASE_LIST += [_gemm("h2", "h2d", 22224, 322, 0, 0, 0, 1, 0, 0, 0)]
 
 # ---------------------------------------------------------------------------------------------------------------- the rest
 def _simple(tag, entry, args, ref, bound, bound_from):
-    return dict(tag=tag, entry=entry, args=args, env={}, ref=ref, bound=bound, bound_from=bound_from)
+    return dict(tag=tag, entry=entry, args=args, ref=ref, bound=bound, bound_from=bound_from)
 
 
 B_CORR = 2e-5       # absolute, test_corr_softmax_pv
@@ -270,23 +270,14 @@ CASE_LIST += [
     _simple("condinst final=1", "uni_condinst_masks", dict(n=5, H8=20, W8=28), "oracle fp64: aligned_bilinear(dynamic_mask_head)", 2e-5, "test_condinst_masks"),
 ]
 
-# ---------------------------------------------------------------------------------------------------------------- shadowed instantiations
-# Built and reachable only through a documented A/B switch (read once per process: these cases run in a fresh child process) or at a width no
-# model configuration has (C = 512).  No census workload dispatches them: they are listed under not_dispatched in variant_census.json.
+# ---------------------------------------------------------------------------------------------------------------- not dispatched by the census
+# Builds no census workload reaches (listed under not_dispatched in variant_census.json): the unpacked 12-wave C = 384 build needs a map with
+# enough strips but too few strip groups, and no model configuration has C = 512.
 CASE_LIST += [
-    _dw(_lnb(768, 2, 8, 0), 768, 3, 49, 83, 2, env={"UNI_DW_W12": "0"}),                           # 8 waves, shadowed by the 12-wave build
-    _dw(_lnb(384, 2, 8, 0), 384, 3, 93, 163, 2, env={"UNI_DW_W12": "0", "UNI_DW_PACK": "0"}),      # 8 waves, shadowed by the packed and the 12-wave builds
-    _dw(_lnb(384, 2, 12, 0), 384, 3, 93, 163, 2, env={"UNI_DW_PACK": "0"}),                        # 12 waves unpacked, shadowed by the packed build
-    _dw(_lnb(192, 2, 12, 0), 192, 3, 171, 163, 2, env={"UNI_DW_W12": "2", "UNI_DW_PACK": "0"}),    # 12 waves for C = 192 (UNI_DW_W12=2)
-    _dw(_lnb(192, 2, 6, 1), 192, 3, 171, 163, 2, env={"UNI_DW_PACK_NW": "6"}),                     # packed lanes on 6 / 9 waves (12 is the default)
-    _dw(_lnb(192, 2, 9, 1), 192, 3, 171, 163, 2, env={"UNI_DW_PACK_NW": "9"}),
-    _dw(_lnb(384, 2, 6, 1), 384, 3, 93, 163, 2, env={"UNI_DW_PACK_NW": "6"}),
-    _dw(_lnb(384, 2, 9, 1), 384, 3, 93, 163, 2, env={"UNI_DW_PACK_NW": "9"}),
-    _dw(_lnb(192, 4, 8, 0), 192, 6, 99, 163, 2, env={"UNI_DW_ROWS": "4"}),                         # 4-row strips where 2 rows are the default
-    _dw(_lnb(384, 4, 8, 0), 384, 3, 99, 163, 2, env={"UNI_DW_ROWS": "4"}),
-    _dw(_lnb(768, 4, 8, 0), 768, 6, 49, 83, 2, env={"UNI_DW_ROWS": "4"}),
-    _dw(_lnb(512, 4, 8, 0), 512, 3, 99, 163, 2),                                                   # C = 512: 1575 4-row strips >= 384 x 4
-    _dw(_lnb(512, 2, 8, 0), 512, 2, 99, 163, 2),                                                   # 1050 4-row strips < 1533 <= 2100 2-row strips
+    # n8 = 21 x 93 x 2 x 96 = 374976; 21 x 47 x 2 = 1974 strips, cdiv(1974, 4) = 494 >= 384; 11 x 47 x 2 = 1034 groups, cdiv(1034, 4) = 259 < 384 -> not packed
+    _dw(_lnb(384, 2, 12, 0), 384, 2, 93, 163, 2),
+    _dw(_lnb(512, 4, 8, 0), 512, 3, 99, 163, 2),        # C = 512: 1575 4-row strips >= 384 x 4
+    _dw(_lnb(512, 2, 8, 0), 512, 2, 99, 163, 2),        # 1050 4-row strips < 1533 <= 2100 2-row strips
 ]
 
 CASES = {c["tag"]: c for c in CASE_LIST}

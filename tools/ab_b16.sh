@@ -4,13 +4,9 @@ run X=base
 run UNI_NO_H2D_192=1
 run UNI_MLP_LAYOUT=0
 run X=base
-run UNI_DW_W12=0
-run UNI_DW_PACK=0
 run UNI_NO_FORK=1
 run X=base
 run UNI_NO_FORK_MB=1
-run UNI_GN_PER=2
-run UNI_GN_PER=8
 run X=base
 run UNI_BENCH_CORR_PER_FRAME=1
 run UNI_NO_MLP_FUSED=1

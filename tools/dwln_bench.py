@@ -1,5 +1,5 @@
 """The fused depthwise 7x7 + LayerNorm kernels alone on the ConvNeXt / head maps of the large model at B frames, in the engine's operand
-format (FMT: 2 = f16x2 default, 0 = bf16, 1 = fp32).  UNI_DW_NOLDSW=1 selects the non-persistent kernels, UNI_DW_PX / UNI_DW_ROWS the tiling."""
+format (FMT: 2 = f16x2 default, 0 = bf16, 1 = fp32; SHAPES = CxHxW list).  The launcher picks the kernel by shape alone (csrc/norm.hip launch_dwconv7_ln)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

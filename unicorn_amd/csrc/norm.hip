@@ -6,7 +6,6 @@
 // All statistics in fp32 with a two-pass (mean, then centred variance) reduction; deterministic
 // (no float atomics).  NHWC everywhere so a wave's lanes walk the channel axis (coalesced 16-B accesses).
 #include "kernels.h"
-#include <cstdlib>
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm: one wave per row, the row lives in registers (C <= 1536 -> <= 6 float4 per lane)
@@ -183,11 +182,10 @@ int launch_gn_apply(const GnApplyArgs& a, hipStream_t s) {
     // then stream several rows: ~4 float4-pairs per thread (measured best of 1 / 4 / 8 / 16), at least ~8 blocks per CU over the whole batch
     const long total = (long)a.M * (a.C / 8);
     const int nb = a.B > 0 ? a.B : 1;
-    static const int per = getenv("UNI_GN_PER") ? atoi(getenv("UNI_GN_PER")) : 4;
-    long grid = (total + 256L * per - 1) / (256L * per);
-    static const int mg_env = getenv("UNI_GN_MINGRID") ? atoi(getenv("UNI_GN_MINGRID")) : 0;
+    constexpr int kGnPairsPerThread = 4;                         // measured best of 1 / 4 / 8 / 16 (2 / 8 again at 16 frames: profiles/r06_ab_b16_env_switches.txt)
+    long grid = (total + 256L * kGnPairsPerThread - 1) / (256L * kGnPairsPerThread);
     // (one frame per call: 1024 instead of 2048 blocks -- every block pays the fp64 prologue -- 0.585 -> 0.552 ms over the 61 launches of a frame)
-    const long min_grid = ((mg_env > 0 ? mg_env : (nb == 1 ? 1024 : 2048)) + nb - 1) / nb;
+    const long min_grid = ((nb == 1 ? 1024 : 2048) + nb - 1) / nb;
     if (grid < min_grid) grid = min_grid < (total + 255) / 256 ? min_grid : (total + 255) / 256;
     if (grid > 2048) grid = 2048;
     {   // gridDim.x * 256 must be a multiple of C / 8 (a thread keeps its channel group): round the grid up to a multiple of C8 / gcd(C8, 256)
@@ -504,8 +502,6 @@ __global__ __launch_bounds__(384) void dwconv7_ln2_kernel(DwLnArgs p, int S, int
 //   * LayerNorm sums reduced inside the waves (reduce-scatter butterfly: 17 shuffles for the 16 pixels), 64 B of scratch per wave.
 // ROWS = 4 output rows per thread: the measured bound of these kernels is the L2 -> CU load path (~22-25 B/clk/CU, the same figure
 // the GEMM's LDS-DMA sees), and 10 input rows for 4 output rows is 4.4 input float4s per output float4 instead of 7.
-// DBG (tools/dwln_bench.py with UNI_DW_DBG, C = 768 / ROWS = 2 only): ablation builds -- 1 no input loads, 2 no LayerNorm reductions
-// (local statistics), 4 no output stores, 8 no FMAs.  DBG = 0 is the kernel the engine runs.
 // NW = 12 (ROWS = 2, round 4): twelve waves per block = THREE per SIMD (<= 168 registers: one 7-tap buffer re-read in place instead of the tap double
 // buffer).  A PMC pass showed the 8-wave kernel at C = 768 as 6 waves on 4 SIMDs (two SIMDs 52 % VALU-busy, two 26 %) with 43 % of the wave cycles waiting.
 // PACK (C = 384 / 192, round 4): CG = 96 / 48 channel groups leave a quarter of the lanes of a strip's waves idle.  Packed, TWO (C = 384) or FOUR
@@ -514,20 +510,35 @@ __global__ __launch_bounds__(384) void dwconv7_ln2_kernel(DwLnArgs p, int S, int
 // buffer offset (descriptor base AT the first pixel, so the range check drops whatever lies past the row end; at the left image edge the base sits
 // on the second strip's pixel and the first strip's lanes carry a negative = out-of-range offset).  The LayerNorm sums are reduce-scattered inside
 // 32- / 16-lane granules (three granules per strip, like the three waves of a C = 768 strip).  S / spr / nstrips then count strip GROUPS.
-template <int C, int ROWS, int DBG = 0, int NW = 8, bool PACK = false>            // C compile-time: the tap offsets become instruction immediates
-__global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S, int spr, int nstrips) {
-    constexpr int PX = 8, IN = PX + 6, CG = C / 4;
+// The compile-time geometry of one build, stated once for the kernel and for its launcher (launch_lnb).  A "unit" is what S / spr / nstrips count:
+// a strip, or (PACK) a strip group.
+template <int C, int NW, bool PACK>
+struct LnbGeom {
+    static constexpr int CG = C / 4;                                 // channel groups (float4s) of a pixel
     static_assert(!PACK || CG == 96 || CG == 48, "packed lanes: C = 384 / 192");
-    constexpr int G = !PACK ? 64 : (CG % 32 == 0 ? 32 : 16);    // lanes of a reduction granule
+    static constexpr int G = !PACK ? 64 : (CG % 32 == 0 ? 32 : 16);  // lanes of a reduction granule
+    static constexpr int NSLOT = NW * 64 / G;                        // granules of a block
+    static constexpr int WPS = PACK ? 3 : (CG + 63) >> 6;            // waves per unit; unpacked, C = 192 / 384 leave the lanes past CG idle
+    static constexpr int SPG = PACK ? 192 / CG : 1;                  // strips per unit
+    static constexpr int UNITS = NW / WPS;                           // units per block (the kernel's S)
+    static constexpr int THREADS = NW * 64;
+    static_assert(UNITS * WPS == NW, "a block is a whole number of units");
+    static constexpr int LDS_BYTES = 49 * C * 4 + 2 * NSLOT * 16 * 4;      // [49][C] taps + [2][NSLOT][16] LayerNorm scratch
+};
+
+template <int C, int ROWS, int NW, bool PACK>                     // C compile-time: the tap offsets become instruction immediates
+__global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S, int spr, int nstrips) {
+    using Geo = LnbGeom<C, NW, PACK>;
+    constexpr int PX = 8, IN = PX + 6, CG = Geo::CG;
+    constexpr int G = Geo::G, NSLOT = Geo::NSLOT;
     constexpr int LG = G == 64 ? 2 : G == 32 ? 1 : 0;            // lane bits below the four reduce-scatter bits
-    constexpr int NSLOT = NW * 64 / G;                           // granules of a block
     extern __shared__ float lds[];
     float* wl = lds;                                             // [49][C]
     float* red = lds + 49 * C;                                   // [2][waves][16]
     const int tid = threadIdx.x;
     for (int u = tid; u < 49 * C / 4; u += blockDim.x) reinterpret_cast<f32x4*>(wl)[u] = reinterpret_cast<const f32x4*>(p.w)[u];
     __syncthreads();
-    constexpr int wps = PACK ? 3 : (CG + 63) >> 6;               // waves per strip (group); unpacked, C = 192 / 384 leave the lanes past CG idle
+    constexpr int wps = Geo::WPS;                                // waves per strip (group)
     constexpr int NGS = PACK ? CG / G : wps;                     // granules per strip
     const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int sl = wv / wps, fl = (wv - sl * wps) * 64 + lane;
@@ -605,7 +616,7 @@ __global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S,
         const int strip = (first + it * step) * S + sl;          // wave-uniform
         const bool active = sl < S && strip < nstrips;
         const int yg = active ? strip / spr : 0;
-        const int x0 = active ? (strip - yg * spr) * PX * (PACK ? 192 / CG : 1) : 0;
+        const int x0 = active ? (strip - yg * spr) * PX * Geo::SPG : 0;
         const int sb = yg / HP, y = (yg - sb * HP) * ROWS;       // sample, first of the output rows
         const size_t img0 = (size_t)sb * p.H * p.W;
         f32x4 acc[ROWS][PX];
@@ -671,7 +682,7 @@ __global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S,
                 }
                 auto pair = [&](f32x4 (&a)[PX], int ky, int nk) __attribute__((always_inline)) {
                     const float* wn = wl + (min(max(nk, 0), 6) * 7) * C + cg * 4;
-                    if (!(DBG & 8) && ky >= 0 && ky < 7) {           // wave-uniform
+                    if (ky >= 0 && ky < 7) {                         // wave-uniform
 #pragma unroll
                         for (int kx = 0; kx < 7; ++kx) {
 #pragma unroll
@@ -694,22 +705,18 @@ __global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S,
             } else {
             f32x4 ra[IN], wa[7], wb[7];
             ld_w(wa, 0);                                         // pair (r = 0, q = 0): tap row 0
-            if (DBG & 1) {
-#pragma unroll
-                for (int j = 0; j < IN; ++j) ra[j] = f32x4{1.f, 2.f, 3.f, 4.f};
-            }
 #pragma unroll 1
             for (int r = 0; r < 6 + ROWS; ++r) {                 // input row y-3+r feeds output row y+q with tap row ky = r - q
-                if (!(DBG & 1)) load_row(ra, y - 3 + r);
+                load_row(ra, y - 3 + r);
 #pragma unroll
                 for (int q = 0; q < ROWS; q += 2) {
                     ld_w(wb, r - (q + 1));                       // next pair: (r, q + 1)
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!(DBG & 8) && r - q >= 0 && r - q < 7) mac(acc[q], wa, ra);
+                    if (r - q >= 0 && r - q < 7) mac(acc[q], wa, ra);
                     __builtin_amdgcn_sched_barrier(0);
                     ld_w(wa, q + 2 < ROWS ? r - (q + 2) : r + 1); // (r, q + 2), or (r + 1, 0)
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!(DBG & 8) && r - q - 1 >= 0 && r - q - 1 < 7) mac(acc[q + 1], wb, ra);
+                    if (r - q - 1 >= 0 && r - q - 1 < 7) mac(acc[q + 1], wb, ra);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -725,7 +732,7 @@ __global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S,
                 const f32x4 v = acc[2 * h + (u >> 3)][u & 7];
                 part[u] = lane_ok ? v[0] + v[1] + v[2] + v[3] : 0.f;
             }
-            if (DBG & 2) { for (int u = 0; u < 16; ++u) tot[u] = part[u] * (float)CG; } else reduce16(part, tot, 0);
+            reduce16(part, tot, 0);
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 const float m = tot[u] * invC;
@@ -734,11 +741,11 @@ __global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S,
                 const float a = v[0] - m, b = v[1] - m, c = v[2] - m, d = v[3] - m;
                 part[u] = lane_ok ? a * a + b * b + c * c + d * d : 0.f;
             }
-            if (DBG & 2) { for (int u = 0; u < 16; ++u) tot[u] = part[u] * (float)CG; } else reduce16(part, tot, 1);
+            reduce16(part, tot, 1);
 #pragma unroll
             for (int u = 0; u < 16; ++u) rstd[2 * h + (u >> 3)][u & 7] = rsqrtf(tot[u] * invC + p.eps);
         }
-        if (active && lane_ok && !((DBG & 4) && p.eps > 0.f)) {       // (DBG 4: the results stay live through the runtime eps test, nothing is stored)
+        if (active && lane_ok) {
             // 16-byte stores: a lane owns 4 channels = 8 bytes of hi + 8 of lo (f16x2) or 8 bytes of bf16, and 8-byte stores are
             // store-issue bound (32 per thread and tile).  Lane pairs (cg, cg ^ 1; CG is even) swap halves through DPP: f16x2 --
             // the even lane writes the 16 hi bytes of the 8-channel group, the odd lane the 16 lo bytes; bf16 -- the even lane writes
@@ -965,113 +972,84 @@ __global__ __launch_bounds__(C) void dwconv7_lns_kernel(DwLnArgs p, int spr, int
     }
 }
 
+// One build of the persistent kernel: opts it into its LDS (once per device), emits its tag and launches it with the block and the LDS of its
+// LnbGeom.  Which build runs where is decided by the chooser below; this function holds no policy.
+template <int C, int ROWS, int NW, bool PACK>
+static int launch_lnb(const DwLnArgs& a, int nb, hipStream_t s) {
+    using Geo = LnbGeom<C, NW, PACK>;
+    auto* kernel = &dwconv7_lnb_kernel<C, ROWS, NW, PACK>;
+    const int upr = cdiv(cdiv(a.W, 8), Geo::SPG), units = upr * cdiv(a.H, ROWS) * nb;      // strips (PACK: strip groups) per row of strips, of the call
+    static DevOnce once;
+    UNI_LDS_OPTIN(once, "dwconv7_lnb", 163840, reinterpret_cast<const void*>(kernel));
+    uni_variant_note("dwconv7_ln lnb<C=%d,ROWS=%d,NW=%d,PACK=%d> fmt=%s batched=%d", C, ROWS, NW, (int)PACK, uni_fmt_name(a.b32), nb > 1);
+    hipLaunchKernelGGL(kernel, dim3(256), dim3(Geo::THREADS), Geo::LDS_BYTES, s, a, Geo::UNITS, upr, units);
+    return 0;
+}
+
 int launch_dwconv7_ln(const DwLnArgs& a, hipStream_t s) {
     UNI_REQUIRE(a.C % 4 == 0 && a.C / 4 <= 512, "dwconv7_ln: C=%d unsupported", a.C);
     const int CG = a.C / 4;
-    int S = 256 / CG;
-    if (S < 1) S = 1;
-    const int T = cdiv(S * CG, 64) * 64;
+    const int nb = a.B > 0 ? a.B : 1;
+    const int spr = cdiv(a.W, 8);
     // variant by the thread count n8 of the 8-px single-row tiling (measured crossovers, tools/norm_bench.py):
     // n8 >= 150k -> 2 rows x 8 px, >= 70k -> 8 px, else 4 px (more, smaller threads to fill the 256 CUs)
-    static const char* env = getenv("UNI_DW_PX");
-    const int nb = a.B > 0 ? a.B : 1;
-    const long n8 = (long)cdiv(a.W, 8) * a.H * nb * CG;
-    int px = n8 >= 150000L ? 16 : n8 >= 70000L ? 8 : 4;
-    if (env) px = atoi(env);
-    // one frame per call, C = 768: the row-split kernel (above) while the map is at most ONE round of one-strip blocks; UNI_DW_SPLIT=0 = A/B switch
-    static const int split_env = getenv("UNI_DW_SPLIT") ? atoi(getenv("UNI_DW_SPLIT")) : 1;
-    if (split_env && !env && a.C == 768 && (long)a.W * a.C * 4 < (1L << 30)) {
-        const int spr = cdiv(a.W, 8), nst = spr * cdiv(a.H, 2) * nb;
-        if (nst <= 256 || split_env == 2) {      // one round of blocks (242 vs 148 us at 16 frames, 31 us at two)      // (UNI_DW_SPLIT=2: every map -- the 16-frame experiment of profiles/r06_dwconv_b1_rowsplit.txt)
+    const long n8 = (long)spr * a.H * nb * CG;
+    const int px = n8 >= 150000L ? 16 : n8 >= 70000L ? 8 : 4;
+    // lns / lnb read rows through buffer descriptors: a row must be shorter than 2 GiB / 4.
+    if ((long)a.W * a.C * 4 < (1L << 30)) {
+        const int st2 = spr * cdiv(a.H, 2) * nb;                 // strips of 2 rows x 8 px
+        // one frame per call, C = 768: the row-split kernel (above) while the map is at most ONE round of one-strip blocks (242 vs 148 us at 16
+        // frames, 31 us at two; all maps at 16 frames: profiles/r06_dwconv_b1_rowsplit.txt)
+        if (a.C == 768 && st2 <= 256) {
             constexpr int ldsb = 3 * 16 * 192 * 16 + 2 * 3 * 16 * 4;
             static DevOnce once;
             UNI_LDS_OPTIN(once, "dwconv7_lns", ldsb, reinterpret_cast<const void*>(&dwconv7_lns_kernel<768>));
             uni_variant_note("dwconv7_ln lns<768> fmt=%s batched=%d", uni_fmt_name(a.b32), nb > 1);
-            hipLaunchKernelGGL((dwconv7_lns_kernel<768>), dim3(nst), dim3(768), ldsb, s, a, spr, nst);
+            hipLaunchKernelGGL((dwconv7_lns_kernel<768>), dim3(st2), dim3(768), ldsb, s, a, spr, st2);
             return 0;
         }
-    }
-    if (px == 16) {
-        const int spr = cdiv(a.W, 8), nstrips = spr * ((a.H + 1) / 2) * nb;
-        // persistent variant (row descriptors, register double buffer, weights in LDS): C a multiple of 256, 49 C floats + scratch
-        // within 160 KB, at least two rounds of work for 256 CUs and a row shorter than 2 GiB / 4
-        static const bool no_b = getenv("UNI_DW_NOLDSW") != nullptr;
-        if (!no_b && (long)a.W * a.C * 4 < (1L << 30) && (a.C == 192 || a.C == 256 || a.C == 384 || a.C == 512 || a.C == 768)) {
-            // output rows per thread: 4 (4.4 input float4s per output float4 instead of 7) where the 128 accumulators leave the
-            // other registers unspilled (C = 256 / 512: one wave per strip), else 2 (tools/dwln_bench.py)
-            static const int rows_env = getenv("UNI_DW_ROWS") ? atoi(getenv("UNI_DW_ROWS")) : 0;
-            int rows = rows_env == 2 || rows_env == 4 ? rows_env : (a.C == 256 || a.C == 512 ? 4 : 2);
-            const int wps = cdiv(CG, 64), Sw = 8 / wps;          // 512 threads: 8 waves
-            const size_t ldsw = (size_t)49 * a.C * 4 + (size_t)2 * 8 * 16 * 4;
-            // a map with too few 4-row strips for 1.5 rounds of blocks (the 50 x 80 head level at 16 frames) still fills them with 2-row strips
-            if (!rows_env && rows == 4 && cdiv(spr * cdiv(a.H, 4) * nb, Sw) < 384) rows = 2;
-            const int nst = spr * cdiv(a.H, rows) * nb;
-            if (cdiv(nst, Sw) >= 384) {
-                static DevOnce attr_once;
-#define DWB_ALL(F) F(192, 2) F(256, 2) F(384, 2) F(512, 2) F(768, 2) F(192, 4) F(256, 4) F(384, 4) F(512, 4) F(768, 4)
-#define DWB_ATTR(CC, RR) reinterpret_cast<const void*>(&dwconv7_lnb_kernel<CC, RR>),
-                UNI_LDS_OPTIN(attr_once, "dwconv7_lnb", 163840, DWB_ALL(DWB_ATTR) reinterpret_cast<const void*>(&dwconv7_lnb_kernel<768, 2>));
-#undef DWB_ATTR
-                const dim3 grid(256), block(Sw * wps * 64);
-                static const int dbg = getenv("UNI_DW_DBG") ? atoi(getenv("UNI_DW_DBG")) : 0;      // ablation builds of the stage-2 kernel (tools/dwln_bench.py)
-                if (dbg && a.C == 768 && rows == 2) {
-#define DWB_DBG(D) if (dbg == D) { static DevOnce once; UNI_LDS_OPTIN(once, "dwconv7_lnb (ablation)", 163840, reinterpret_cast<const void*>(&dwconv7_lnb_kernel<768, 2, D>)); \
-                                   uni_variant_note("dwconv7_ln lnb<C=768,ROWS=2,DBG=%d,NW=8,PACK=0> fmt=%s batched=%d", D, uni_fmt_name(a.b32), nb > 1); \
-                                   hipLaunchKernelGGL((dwconv7_lnb_kernel<768, 2, D>), grid, block, ldsw, s, a, Sw, spr, nst); return 0; }
-                    DWB_DBG(1) DWB_DBG(2) DWB_DBG(4) DWB_DBG(8) DWB_DBG(3) DWB_DBG(9) DWB_DBG(15)
-#undef DWB_DBG
-                }
-                // packed lanes for C = 384 / 192 (two / four strips side by side fill three waves; see the kernel's header).  UNI_DW_PACK = 0 / 1 (A/B
-                // switch), UNI_DW_PACK_NW = 6 / 9 / 12 waves per block (default per C below)
-                static const int pack = getenv("UNI_DW_PACK") ? atoi(getenv("UNI_DW_PACK")) : 1;
-                if (pack && rows == 2 && (a.C == 384 || a.C == 192)) {
-                    static const int nw_env = getenv("UNI_DW_PACK_NW") ? atoi(getenv("UNI_DW_PACK_NW")) : 0;
-                    const int sps = 192 / CG, sprg = cdiv(spr, sps), nstg = sprg * cdiv(a.H, rows) * nb;
-                    // 12 waves (four groups per block: 602 -> 528 us / 298 -> 265 us on the stage-0 / stage-1 maps at 16 frames; 9 waves 559 / 276, 6 waves
-                    // 579 / 292).  One frame of the stage-0 map has too few groups for 12-wave blocks and measured 1 % slower on 6-wave blocks than unpacked.
-                    const int nw = nw_env == 6 || nw_env == 9 || nw_env == 12 ? nw_env : 12;
-                    const int Sg = nw / 3;
-                    const int gran = a.C == 384 ? 32 : 16;
-                    const size_t ldsp = (size_t)49 * a.C * 4 + (size_t)2 * (nw * 64 / gran) * 16 * 4;
-                    if (cdiv(nstg, Sg) >= 384) {
-#define DWB_PACK(CC, NWW) if (a.C == CC && nw == NWW) { static DevOnce once; UNI_LDS_OPTIN(once, "dwconv7_lnb (packed lanes)", 163840, reinterpret_cast<const void*>(&dwconv7_lnb_kernel<CC, 2, 0, NWW, true>)); \
-                                     uni_variant_note("dwconv7_ln lnb<C=%d,ROWS=2,DBG=0,NW=%d,PACK=1> fmt=%s batched=%d", CC, NWW, uni_fmt_name(a.b32), nb > 1); \
-                                     hipLaunchKernelGGL((dwconv7_lnb_kernel<CC, 2, 0, NWW, true>), grid, dim3(NWW * 64), ldsp, s, a, Sg, sprg, nstg); return 0; }
-                        DWB_PACK(192, 6) DWB_PACK(192, 9) DWB_PACK(192, 12) DWB_PACK(384, 6) DWB_PACK(384, 9) DWB_PACK(384, 12)
-#undef DWB_PACK
-                    }
-                }
-                // 12 waves per block (three per SIMD) for C = 768 / 384: 177 -> 147 us and 313 -> 298 us on the stage-2 / stage-1 maps at 16 frames
-                // (C = 192: 598 -> 676 us, stays on 8 waves).  UNI_DW_W12 = 0 / 1 / 2: off / default / also C = 192 (A/B switch).
-                static const int w12 = getenv("UNI_DW_W12") ? atoi(getenv("UNI_DW_W12")) : 1;
-                if (w12 && rows == 2 && (a.C == 384 || a.C == 768 || (w12 == 2 && a.C == 192))) {      // (C = 256 measured slower on 12 waves: 53.5 vs 45.2 us at 50 x 80)
-                    const int Sw12 = 12 / wps;
-                    const size_t lds12 = (size_t)49 * a.C * 4 + (size_t)2 * 12 * 16 * 4;
-#define DWB_W12(CC) if (a.C == CC) { static DevOnce once; UNI_LDS_OPTIN(once, "dwconv7_lnb (12 waves)", 163840, reinterpret_cast<const void*>(&dwconv7_lnb_kernel<CC, 2, 0, 12>)); \
-                                     uni_variant_note("dwconv7_ln lnb<C=%d,ROWS=2,DBG=0,NW=12,PACK=0> fmt=%s batched=%d", CC, uni_fmt_name(a.b32), nb > 1); \
-                                     hipLaunchKernelGGL((dwconv7_lnb_kernel<CC, 2, 0, 12>), grid, dim3(Sw12 * wps * 64), lds12, s, a, Sw12, spr, nst); return 0; }
-                    DWB_W12(192) DWB_W12(384) DWB_W12(768)
-#undef DWB_W12
-                }
-#define DWB_GO(CC, RR) if (a.C == CC && rows == RR) { uni_variant_note("dwconv7_ln lnb<C=%d,ROWS=%d,DBG=0,NW=8,PACK=0> fmt=%s batched=%d", CC, RR, uni_fmt_name(a.b32), nb > 1); \
-                         hipLaunchKernelGGL((dwconv7_lnb_kernel<CC, RR>), grid, block, ldsw, s, a, Sw, spr, nst); return 0; }
-                DWB_ALL(DWB_GO)
-#undef DWB_GO
-#undef DWB_ALL
+        // The persistent kernel (row descriptors, register double buffer, weights in LDS) wants 1.5 rounds of blocks for the 256 CUs.  The work
+        // thresholds are POLICY, each measured on the maps its comment names, not geometry: strips are counted in blocks of Sw, the strips of an
+        // 8-WAVE block, also where the build that then runs has 12 waves (counting the chosen build's own blocks would move the C = 384 / 768
+        // crossovers).
+        const int Sw = 8 / cdiv(CG, 64);
+        auto enough = [](int units, int per_block) { return cdiv(units, per_block) >= 384; };
+        if (px == 16 && enough(st2, Sw)) {
+            const int st4 = spr * cdiv(a.H, 4) * nb;             // strips of 4 rows
+            auto groups = [&](int sps) { return cdiv(spr, sps) * cdiv(a.H, 2) * nb; };      // packed lanes: groups of sps strips side by side
+            switch (a.C) {
+                // C = 192 / 384, packed lanes on 12 waves = four groups per block: 602 -> 528 us / 298 -> 265 us on the stage-0 / stage-1 maps at 16
+                // frames (9 waves 559 / 276, 6 waves 579 / 292).  One frame of the stage-0 map has too few groups for such blocks and measured 1 %
+                // slower on 6-wave blocks than unpacked: it stays on 8 waves (12 unpacked: 598 -> 676 us).
+                case 192: return enough(groups(4), 4) ? launch_lnb<192, 2, 12, true>(a, nb, s) : launch_lnb<192, 2, 8, false>(a, nb, s);
+                // unpacked, C = 384 / 768 run 12 waves per block (three per SIMD): 313 -> 298 us / 177 -> 147 us on the stage-1 / stage-2 maps at 16 frames
+                case 384: return enough(groups(2), 4) ? launch_lnb<384, 2, 12, true>(a, nb, s) : launch_lnb<384, 2, 12, false>(a, nb, s);
+                case 768: return launch_lnb<768, 2, 12, false>(a, nb, s);
+                // C = 256 / 512 (one / two waves per strip): 4 output rows per thread -- 4.4 input float4s per output float4 instead of 7 -- where the
+                // 128 accumulators leave the other registers unspilled (tools/dwln_bench.py).  A map with too few 4-row strips for 1.5 rounds of blocks
+                // (the 50 x 80 head level at 16 frames) still fills them with 2-row strips.  (C = 256 measured slower on 12 waves: 53.5 vs 45.2 us at 50 x 80.)
+                case 256: return enough(st4, Sw) ? launch_lnb<256, 4, 8, false>(a, nb, s) : launch_lnb<256, 2, 8, false>(a, nb, s);
+                case 512: return enough(st4, Sw) ? launch_lnb<512, 4, 8, false>(a, nb, s) : launch_lnb<512, 2, 8, false>(a, nb, s);
+                default: break;                                  // every other width: the kernels below
             }
         }
+    }
+    // everything else by n8
+    int S = 256 / CG;
+    if (S < 1) S = 1;
+    const int T = cdiv(S * CG, 64) * 64;
+    if (px == 16) {
+        const int nstrips = spr * ((a.H + 1) / 2) * nb;
         uni_variant_note("dwconv7_ln ln2 CG=%d S=%d fmt=%s batched=%d", CG, S, uni_fmt_name(a.b32), nb > 1);
         hipLaunchKernelGGL(dwconv7_ln2_kernel, dim3(cdiv(nstrips, S)), dim3(T), strip_reduce_lds(S, CG, 16), s, a, S, CG, spr, nstrips);
-        return 0;
-    }
-    if (px == 8) {
-        const int spr = cdiv(a.W, 8), nstrips = spr * a.H * nb;
+    } else if (px == 8) {
+        const int nstrips = spr * a.H * nb;
         uni_variant_note("dwconv7_ln ln<PX=8> CG=%d S=%d fmt=%s batched=%d", CG, S, uni_fmt_name(a.b32), nb > 1);
         hipLaunchKernelGGL(dwconv7_ln_kernel<8>, dim3(cdiv(nstrips, S)), dim3(T), strip_reduce_lds(S, CG, 8), s, a, S, CG, spr, nstrips);
     } else {
-        const int spr = cdiv(a.W, 4), nstrips = spr * a.H * nb;
+        const int spr4 = cdiv(a.W, 4), nstrips = spr4 * a.H * nb;
         uni_variant_note("dwconv7_ln ln<PX=4> CG=%d S=%d fmt=%s batched=%d", CG, S, uni_fmt_name(a.b32), nb > 1);
-        hipLaunchKernelGGL(dwconv7_ln_kernel<4>, dim3(cdiv(nstrips, S)), dim3(T), strip_reduce_lds(S, CG, 4), s, a, S, CG, spr, nstrips);
+        hipLaunchKernelGGL(dwconv7_ln_kernel<4>, dim3(cdiv(nstrips, S)), dim3(T), strip_reduce_lds(S, CG, 4), s, a, S, CG, spr4, nstrips);
     }
     return 0;
 }
@@ -1207,8 +1185,7 @@ int launch_stem(const StemArgs& a, hipStream_t s) {
     int S = 256 / CG;
     if (S < 1) S = 1;
     const int npix = (a.H / 4) * (a.W / 4) * (a.B > 0 ? a.B : 1);
-    static const char* env = getenv("UNI_STEM1");
-    if (a.W % 16 == 0 && !env) {
+    if (a.W % 16 == 0) {
         const int spr = a.W / 16, nstrips = npix / 4;
         const int T4 = cdiv(S * CG, 64) * 64;
         size_t lds4 = S * 192 * sizeof(float) + strip_reduce_lds(S, CG, 4);
