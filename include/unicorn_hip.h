@@ -453,6 +453,38 @@ int uni_dwln_train_bwd_f64(const double* x, const double* weight, const double* 
                            const double* grad_y, int B, int H, int W, int C, double* grad_x, double* grad_weight, double* grad_bias,
                            double* grad_ln_weight, double* grad_ln_bias, void* workspace, size_t workspace_bytes, uni_stream_t stream);
 
+/* The close of a ConvNeXt block for TRAINING (unicorn/models/backbone/convnext.py:49-53: layer scale gamma * x, permute to (N, C, H, W),
+ * input + drop_path(x)), forward and backward for a whole batch: one launch forward, at most two backward, no host synchronisation, no
+ * read-back, no allocation, no atomics.  Operator only: the model-level engine stays inference only.
+ *   y, grad_y            dense [B][H][W][C], the output of pwconv2.  y_dtype: 0 = the type of the form (fp32, fp64 in the _f64 form), 1 = fp16,
+ *                        2 = bf16 (fp32 form only); grad_y has the type of y.  Conversion in registers, all arithmetic fp32 (fp64).
+ *   residual, grad_out   nchw == 0: dense [B][H][W][C] (channels-last memory of a (B, C, H, W) tensor), nchw != 0: dense [B][C][H][W]
+ *   out                  dense [B][H][W][C], always
+ *   gamma, grad_gamma    [C]; gamma may be NULL (= 1)
+ *   scale                [B], the per-sample drop-path factor (0 or 1 / keep); may be NULL (= 1)
+ *   uni_block_tail_fwd   out[n][c][h][w] = residual[n][c][h][w] + (gamma[c] * y[n][h][w][c]) * scale[n].  Writes out COMPLETELY.
+ *   uni_block_tail_bwd   grad_y[n][h][w][c] = gamma[c] * (grad_out[n][c][h][w] * scale[n]) and grad_gamma[c] = sum over n, h, w of
+ *                        (grad_out * scale[n]) * y, each written COMPLETELY; either may be NULL: its work is skipped (and the reduce launch when
+ *                        grad_gamma is NULL; the workspace may then be NULL).  The gradient of residual is grad_out itself.
+ * A sample with scale[n] == 0 is not read: out = residual, grad_y = 0, and it adds exactly 0 to grad_gamma even where y holds Inf or NaN
+ * (the one deliberate difference to the eager lines, which give NaN there).  One writer per element, fixed summation orders (the lanes of a
+ * block in ascending order, blocks in ascending order in double): two calls give the same bits.
+ * Limits: B, H, W >= 1, C % 4 == 0, 4 <= C <= 2048, B H W < 2^31 (element offsets are 64-bit), the maps and the workspace 16-byte aligned
+ * (gamma, scale and grad_gamma need their own type's alignment only); other shapes are refused with an error string and
+ * uni_block_tail_workspace_bytes returns 0 for them.
+ * workspace (backward with grad_gamma only): 16-byte aligned device scratch of >= uni_block_tail_workspace_bytes(B, H, W, C) bytes (fp32; the
+ * _f64 form needs twice that) = 4 * 1024 * C: at most 1024 blocks along the pixels write one row of C partial sums each.  Nothing is kept in
+ * it between calls. */
+size_t uni_block_tail_workspace_bytes(int B, int H, int W, int C);
+int uni_block_tail_fwd(const void* y, int y_dtype, const float* residual, int nchw, const float* gamma, const float* scale, int B, int H, int W,
+                       int C, float* out, uni_stream_t stream);
+int uni_block_tail_bwd(const void* y, int y_dtype, const float* grad_out, int nchw, const float* gamma, const float* scale, int B, int H, int W,
+                       int C, void* grad_y, float* grad_gamma, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_block_tail_fwd_f64(const void* y, int y_dtype, const double* residual, int nchw, const double* gamma, const double* scale, int B, int H,
+                           int W, int C, double* out, uni_stream_t stream);
+int uni_block_tail_bwd_f64(const void* y, int y_dtype, const double* grad_out, int nchw, const double* gamma, const double* scale, int B, int H,
+                           int W, int C, void* grad_y, double* grad_gamma, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+
 /* What stands around the label propagation in the SOT / VOS TRAINING losses (unicorn/models/unicorn.py:315-337 compute_loss_sot, :339-390
  * compute_loss_vos) for a whole BATCH, without a host synchronisation, a read-back or an allocation; the number of launches does not
  * depend on the data.  The propagation itself is uni_corr_softmax_pv_lse / _bwd on the label rows these entries produce.

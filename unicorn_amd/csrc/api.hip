@@ -498,6 +498,21 @@ size_t uni_dwln_train_workspace_bytes(int B, int H, int W, int C) { return dwln_
                                      S(stream)));                                                                                                  \
     }
 UNI_PAIR(DEF_DWLN_TRAIN)
+size_t uni_block_tail_workspace_bytes(int B, int H, int W, int C) { return block_tail_workspace_bytes(B, H, W, C); }
+#define DEF_BLOCK_TAIL(SFX, T)                                                                                                                     \
+    int uni_block_tail_fwd##SFX(const void* y, int y_dtype, const T* residual, int nchw, const T* gamma, const T* scale, int B, int H, int W,      \
+                                int C, T* out, uni_stream_t stream) {                                                                              \
+        UNI_REQUIRE(y && residual && out, "block_tail_fwd" #SFX ": NULL argument");                                                                \
+        const BtArgs<T> a{y, y_dtype, residual, nchw, gamma, scale, B, H, W, C};                                                                   \
+        API(launch_block_tail_fwd<T>(a, out, S(stream)));                                                                                          \
+    }                                                                                                                                              \
+    int uni_block_tail_bwd##SFX(const void* y, int y_dtype, const T* grad_out, int nchw, const T* gamma, const T* scale, int B, int H, int W,      \
+                                int C, void* grad_y, T* grad_gamma, void* workspace, size_t workspace_bytes, uni_stream_t stream) {                \
+        UNI_REQUIRE(y && grad_out, "block_tail_bwd" #SFX ": NULL argument");                                                                       \
+        const BtArgs<T> a{y, y_dtype, grad_out, nchw, gamma, scale, B, H, W, C};                                                                   \
+        API(launch_block_tail_bwd<T>(a, grad_y, grad_gamma, workspace, workspace_bytes, S(stream)));                                               \
+    }
+UNI_PAIR(DEF_BLOCK_TAIL)
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

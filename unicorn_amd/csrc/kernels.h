@@ -346,6 +346,25 @@ int launch_dwln_train_fwd(const DwlnArgs<T>& a, T* y, T* stats, hipStream_t s);
 template <typename T>
 int launch_dwln_train_bwd(const DwlnArgs<T>& a, const T* stats, const T* gy, T* gx, T* gw, T* gb, T* ggamma, T* gbeta, void* ws, size_t ws_bytes,
                           hipStream_t s);
+// block_tail.hip: the close of a ConvNeXt block for TRAINING (convnext.py:49-53): out = x + (gamma * y) * s[n] in channels-last memory and its
+// backward grad_y = gamma * (x * s[n]), grad_gamma[c] = sum (x * s[n]) * y, fp32 (y / grad_y fp32, fp16 or bf16) and fp64, one launch forward and
+// at most two backward, no host read-back, no atomics.  y, grad_y dense [B][H][W][C]; x = residual (forward) / grad_out (backward), dense
+// [B][H][W][C] or, with nchw != 0, [B][C][H][W]; gamma [C] and scale [B] may be NULL (= 1); gy and ggamma may be NULL (not computed).
+// C % 4 == 0, C <= 2048, B H W < 2^31.  Workspace (backward with ggamma only): block_tail_workspace_bytes for fp32, twice that for fp64.
+size_t block_tail_workspace_bytes(int B, int H, int W, int C);
+template <typename T>
+struct BtArgs {
+    const void* y;
+    int y_dtype;                                // 0: the type T, 1 fp16, 2 bf16 (fp32 form only)
+    const T* x;
+    int nchw;
+    const T *gamma, *scale;
+    int B, H, W, C;
+};
+template <typename T>
+int launch_block_tail_fwd(const BtArgs<T>& a, T* out, hipStream_t s);
+template <typename T>
+int launch_block_tail_bwd(const BtArgs<T>& a, void* gy, T* ggamma, void* ws, size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

@@ -8,7 +8,17 @@ through unicorn_amd.ops.dwconv7_ln without restating the block's forward: the bl
 the fused result as an (N, C, H, W) view (`y.permute(0, 3, 1, 2)`), so the block's own permute yields the contiguous (N, H, W, C) tensor, and
 its `norm` gets one that hands that tensor on unchanged.  Module tree, parameter names and state_dict() stay as they were.  The two callables
 are plain objects that hold the two modules, so copy.deepcopy(model) (ModelEMA) gives a copy whose fused blocks use the copy's parameters.
-Outside training mode, and for CPU tensors, both fall back to the modules' original forwards."""
+Outside training mode, and for CPU tensors, both fall back to the modules' original forwards.
+
+fuse_block_tail(model) routes the close of the same block (convnext.py:49-53)
+
+    if self.gamma is not None: x = self.gamma * x
+    x = x.permute(0, 3, 1, 2); x = input + self.drop_path(x)
+
+through unicorn_amd.ops.block_tail.  `self.gamma * x` cannot be reached through a submodule, so the BLOCK gets the instance-level `forward`: it
+calls the block's own submodules in the reference's order (dwconv -> permute -> norm -> pwconv1 -> act -> pwconv2; fuse_dwconv_ln and module
+hooks keep working) and then the operator, whose output is channels-last memory: what the next block's dwconv7_ln reads in place.  The
+drop-path mask is drawn as timm's DropPath draws it, so a seeded run drops the same samples fused and unfused.  fuse_convnext applies both."""
 import torch
 
 from . import ops
@@ -88,3 +98,83 @@ def unfuse_dwconv_ln(model):
             del m.__dict__["forward"]
             n += isinstance(f, _FusedDwConv)
     return n
+
+
+def _drop_path_ok(dp):
+    if isinstance(dp, torch.nn.Identity):
+        return True
+    p = getattr(dp, "drop_prob", None)
+    return isinstance(dp, torch.nn.Module) and isinstance(p, float) and 0.0 <= p < 1.0 and isinstance(getattr(dp, "scale_by_keep", True), bool)
+
+
+def _drop_path_scale(dp, x):
+    """the per-sample factor of timm's drop_path (0 or 1 / keep) as an (N, 1, 1, 1) tensor, or None where timm returns its input"""
+    if isinstance(dp, torch.nn.Identity) or dp.drop_prob == 0.0 or not dp.training:
+        return None
+    keep = 1.0 - dp.drop_prob
+    mask = torch.empty((x.shape[0], 1, 1, 1), dtype=torch.float32, device=x.device).bernoulli_(keep)
+    if keep > 0.0 and getattr(dp, "scale_by_keep", True):
+        mask.div_(keep)
+    return mask
+
+
+class _FusedBlockTail:
+    """instance-level `forward` of a block: its own submodules, then ops.block_tail"""
+    __slots__ = ("block",)
+
+    def __init__(self, block):
+        self.block = block
+
+    def __call__(self, x):
+        b = self.block
+        if not (b.training and x.is_cuda):
+            return type(b).forward(b, x)
+        y = b.pwconv2(b.act(b.pwconv1(b.norm(b.dwconv(x).permute(0, 2, 3, 1)))))
+        scale = _drop_path_scale(b.drop_path, x)
+        if scale is not None and x.dtype == torch.float64:
+            scale = scale.double()
+        return ops.block_tail(y, x, b.gamma, scale)
+
+
+def _tail_fusable(block):
+    if not all(isinstance(getattr(block, n, None), torch.nn.Module) for n in ("dwconv", "norm", "pwconv1", "act", "pwconv2", "drop_path")):
+        return False
+    Cc = getattr(block.dwconv, "in_channels", None)
+    if not isinstance(block.pwconv2, torch.nn.Linear) or not isinstance(Cc, int) or block.pwconv2.out_features != Cc:
+        return False
+    if Cc % 4 or not 4 <= Cc <= ops.DWLN_MAX_C or not hasattr(block, "gamma"):
+        return False
+    g = block.gamma
+    if g is not None and not (isinstance(g, torch.nn.Parameter) and tuple(g.shape) == (Cc,)):
+        return False
+    return _drop_path_ok(block.drop_path)
+
+
+def fuse_block_tail(model):
+    """Fuse the close of every block of `model` that has the modules dwconv, norm, pwconv1, act, pwconv2 (a Linear onto dwconv's C channels;
+    C % 4 == 0, C <= 2048) and drop_path (nn.Identity, or a module with a float drop_prob in [0, 1) and an optional scale_by_keep: timm's
+    DropPath) and an attribute gamma that is None or a (C,) parameter.  Anything else is left alone.  Returns the number of blocks fused
+    (blocks that are fused already are counted).  The block is expected to run the lines of convnext.py:41-54."""
+    n = 0
+    for block in model.modules():
+        if not _tail_fusable(block):
+            continue
+        if not isinstance(block.__dict__.get("forward"), _FusedBlockTail):
+            block.forward = _FusedBlockTail(block)
+        n += 1
+    return n
+
+
+def unfuse_block_tail(model):
+    """Remove what fuse_block_tail set; returns the number of blocks restored."""
+    n = 0
+    for m in model.modules():
+        if isinstance(m.__dict__.get("forward"), _FusedBlockTail):
+            del m.__dict__["forward"]
+            n += 1
+    return n
+
+
+def fuse_convnext(model):
+    """fuse_dwconv_ln + fuse_block_tail -> (blocks whose opening is fused, blocks whose close is fused)"""
+    return fuse_dwconv_ln(model), fuse_block_tail(model)

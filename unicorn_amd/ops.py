@@ -991,6 +991,114 @@ def dwconv7_ln(x, weight, bias, ln_weight, ln_bias, eps=1e-6):
     return DwConv7LNFunction.apply(x, weight, bias, ln_weight, ln_bias, float(eps))
 
 
+_BT_Y_DTYPE = {torch.float32: 0, torch.float64: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _bt_layout(t):
+    """-> (t or a channels-last copy of it, nchw flag): NCHW-contiguous and channels-last memory are read in place"""
+    if t.is_contiguous(memory_format=torch.channels_last):
+        return t, 0
+    if t.is_contiguous():
+        return t, 1
+    return t.contiguous(memory_format=torch.channels_last), 0
+
+
+class BlockTailFunction(torch.autograd.Function):
+    """The close of a ConvNeXt block (convnext.py:49-53): apply(y (N,H,W,C) contiguous, residual (N,C,H,W), gamma (C,) or None, scale (N,) or
+    None) -> out (N,C,H,W) in channels-last memory, in the dtype of residual (fp32 / fp64; ops.block_tail checks).  y may be fp16 / bf16 next
+    to an fp32 residual.  residual and grad_out are read in place in NCHW-contiguous or channels-last memory, anything else is converted once.
+    Saves y, gamma and scale, never out.  The gradient of residual is grad_out itself, that of y a contiguous (N,H,W,C) tensor of y's dtype,
+    that of gamma (C,); only what autograd asks for is computed.  No host synchronisation, one writer per element: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, y, residual, gamma, scale):
+        N, Cc, H, W = residual.shape
+        ctx.dims = (N, Cc, H, W)
+        ctx.save_for_backward(y, gamma, scale)
+        out = torch.empty((N, Cc, H, W), device=residual.device, dtype=residual.dtype, memory_format=torch.channels_last)
+        if N == 0:
+            return out
+        res, nchw = _bt_layout(residual)
+        fn, name = _entry("uni_block_tail_fwd", residual.dtype)
+        with torch.cuda.device(residual.device):
+            L.check(fn(L.ptr(y), _BT_Y_DTYPE[y.dtype], L.ptr(res), nchw, L.ptr(gamma), L.ptr(scale), N, H, W, Cc, L.ptr(out), L.stream_ptr()), name)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        N, Cc, H, W = ctx.dims
+        y, gamma, scale = ctx.saved_tensors
+        need_y, need_res, need_g = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and gamma is not None
+        gy = torch.empty_like(y) if need_y else None
+        gg = torch.empty_like(gamma) if need_g else None
+        if N == 0:
+            return gy, grad_out if need_res else None, gg.zero_() if need_g else None, None
+        if need_y or need_g:
+            g, nchw = _bt_layout(grad_out)
+            fn, name = _entry("uni_block_tail_bwd", g.dtype)
+            with torch.cuda.device(g.device):
+                ws = None
+                if need_g:
+                    ws = torch.empty(L.lib().uni_block_tail_workspace_bytes(N, H, W, Cc) * _ws_factor(g.dtype), device=g.device, dtype=torch.uint8)
+                L.check(fn(L.ptr(y), _BT_Y_DTYPE[y.dtype], L.ptr(g), nchw, L.ptr(gamma), L.ptr(scale), N, H, W, Cc, L.ptr(gy), L.ptr(gg),
+                           L.ptr(ws), ws.numel() if need_g else 0, L.stream_ptr()), name)
+        return gy, grad_out if need_res else None, gg, None
+
+
+def block_tail(y, residual, gamma=None, scale=None):
+    """`input + drop_path((gamma * x).permute(0, 3, 1, 2))` of a ConvNeXt block (convnext.py:49-53) as one operator with the drop-path factor
+    given per sample: out[n, c, h, w] = residual[n, c, h, w] + scale[n] * gamma[c] * y[n, h, w, c].
+      y         (N, H, W, C), the output of pwconv2: fp32, or fp16 / bf16 (what pwconv2 returns under autocast); made contiguous if it is not
+      residual  (N, C, H, W) fp32; a half residual is cast with .float(), as type promotion does in the eager lines.  NCHW-contiguous and
+                channels-last memory are read in place, any other strides are converted once to channels-last
+      gamma     (C,) fp32 or None (= 1)
+      scale     (N,) or (N, 1, 1, 1) fp32 without gradient, or None (= 1): 0 or 1 / keep of the sample
+    All four fp64 is accepted for checks.  Returns out (N, C, H, W) fp32 (fp64) with out.is_contiguous(memory_format=torch.channels_last).
+    Gradients: residual receives grad_out itself (no copy), y a contiguous (N, H, W, C) tensor of its own dtype, gamma (C,); grad_out is read in
+    place in either of the two layouts.  Autograd keeps y, gamma and scale, never out.  C % 4 == 0, 4 <= C <= 2048.  The one deliberate
+    difference to the eager lines: a sample with scale 0 is not read, so its grad_y is 0 and it adds 0 to grad_gamma even where y holds Inf
+    or NaN (eager gives NaN).  N == 0 returns an empty tensor without a library call."""
+    for n, t in (("y", y), ("residual", residual)):
+        if not isinstance(t, torch.Tensor):
+            raise L.UnicornHipError("block_tail: %s is not a tensor" % n)
+    for n, t in (("gamma", gamma), ("scale", scale)):
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise L.UnicornHipError("block_tail: %s is not a tensor or None" % n)
+    if residual.dim() != 4:
+        raise L.UnicornHipError("block_tail: residual of shape %s is not (N, C, H, W)" % (tuple(residual.shape),))
+    N, Cc, H, W = residual.shape
+    if tuple(y.shape) != (N, H, W, Cc):
+        raise L.UnicornHipError("block_tail: y of shape %s is not (N, H, W, C) = (%d, %d, %d, %d) of residual" % (tuple(y.shape), N, H, W, Cc))
+    if gamma is not None and tuple(gamma.shape) != (Cc,):
+        raise L.UnicornHipError("block_tail: gamma of shape %s is not (%d,)" % (tuple(gamma.shape), Cc))
+    if scale is not None and tuple(scale.shape) not in ((N,), (N, 1, 1, 1)):
+        raise L.UnicornHipError("block_tail: scale of shape %s is not (%d,) or (%d, 1, 1, 1)" % (tuple(scale.shape), N, N))
+    if Cc % 4 or not 4 <= Cc <= DWLN_MAX_C:
+        raise L.UnicornHipError("block_tail: C = %d is outside C %% 4 == 0, 4 <= C <= %d" % (Cc, DWLN_MAX_C))
+    if N and (H == 0 or W == 0 or N * H * W >= 1 << 31):
+        raise L.UnicornHipError("block_tail: shape N=%d H=%d W=%d is outside a non-empty map with N H W < 2^31" % (N, H, W))
+    if scale is not None and scale.requires_grad:
+        raise L.UnicornHipError("block_tail: scale requires a gradient; it is a constant of the step")
+    ts = [t for t in (y, residual, gamma, scale) if t is not None]
+    if y.dtype == torch.float64:
+        ok = all(t.dtype == torch.float64 for t in ts)
+    else:
+        ok = (y.dtype in _BT_Y_DTYPE and residual.dtype in (torch.float32, torch.float16, torch.bfloat16)
+              and all(t.dtype == torch.float32 for t in (gamma, scale) if t is not None))
+    if not ok:
+        raise L.UnicornHipError("block_tail: dtypes %s unsupported (y fp32 / fp16 / bf16 with residual fp32 or half and gamma, scale fp32; or "
+                                "all fp64)" % ", ".join(str(t.dtype) for t in ts))
+    _need_cuda(*ts)
+    if len({t.device for t in ts}) != 1:
+        raise L.UnicornHipError("block_tail: tensors on different devices")
+    if residual.dtype in (torch.float16, torch.bfloat16):
+        residual = residual.float()
+    if scale is not None:
+        scale = scale.detach().reshape(N).contiguous()
+    return BlockTailFunction.apply(y.contiguous(), residual, None if gamma is None else gamma.contiguous(), scale)
+
+
 def _prop_ws(dev, B, Kc, Q):
     need = L.lib().uni_prop_workspace_bytes(B, Kc, Q)
     if need == 0:
