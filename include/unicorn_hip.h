@@ -711,6 +711,31 @@ int uni_gemm_ex(const void* a, int lda, const void* w_packed, float wscale, int 
                 int stride, int pad, const float* bias, int act, int act_col0, const float* residual, int ldr, float* out_f32, int ldf,
                 void* out_op, int ldb, double* gn_stats, int cpg, int force_cfg, uni_stream_t stream);
 int uni_cast_f32(const float* x, int ldx, float* out, int ldo, int M, int C, uni_stream_t stream);
+/* uni_gemm_ex with the two launch modes the engine sets on a batch, without a context.  Stacked samples: a holds B maps [B][Hin][Win][Cin]
+ * (Hin, Win per sample, 1 <= B < 128), M = B * Hout * Wout; a convolution pads every sample on its own and the GroupNorm sums of sample b
+ * go to gn_stats + 64 b (gn_stats: 64 B doubles, zeroed by the caller; cpg divides N into at most 32 groups).  Row remap (out_hw > 0):
+ * row r of out_f32 is written at (r / out_hw) * out_stride + out_off + r % out_hw, which is how one launch spreads a pyramid level over
+ * the anchor rows of several images; out_f32 has outF_rows rows and the call fails when the last remapped row (or, without a remap, M)
+ * does not fit.  out_op is never remapped.  splitk > 1 (fmt 2 only): that many K ranges through a slab kept by the library, then the
+ * reduce kernel (bias, residual, statistics); fp32 output only, no activation, no remap.  Every argument is checked before a launch. */
+int uni_gemm_stacked(const void* a, int lda, const void* w_packed, float wscale, int fmt, int B, int M, int N, int Hin, int Win, int Cin, int KH,
+                     int KW, int stride, int pad, const float* bias, int act, int act_col0, const float* residual, int ldr, float* out_f32,
+                     int ldf, int out_hw, int out_stride, int out_off, int outF_rows, void* out_op, int ldb, double* gn_stats, int cpg,
+                     int splitk, int force_cfg, uni_stream_t stream);
+/* The glue launchers the engine runs between its own buffers, without a context.  fmt = operand format of out (0 = bf16, 1 = fp32, 2 = f16x2).
+ * uni_cast_operand_pair_ex: x0, x1 [B][hw][C] fp32 (two frames) -> out [B][2][hw][C] operand rows (the token layout of the interaction
+ * stage).  uni_pixel_shuffle_ex: x (B, h, w, C) fp32 -> out (B, 2h, 2w, C / 4) operand rows, PixelShuffle(2).  uni_add_pos_ex: tokens src
+ * [B][2][hw][C] + pos0 / pos1 [hw][C] (frame 0 / 1, shared by the batch) + lvl[frame][C] -> operand rows (deformable_transformer.py:74,124).
+ * uni_add_aligned_bilinear_ex: dst (B, f h, f w, C) += aligned_bilinear(src (B, h, w, C), f) (condinst/comm.py:5-27).  uni_pos_embed_ex:
+ * [col_embed(x) | row_embed(y)] of two (sz, nf) tables, bilinear to (h, w) -> out (h w, 2 nf) (position_encoding.py:25-36).
+ * uni_msda_tokens_ex: uni_msda_tokens with the output in any operand format. */
+int uni_cast_operand_pair_ex(const float* x0, const float* x1, void* out, int B, int hw, int C, int fmt, uni_stream_t stream);
+int uni_pixel_shuffle_ex(const float* x, void* out, int B, int h, int w, int C, int fmt, uni_stream_t stream);
+int uni_add_pos_ex(const float* src, const float* pos0, const float* pos1, const float* lvl, void* out, int B, int hw, int C, int fmt,
+                   uni_stream_t stream);
+int uni_add_aligned_bilinear_ex(const float* src, int B, int h, int w, int C, int factor, float* dst, uni_stream_t stream);
+int uni_pos_embed_ex(const float* row_embed, const float* col_embed, int sz, int nf, int h, int w, float* out_nhwc, uni_stream_t stream);
+int uni_msda_tokens_ex(const float* value, const float* offaw, int ldo, int B, int h, int w, void* out, int fmt, uni_stream_t stream);
 
 #ifdef __cplusplus
 }

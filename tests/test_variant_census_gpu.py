@@ -258,6 +258,51 @@ def run_gemm(L, a, bound):
     return checks
 
 
+def run_gemm_stacked(L, a, bound):
+    """uni_gemm_stacked: B stacked samples and / or the outF row remap against the batched fp64 conv (vc.gemm_stacked_problem); every buffer is
+    pre-filled, and what the kernel must not write -- the gaps between the remapped images, the columns >= N, the rows behind, the unused part
+    of every statistics slot -- must still hold the fill"""
+    Hin, Win, Cin, N, k, stride, pad = a["geo"]
+    B, act, G, c0, h2 = a["B"], a["act"], a["G"], a["act_col0"], a["fam"] == "h2"
+    P = vc.gemm_stacked_problem(a, bound)
+    M, exp, tol = P["M"], P["exp"], P["tol"]
+    rows = P["x"].permute(0, 2, 3, 1).reshape(B * Hin * Win, Cin).contiguous().cuda()
+    FILL = -777.0
+    ldf, ldb, ldr = a["ldf"], N + 8, N + 4
+    outF = torch.full((a["outF_rows"], ldf), FILL, device="cuda") if a["outF"] else None
+    stats = torch.zeros(64 * (B + 1), device="cuda", dtype=torch.float64) if G else None      # one slot more than the launch may touch
+    bias_d, res_d = (P["bias"].cuda() if a["bias"] else None), (P["res"].cuda() if a["res"] else None)
+    if h2:
+        A = _cast_h2(L, rows)
+        Wp, wscale = _pack_h2(L, P["w"])
+    else:
+        K = Cin * k * k
+        Wp = torch.zeros(((N + 255) // 256 * 256, (K + 63) // 64 * 64))
+        Wp[:N, :K] = P["w"].permute(0, 2, 3, 1).reshape(N, K)
+        A, Wp, wscale = rows, Wp.cuda(), 1.0
+    ofmt = 2 if h2 else 1
+    outB = op_buffer(M + 1, ldb, ofmt) if a["outB"] else None
+    L.check(L.lib().uni_gemm_stacked(L.ptr(A), Cin, L.ptr(Wp), wscale, ofmt, B, M, N, Hin, Win, Cin, k, k, stride, pad, L.ptr(bias_d), act, c0, L.ptr(res_d), ldr,
+                                     L.ptr(outF), ldf, a["out_hw"], a["out_stride"], a["out_off"], a["outF_rows"], L.ptr(outB), ldb, L.ptr(stats),
+                                     (N // G) if G else 0, a["splitk"], a["cfg"], L.stream_ptr()), "gemm_stacked")
+    torch.cuda.synchronize()
+    checks = []
+    if outF is not None:
+        got = outF.cpu().double()
+        written = torch.zeros(a["outF_rows"], ldf, dtype=torch.bool)
+        written[P["orow"], :N] = True
+        assert bool((got[~written] == FILL).all()), "outF: written outside the (remapped) rows x N columns"
+        checks.append(("outF", got[P["orow"], :N], exp, tol))
+    if outB is not None:
+        assert op_untouched(outB, ofmt, M, N), "outB: complement written"
+        checks.append(("outB", op_decode(outB, ofmt)[:M, :N], exp, tol + (exp.abs() * 2.0 ** -21 if h2 else 0)))
+    if G:
+        st = stats.cpu().reshape(B + 1, 64)
+        assert bool((st[:B, 2 * G:] == 0).all()) and bool((st[B] == 0).all()), "statistics: written outside the [G][2] sums of the B slots"
+        checks.append(("stats", st[:B, :2 * G].reshape(B, G, 2), P["stats_ref"], P["stats_tol"]))
+    return checks
+
+
 def run_corr(L, a, bound):
     from unicorn_amd.ops import corr_softmax_pv, corr_softmax_pv_batched
     B, R, Q, K, prec = a["B"], a["R"], a["Q"], a["K"], a["prec"]
@@ -341,7 +386,8 @@ def run_mlp(L, a, bound):
     return checks
 
 
-def run_msda_tokens(L, a, bound):
+def _msda_problem(a):
+    """-> value (B, Lq, 256), offaw (B Lq, 192), fp64 reference (B Lq, 256) of the fused sampler"""
     import unicorn_oracle as uo
     B, h, w = a["B"], a["h"], a["w"]
     g = torch.Generator().manual_seed(B * 100 + h)
@@ -351,16 +397,131 @@ def run_msda_tokens(L, a, bound):
     off[:, :5] *= 30.0
     logits = torch.randn(B, Lq, 8, 8, generator=g) * 2.0
     offaw = torch.cat([off.reshape(B * Lq, 128), logits.reshape(B * Lq, 64)], 1).contiguous()
-    out = torch.empty(B * Lq, 256, device="cuda")
-    vd, od = value.cuda(), offaw.cuda()
-    L.check(L.lib().uni_msda_tokens(L.ptr(vd), L.ptr(od), 192, B, h, w, L.ptr(out), L.stream_ptr()), "uni_msda_tokens")
-    torch.cuda.synchronize()
     ii, jj = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
     ref = torch.stack([(jj.reshape(-1) + 0.5) / w, (ii.reshape(-1) + 0.5) / h], -1).repeat(2, 1).double()
     loc = ref[None, :, None, None, None, :] + off.double() / torch.tensor([w, h], dtype=torch.float64)
     attn = torch.softmax(logits.double(), -1).view(B, Lq, 8, 2, 4)
     want = uo.msda_core(value.double().view(B, Lq, 8, 32), [(h, w), (h, w)], loc, attn).reshape(B * Lq, 256)
+    return value, offaw, want
+
+
+def run_msda_tokens(L, a, bound):
+    B, h, w = a["B"], a["h"], a["w"]
+    value, offaw, want = _msda_problem(a)
+    out = torch.empty(B * 2 * h * w, 256, device="cuda")
+    vd, od = value.cuda(), offaw.cuda()
+    L.check(L.lib().uni_msda_tokens(L.ptr(vd), L.ptr(od), 192, B, h, w, L.ptr(out), L.stream_ptr()), "uni_msda_tokens")
+    torch.cuda.synchronize()
     return [("out", out.cpu().double(), want, bound + 1e-4 * want.abs())]          # allclose(rtol 1e-4, atol 2e-5)
+
+
+# ------------------------------------------------------------------------------------------------ the glue launchers between context buffers
+def _op_tol(e, fmt, bound):
+    """operand rows against the fp64 value they store: the restated row bound of the format, exact for fp32 (as run_cast)"""
+    return torch.zeros_like(e) if fmt == 1 else bound * max(1.0, e.abs().max().item())
+
+
+def run_msda_tokens_ex(L, a, bound):
+    B, h, w, fmt = a["B"], a["h"], a["w"], a["fmt"]
+    value, offaw, want = _msda_problem(a)
+    M = B * 2 * h * w
+    out = op_buffer(M + 1, 256, fmt)
+    vd, od = value.cuda(), offaw.cuda()
+    L.check(L.lib().uni_msda_tokens_ex(L.ptr(vd), L.ptr(od), 192, B, h, w, L.ptr(out), fmt, L.stream_ptr()), "uni_msda_tokens_ex")
+    torch.cuda.synchronize()
+    assert op_untouched(out, fmt, M, 256), "msda_tokens_ex wrote behind its output"
+    return [("out", op_decode(out, fmt)[:M], want, bound * max(1.0, want.abs().max().item()))]
+
+
+def run_cast_pair(L, a, bound):
+    B, hw, C_, fmt = a["B"], a["h"] * a["w"], a["C"], a["fmt"]
+    g = torch.Generator().manual_seed(B + C_)
+    x = torch.randn(2, B, hw, C_, generator=g) * (1.0 + torch.arange(2 * B).float().reshape(2, B, 1, 1))      # every (frame, sample) on its own scale
+    e = x.permute(1, 0, 2, 3).reshape(2 * B * hw, C_).double()                                                # [B][2][hw][C]
+    x0, x1 = x[0].contiguous().cuda(), x[1].contiguous().cuda()
+    out = op_buffer(2 * B * hw + 1, C_, fmt)
+    L.check(L.lib().uni_cast_operand_pair_ex(L.ptr(x0), L.ptr(x1), L.ptr(out), B, hw, C_, fmt, L.stream_ptr()), "cast_operand_pair_ex")
+    torch.cuda.synchronize()
+    assert op_untouched(out, fmt, 2 * B * hw, C_), "cast_operand_pair_ex wrote behind its output"
+    return [("out", op_decode(out, fmt)[:2 * B * hw], e, _op_tol(e, fmt, bound))]
+
+
+def run_pixel_shuffle(L, a, bound):
+    B, h, w, C_, fmt = a["B"], a["h"], a["w"], a["C"], a["fmt"]
+    g = torch.Generator().manual_seed(B + C_ + 1)
+    x = torch.randn(B, C_, h, w, generator=g) * (1.0 + torch.arange(B).float().reshape(B, 1, 1, 1))
+    e = F.pixel_shuffle(x.double(), 2).permute(0, 2, 3, 1).reshape(4 * B * h * w, C_ // 4)
+    xd = x.permute(0, 2, 3, 1).contiguous().cuda()
+    out = op_buffer(4 * B * h * w + 8, C_ // 4, fmt)
+    L.check(L.lib().uni_pixel_shuffle_ex(L.ptr(xd), L.ptr(out), B, h, w, C_, fmt, L.stream_ptr()), "pixel_shuffle_ex")
+    torch.cuda.synchronize()
+    assert op_untouched(out, fmt, 4 * B * h * w, C_ // 4), "pixel_shuffle_ex wrote behind its output"
+    return [("out", op_decode(out, fmt)[:4 * B * h * w], e, _op_tol(e, fmt, bound))]
+
+
+def run_add_pos(L, a, bound):
+    B, hw, C_, fmt = a["B"], a["h"] * a["w"], a["C"], a["fmt"]
+    g = torch.Generator().manual_seed(B + C_ + 2)
+    src = torch.randn(B, 2, hw, C_, generator=g) * (1.0 + torch.arange(B).float().reshape(B, 1, 1, 1))
+    pos = torch.randn(2, hw, C_, generator=g)                  # frame 0 / 1, shared by the batch
+    lvl = torch.randn(2, C_, generator=g)
+    e = (src.double() + pos.double()[None] + lvl.double()[None, :, None, :]).reshape(2 * B * hw, C_)
+    sd, p0, p1, ld = src.cuda(), pos[0].contiguous().cuda(), pos[1].contiguous().cuda(), lvl.cuda()
+    out = op_buffer(2 * B * hw + 1, C_, fmt)
+    L.check(L.lib().uni_add_pos_ex(L.ptr(sd), L.ptr(p0), L.ptr(p1), L.ptr(ld), L.ptr(out), B, hw, C_, fmt, L.stream_ptr()), "add_pos_ex")
+    torch.cuda.synchronize()
+    assert op_untouched(out, fmt, 2 * B * hw, C_), "add_pos_ex wrote behind its output"
+    got = op_decode(out, fmt)[:2 * B * hw]
+    if fmt != 1:
+        return [("out", got, e, _op_tol(e, fmt, bound))]
+    # fp32 rows: the sum itself is rounded, so "exact" is the fp32 evaluation in the kernel's association src + (pos + lvl) -- correctly rounded
+    # additions, the same bits on any IEEE machine -- and that evaluation lies within two roundings, 2^-23 (|src| + |pos| + |lvl|), of fp64
+    e32 = (src + (pos[None] + lvl[None, :, None, :])).reshape(2 * B * hw, C_).double()
+    mag = (src.abs().double() + pos.abs().double()[None] + lvl.abs().double()[None, :, None, :]).reshape(2 * B * hw, C_)
+    return [("out (fp64 sum)", got, e, 2.0 ** -23 * mag + 1e-30), ("out (fp32 sum, exact)", got, e32, torch.zeros_like(e32))]
+
+
+def _fp32_yardstick(what, r32, r64, cap):
+    """the project's yardstick for fp32 results of fp32 arithmetic: 4 x the distance of the oracle's own fp32 evaluation from its fp64
+    evaluation of the same inputs (CPU), capped by the case's restated bound (relative to max(1, max |reference|))"""
+    d = (r32.double() - r64).abs().max().item()
+    tol = min(4.0 * d, cap * max(1.0, r64.abs().max().item()))
+    print("%s: oracle fp32 - fp64 %.3e -> tolerance %.3e" % (what, d, tol))
+    return tol
+
+
+def run_add_aligned_bilinear(L, a, bound):
+    import unicorn_oracle as uo
+    B, h, w, C_, f = a["B"], a["h"], a["w"], a["C"], a["factor"]
+    g = torch.Generator().manual_seed(B + C_ + f)
+    src = torch.randn(B, C_, h, w, generator=g) * (1.0 + torch.arange(B).float().reshape(B, 1, 1, 1))
+    dst = torch.randn(B, C_, f * h, f * w, generator=g)
+    r64 = dst.double() + uo.aligned_bilinear(src.double(), f)                # per sample: the oracle pads / interpolates every (h, w) map on its own
+    r32 = dst + uo.aligned_bilinear(src, f)
+    rows = B * f * h * f * w
+    buf = torch.full((rows + 1, C_), 7.0, device="cuda")
+    buf[:rows] = dst.permute(0, 2, 3, 1).reshape(rows, C_).cuda()
+    sd = src.permute(0, 2, 3, 1).contiguous().cuda()
+    L.check(L.lib().uni_add_aligned_bilinear_ex(L.ptr(sd), B, h, w, C_, f, L.ptr(buf), L.stream_ptr()), "add_aligned_bilinear_ex")
+    torch.cuda.synchronize()
+    assert op_untouched(buf, 1, rows, C_), "add_aligned_bilinear_ex wrote behind its output"
+    flat = lambda t: t.permute(0, 2, 3, 1).reshape(rows, C_)
+    return [("dst", buf.cpu().double()[:rows], flat(r64), _fp32_yardstick("add_aligned_bilinear", flat(r32), flat(r64), bound))]
+
+
+def run_pos_embed(L, a, bound):
+    import unicorn_oracle as uo
+    h, w, sz, nf = a["h"], a["w"], a["sz"], a["nf"]
+    g = torch.Generator().manual_seed(sz + nf)
+    P = {"pos_emb.row_embed.weight": torch.rand(sz, nf, generator=g), "pos_emb.col_embed.weight": torch.rand(sz, nf, generator=g)}      # nn.init.uniform_
+    flat = lambda t: t[0].permute(1, 2, 0).reshape(h * w, 2 * nf)
+    r64, r32 = flat(uo.pos_embed({k: v.double() for k, v in P.items()}, h, w)), flat(uo.pos_embed(P, h, w))
+    out = torch.full((h * w + 1, 2 * nf), 7.0, device="cuda")
+    rd, cd = P["pos_emb.row_embed.weight"].cuda(), P["pos_emb.col_embed.weight"].cuda()
+    L.check(L.lib().uni_pos_embed_ex(L.ptr(rd), L.ptr(cd), sz, nf, h, w, L.ptr(out), L.stream_ptr()), "pos_embed_ex")
+    torch.cuda.synchronize()
+    assert op_untouched(out, 1, h * w, 2 * nf), "pos_embed_ex wrote behind its output"
+    return [("out", out.cpu().double()[:h * w], r64, _fp32_yardstick("pos_embed", r32, r64, bound))]
 
 
 def run_prior_pyramid(L, a, bound):
@@ -399,8 +560,10 @@ def run_condinst(L, a, bound):
 
 
 RUNNERS = {"uni_dwconv7_ln_ex": run_dwconv7_ln_ex, "uni_layernorm_ex": run_layernorm_ex, "uni_groupnorm_act_ex": run_groupnorm_act_ex,
-           "uni_gemm_h2": run_gemm, "uni_gemm_ex": run_gemm, "uni_corr_softmax_pv": run_corr, "uni_corr_softmax_pv_batched": run_corr,
+           "uni_gemm_h2": run_gemm, "uni_gemm_ex": run_gemm, "uni_gemm_stacked": run_gemm_stacked, "uni_corr_softmax_pv": run_corr, "uni_corr_softmax_pv_batched": run_corr,
            "uni_cast_h2": run_cast, "uni_cast_f32": run_cast, "uni_stem_ex": run_stem, "uni_mlp_fused": run_mlp, "uni_msda_tokens": run_msda_tokens,
+           "uni_msda_tokens_ex": run_msda_tokens_ex, "uni_cast_operand_pair_ex": run_cast_pair, "uni_pixel_shuffle_ex": run_pixel_shuffle,
+           "uni_add_pos_ex": run_add_pos, "uni_add_aligned_bilinear_ex": run_add_aligned_bilinear, "uni_pos_embed_ex": run_pos_embed,
            "uni_prior_pyramid": run_prior_pyramid, "uni_decode_outputs": run_decode, "uni_condinst_masks": run_condinst}
 
 
@@ -414,7 +577,10 @@ def run_case(L, tag):
         assert torch.isfinite(got).all(), what
         err = (got - exp).abs()
         if torch.is_tensor(tol):            # element-wise tolerance (sum |a||w| scale of a GEMM, allclose-style bounds)
-            lines.append("%s: %s max err / tolerance %.3f" % (tag, what, (err / tol.clamp_min(1e-300)).max().item() if bool((tol > 0).all()) else err.max().item()))
+            if bool((tol > 0).all()):
+                lines.append("%s: %s max err / tolerance %.3f" % (tag, what, (err / tol).max().item()))
+            else:                           # exact where the tolerance is 0
+                lines.append("%s: %s max err %.3e (held to the exact value)" % (tag, what, err.max().item()))
             ok = bool((err <= tol).all())
         else:
             lines.append("%s: %s max err %.3e (tolerance %.3e)" % (tag, what, err.max().item(), tol))
@@ -474,6 +640,47 @@ def test_trace_split_k_gives_partial_and_reduce_tags(L):
     assert len(tags) == 2 and len(part) == 1 and len(red) == 1 and set(tags.values()) == {1}, tags
     exp = x.double() @ w.reshape(N, K).double().cuda().t()
     assert (out.double() - exp).abs().max().item() < 1e-4 * exp.abs().max().item()
+
+
+def test_gemm_stacked_rejects_bad_arguments_before_any_launch(L):
+    """uni_gemm_stacked checks every argument before it launches: a bad sample count, remap or split-K request is an error code with a
+    message, no tag is traced and no output element changes.  (Every buffer here is large enough for any reading of the arguments.)  The
+    tightest valid remap -- the last remapped row is the last row of out_f32 -- is accepted."""
+    lib = L.lib()
+    B, Hin, Win, Cin, N = 5, 7, 9, 128, 192
+    M, rows, ldf = B * Hin * Win, 1000, N + 4
+    A = torch.zeros(M, Cin, device="cuda")
+    Wp = torch.zeros(256, 128, device="cuda")
+    outF = torch.full((rows, ldf), -777.0, device="cuda")
+    stats = torch.zeros(64 * B, device="cuda", dtype=torch.float64)
+    ok = dict(fmt=1, B=B, M=M, out_hw=0, out_stride=0, out_off=0, outF_rows=rows, act=0, stats=None, cpg=0, splitk=0)
+    remap = dict(out_hw=63, out_stride=200, out_off=10)             # last row: 4 * 200 + 10 + 63 = 873 rows needed
+
+    def call(**kw):
+        a = dict(ok, **kw)
+        return lib.uni_gemm_stacked(L.ptr(A), Cin, L.ptr(Wp), 1.0, a["fmt"], a["B"], a["M"], N, Hin, Win, Cin, 1, 1, 1, 0, None, a["act"], 0, None, 0, L.ptr(outF), ldf,
+                                    a["out_hw"], a["out_stride"], a["out_off"], a["outF_rows"], None, 0, L.ptr(a["stats"]), a["cpg"], a["splitk"], 0, L.stream_ptr())
+
+    bad = {"B = 0": dict(B=0), "B = -1": dict(B=-1), "B = 128": dict(B=128), "M one short": dict(M=M - 1), "B = 3 does not match the map": dict(B=3),
+           "remap one row behind outF_rows": dict(remap, outF_rows=872), "out_hw does not divide M": dict(remap, out_hw=64),
+           "out_stride < out_hw": dict(remap, out_stride=62), "out_off < 0": dict(remap, out_off=-1), "outF_rows < M": dict(outF_rows=M - 1),
+           "split-K in fp32": dict(splitk=2), "split-K with an activation": dict(fmt=2, splitk=2, act=1), "split-K 65": dict(fmt=2, splitk=65),
+           "split-K with a remap": dict(remap, fmt=2, splitk=2), "statistics without cpg": dict(stats=stats), "cpg does not divide N": dict(stats=stats, cpg=5),
+           "48 groups": dict(stats=stats, cpg=4), "statistics with an activation": dict(stats=stats, cpg=12, act=1)}
+
+    def all_bad():
+        for what, kw in bad.items():
+            assert call(**kw) != 0, "accepted: " + what
+            assert lib.uni_last_error(), what
+    _, tags = traced(L, all_bad)
+    assert tags == {}, tags
+    assert bool((outF == -777.0).all()) and bool((stats == 0).all())
+    L.check(call(**dict(remap, outF_rows=873)), "gemm_stacked (tightest valid remap)")
+    torch.cuda.synchronize()
+    written = torch.zeros(rows, dtype=torch.bool)
+    written[vc.gemm_stacked_problem(dict(geo=(Hin, Win, Cin, N, 1, 1, 0), B=B, act=0, G=0, act_col0=0, cfg=0, bias=False, res=False, **remap))["orow"]] = True
+    got = outF.cpu()
+    assert bool((got[written][:, :N] == 0).all()) and bool((got[written][:, N:] == -777.0).all()) and bool((got[~written] == -777.0).all())
 
 
 # ------------------------------------------------------------------------------------------------ 2. census

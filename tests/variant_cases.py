@@ -218,8 +218,8 @@ CASE_LIST += [_gemm("h2", "h2d", 42232, 346, *t) for t in ((0, 0, 0, 0, 1, 0, 2)
 CASE_LIST += [_gemm("h2", "h2q_outB", 188, 188, 0, 0, 0, 0, 1, 0, 1), _gemm("h2", "h2q_outB", 188, 188, 0, 0, 0, 0, 1, 0, 2),
               _gemm("h2", "h2q_outF", 188, 188, 0, 0, 0, 1, 0, 0, 0), _gemm("h2", "h2q_outF", 188, 188, 0, 0, 0, 1, 0, 1, 0)]
 CASE_LIST += [_reduce(0, 0, 1, 1), _reduce(1, 1, 0, 0)]
-# What the 16-frame step and the head's remapped outputs run on (their tags carry stacked=1 / remap=1 and sit in CTX_ONLY; the closure asks
-# for the same tag with both switches at 0, i.e. the same template instantiation on one sample): the ping-pong kernel as an implicit GEMM and
+# What the 16-frame step and the head's remapped outputs run on, on one sample and without the remap (the stacked=1 / remap=1 tags have
+# their own cases further down, on uni_gemm_stacked): the ping-pong kernel as an implicit GEMM and
 # with GroupNorm sums, the 256 x 192 tile with sums / as a conv, the direct-epilogue tiles of the N = 5 / 6 / 169 head layers with the
 # sigmoid on every column and on a column window.
 CASE_LIST += [
@@ -235,6 +235,125 @@ CASE_LIST += [
 ]
 # deep tile 322 (128 x 128, 4-deep ring): the heuristic keeps it for long-K plain GEMMs with 193 .. 256 tiles, which no census workload has
 CASE_LIST += [_gemm("h2", "h2d", 22224, 322, 0, 0, 0, 1, 0, 0, 0)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- GEMM: stacked samples, row remap
+# uni_gemm_stacked sets the two switches the engine sets on a batch: B samples per launch (Mper != M: 3x3 halos stop at every sample's own
+# border, GroupNorm sums of sample b at stats + 64 b) and the outF row remap of the head outputs.  Two maps, the smallest that make tiles
+# straddle samples: (13, 17) x 3 -- Mper = 221, M = 663: every 64- / 128- / 256-row tile boundary falls inside a sample, the first 256-row
+# tile holds parts of two samples, the last tile is ragged -- and (7, 9) x 5 -- Mper = 63, M = 315: one 256-row tile holds more than four
+# samples (the b_lo .. b_hi loop of gemm_stats runs five times), a 64-row tile has a sample boundary at row 63.  Cin / N as the one-sample
+# geometries above.  Sample b is drawn as x_b (1 + b) + 0.5 b, so a row attributed to the wrong sample moves a sum by far more than the
+# tolerance (tests/test_variant_cases_cpu.py shows it for every case, without a GPU).
+MAP_A, MAP_B = (13, 17, 3), (7, 9, 5)       # (Hin, Win, B)
+REMAP = dict(out_stride=300, out_off=40)    # anchors per image / first anchor row of the level; out_hw = the level's rows per image (221)
+STATS_RTOL, STATS_ATOL = 2e-5, 2e-2         # test_gemm_h2
+
+
+def _gemms(fam, kernel, code, force, conv, stats, splitk, outF, outB, res, act, base, hwb, remap=0, win=0, bias=True, reduce_tag=False):
+    """a uni_gemm_stacked case: `base` gives Cin / N / k / stride / pad, hwb = (Hin, Win, B) the map and the number of samples"""
+    Hin, Win, B = hwb
+    geo = (Hin, Win) + tuple(base[2:])
+    N = geo[3]
+    ldf = N if N == 169 else N + (4 if N % 4 == 0 else 3)      # the controller output keeps the engine's odd ld = 169; everything else has columns behind N
+    epi = fam != "f32" and N % 8 == 0
+    if reduce_tag:
+        tag = "gemm:splitk_reduce bias=%d res=%d stats=%d stacked=%d" % (bias, res, stats, B > 1)
+    else:
+        tag = "gemm:%s cfg=%d fmt=%s conv=%d stats=%d splitk=%d epi=%d outF=%d outB=%d res=%d act=%d%s remap=%d stacked=%d" % (
+            kernel, code, "f32" if fam == "f32" else "h2", conv, stats and not splitk, splitk, epi, outF, outB, res and not splitk, act, "w" if win else "",
+            bool(remap) and not splitk, B > 1)
+    args = dict(fam=fam, geo=geo, B=B, act=act, act_col0=win, bias=bool(bias), res=bool(res), G=16 if stats else 0, outF=bool(outF), outB=bool(outB), cfg=force,
+                splitk=2 if splitk else 0, ldf=ldf, out_hw=0, out_stride=0, out_off=0, outF_rows=0)
+    M = B * ((Hin + 2 * geo[6] - geo[4]) // geo[5] + 1) * ((Win + 2 * geo[6] - geo[4]) // geo[5] + 1)
+    if remap:      # remap = images per launch: the rows of image i go to i * out_stride + out_off, 3 more rows behind the last one
+        args.update(REMAP, out_hw=M // remap)
+        args["outF_rows"] = (remap - 1) * REMAP["out_stride"] + REMAP["out_off"] + M // remap + 3
+    elif outF:
+        args["outF_rows"] = M + 1
+    return dict(tag=tag, entry="uni_gemm_stacked", args=args,
+                ref="torch fp64: F.conv2d of the (B, Cin, Hin, Win) batch of the unrounded fp32 operands (every sample padded on its own) + activation + residual; "
+                    "per-sample fp64 group sums", bound=B_GEMM, bound_from="test_gemm_h2")
+
+
+# (conv, stats, splitk, outF, outB, res, act) as above.  Every family as an implicit GEMM, with GroupNorm sums and with both; the map of a
+# case is the one whose boundary pattern its tile height has not had yet in that family
+def _family(fam, kernel, code, force, plain, conv3, m_conv, m_stats, m_both):
+    return [_gemms(fam, kernel, code, force, 1, 0, 0, 1, 0, 0, 0, conv3, m_conv), _gemms(fam, kernel, code, force, 0, 1, 0, 1, 0, 0, 0, plain, m_stats),
+            _gemms(fam, kernel, code, force, 1, 1, 0, 1, 0, 0, 0, conv3, m_both)]
+
+
+STACKED = []
+STACKED += _family("f32", "f32", 2211, 0, PLAIN, CONV3, MAP_A, MAP_B, MAP_A)
+STACKED += _family("h2", "h2", 2222, 22, PLAIN, CONV3, MAP_A, MAP_B, MAP_B)
+STACKED += _family("h2", "h2", 2211, 11, PLAIN, CONV3, MAP_B, MAP_A, MAP_B)
+STACKED += _family("h2", "h2d", 22113, 331, PLAIN, CONV3, MAP_A, MAP_A, MAP_B)
+STACKED += _family("h2", "h2d", 22123, 332, PLAIN, CONV3, MAP_B, MAP_B, MAP_A)
+STACKED += _family("h2", "h2d", 42232, 346, PLAIN384, CONV384, MAP_A, MAP_A, MAP_B)
+STACKED += _family("h2", "h2q_outF", 188, 188, PLAIN, CONV3, MAP_A, MAP_A, MAP_B)
+STACKED += [_gemms("h2", "h2q_outB", 188, 188, 1, 0, 0, 0, 1, 0, 1, CONV3, MAP_B)]
+# K ranges: the partial launch (64 x 64 deep tile, as the one-sample cases) and the reduce kernel, whose grid is (cdiv(Mper, 8), B): 221 and 63 are
+# no multiples of 8, so the last block of every sample is ragged
+STACKED += [_gemms("h2", "h2d", 22113, 331, 0, 0, 1, 1, 0, 1, 0, PLAIN, MAP_A), _gemms("h2", "h2d", 22113, 331, 1, 1, 1, 1, 0, 0, 0, CONV3, MAP_B, bias=False),
+            _gemms("h2", "h2d", 22113, 331, 0, 0, 1, 1, 0, 1, 0, PLAIN, MAP_B, reduce_tag=True),
+            _gemms("h2", "h2d", 22113, 331, 1, 1, 1, 1, 0, 0, 0, CONV3, MAP_A, bias=False, reduce_tag=True)]
+# the head's remapped outputs: reg / obj predictions (N = 5, sigmoid on every column and on the columns >= 4), one launch over the 3 x 221 rows
+# of three images as the engine launches it (a 1x1 convolution over [B * hw] rows: remap=1 stacked=0), and the controller conv (3x3, N = 169,
+# ld 169, three stacked samples: remap=1 stacked=1), on the direct-epilogue tiles and the exact-fp32 kernel
+HEAD5_ROWS = (663, 1, 1)
+for _fam, _kernel, _code, _force in (("h2", "h2", 2211, 11), ("h2", "h2", 2221, 21), ("f32", "f32", 2211, 0)):
+    STACKED += [_gemms(_fam, _kernel, _code, _force, 0, 0, 0, 1, 0, 0, 4, HEAD5, HEAD5_ROWS, remap=3),
+                _gemms(_fam, _kernel, _code, _force, 0, 0, 0, 1, 0, 0, 4, HEAD5, HEAD5_ROWS, remap=3, win=4),
+                _gemms(_fam, _kernel, _code, _force, 1, 0, 0, 1, 0, 0, 0, CTRL169, MAP_A, remap=3)]
+# dispatched by the census and not among the above: the one-frame controller conv of the fp32 model (remap=1 on one sample: out_hw = Mper, the
+# level's rows land at out_off), and the 64 x 64 deep tile as a conv + ReLU into operand rows on stacked samples
+STACKED += [_gemms("f32", "f32", 2211, 0, 1, 0, 0, 1, 0, 0, 0, CTRL169, (13, 17, 1), remap=1),
+            _gemms("h2", "h2d", 22113, 331, 1, 0, 0, 0, 1, 0, 1, CONV3, MAP_A)]
+CASE_LIST += STACKED
+
+
+def gemm_stacked_problem(a, bound=B_GEMM):
+    """Inputs, fp64 reference and tolerances of a uni_gemm_stacked case, on the CPU (shared by the GPU runner and the CPU self-check of the
+    cases).  raw = conv + bias as (M, N) rows, finish(raw) = activation window + residual, stats(raw, shift) = per-sample group sums of the
+    rows [b Mper + shift, (b + 1) Mper + shift), orow = the outF row of every output row."""
+    import torch
+    import torch.nn.functional as F
+    acts = {0: lambda t: t, 1: F.relu, 2: F.gelu, 3: F.silu, 4: torch.sigmoid}
+    Hin, Win, Cin, N, k, stride, pad = a["geo"]
+    B, act, G, c0 = a["B"], a["act"], a["G"], a["act_col0"]
+    g = torch.Generator().manual_seed(Hin * 7 + N + a["cfg"] + act + 31 * B + c0)
+    sb = torch.arange(B).float().reshape(B, 1, 1, 1)
+    x = torch.randn(B, Cin, Hin, Win, generator=g) * 3.0 * (1.0 + sb) + 0.5 * sb
+    w = torch.randn(N, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
+    bias = torch.randn(N, generator=g) * 0.1 if a["bias"] else None
+    bd = bias.double() if a["bias"] else None
+
+    def rows(t):
+        return t.permute(0, 2, 3, 1).reshape(-1, N)
+
+    raw = rows(F.conv2d(x.double(), w.double(), bd, stride=stride, padding=pad))
+    mag = rows(F.conv2d(x.abs().double(), w.abs().double(), None, stride=stride, padding=pad))
+    M = raw.shape[0]
+    Mper = M // B
+    res = torch.randn(M, N + 4, generator=g) if a["res"] else None
+
+    def finish(r):
+        return torch.cat([r[:, :c0], acts[act](r[:, c0:])], 1) + (res[:, :N].double() if a["res"] else 0)
+
+    def stats(r, shift=0):
+        out = torch.zeros(B, G, 2, dtype=torch.float64)
+        for b in range(B):
+            grp = r[b * Mper + shift:(b + 1) * Mper + shift].reshape(-1, G, N // G)
+            out[b, :, 0], out[b, :, 1] = grp.sum((0, 2)), (grp ** 2).sum((0, 2))
+        return out
+
+    m = torch.arange(M)
+    orow = (m // a["out_hw"]) * a["out_stride"] + a["out_off"] + m % a["out_hw"] if a["out_hw"] else m
+    P = dict(x=x, w=w, bias=bias, res=res, raw=raw, exp=finish(raw), tol=(mag * bound + 1e-6) * 1.2, M=M, Mper=Mper, orow=orow, finish=finish, stats=stats, rows=rows)
+    if G:
+        P["stats_ref"] = stats(raw)
+        P["stats_tol"] = STATS_ATOL + STATS_RTOL * P["stats_ref"].abs()
+    return P
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rest
@@ -270,6 +389,28 @@ CASE_LIST += [
     _simple("condinst final=1", "uni_condinst_masks", dict(n=5, H8=20, W8=28), "oracle fp64: aligned_bilinear(dynamic_mask_head)", 2e-5, "test_condinst_masks"),
 ]
 
+# ---------------------------------------------------------------------------------------------------------------- glue launchers between context buffers
+# the `_ex` entries of the launchers the engine runs between its own buffers: one case per census tag, one (7, 5) map or three stacked ones
+# (every sample / frame drawn on its own scale), C as the stage that runs them: 256 interaction tokens, 128 -> 32 PixelShuffle channels.
+# Operand rows: the restated row bound of the format, fp32 rows exact (run_cast).  fp32 results of fp32 arithmetic (add_aligned_bilinear,
+# pos_embed): 4 x the distance of the oracle's own fp32 evaluation from its fp64 one, computed by the runner; `bound` is the cap on that.
+def _glue(tag, entry, ref, fmt=1, bound=B_H2_ROWS, bound_from="test_dwconv7_ln_batched_all_formats", **args):
+    return dict(tag=tag, entry=entry, args=dict(fmt=fmt, h=7, w=5, **args), ref=ref, bound=bound, bound_from=bound_from)
+
+
+for _fmt, _B in ((1, 1), (2, 1), (2, 3)):
+    _t = "fmt=%s batched=%d" % (("bf16", "f32", "h2")[_fmt], _B > 1)
+    CASE_LIST += [
+        _glue("cast_operand_pair " + _t, "uni_cast_operand_pair_ex", "the fp64 value of the fp32 inputs, laid out [B][2][hw][C]", _fmt, B=_B, C=256),
+        _glue("pixel_shuffle_bf16 " + _t, "uni_pixel_shuffle_ex", "torch fp64: F.pixel_shuffle(., 2) of the (B, C, h, w) map", _fmt, B=_B, C=128),
+        _glue("add_pos_bf16 " + _t, "uni_add_pos_ex", "torch fp64: src + pos + lvl per frame of the pair", _fmt, B=_B, C=256)]
+    if _fmt == 2:      # (fmt=f32 batched=0 is uni_msda_tokens, above)
+        CASE_LIST += [_glue("msda_fused " + _t, "uni_msda_tokens_ex", "oracle fp64: msda_core on softmax weights and ref + off / (W, H)", _fmt, B=_B)]
+CASE_LIST += [_glue("add_aligned_bilinear factor=%d batched=%d" % (_f, _B > 1), "uni_add_aligned_bilinear_ex", "oracle fp64: dst + aligned_bilinear(src, factor) per sample",
+                    bound=1e-5, bound_from="test_decode_outputs_device", B=_B, C=32, factor=_f) for _f in (2, 4) for _B in (1, 3)]
+CASE_LIST += [_glue("pos_embed", "uni_pos_embed_ex", "oracle fp64: pos_embed (bilinear resize of the [col | row] table grid)", bound=1e-5,
+                    bound_from="test_decode_outputs_device", sz=40, nf=128)]
+
 # ---------------------------------------------------------------------------------------------------------------- not dispatched by the census
 # Builds no census workload reaches (listed under not_dispatched in variant_census.json): the unpacked 12-wave C = 384 build needs a map with
 # enough strips but too few strip groups, and no model configuration has C = 512.
@@ -283,25 +424,16 @@ CASE_LIST += [
 CASES = {c["tag"]: c for c in CASE_LIST}
 
 # ---------------------------------------------------------------------------------------------------------------- context-only tags
-# Launchers that keep NO context-free entry point; nothing else may be parked here (tests/test_variant_cases_cpu.py).
-CTX_ONLY_ALLOWED = ("cast_operand_pair", "pixel_shuffle_bf16", "add_pos_bf16", "add_aligned_bilinear", "pos_embed", "gemm:", "msda_fused")
+# Launchers that keep NO context-free entry point; nothing else may be parked here (tests/test_variant_cases_cpu.py).  Every launcher the
+# census dispatches has one now: the lists stay for the next launcher that is written against context buffers only.
+CTX_ONLY_ALLOWED = ()
 CTX_ONLY = [
     # (tag pattern, reason, model-level test that runs it)
-    (r"^cast_operand_pair ", "token layout [B][2][hw] of the interaction stage, built from context buffers", "test_batched_frames_equal_single_frame_runs"),
-    (r"^pixel_shuffle_bf16 ", "upsample-stage scatter between context buffers", "test_batched_frames_equal_single_frame_runs"),
-    (r"^add_pos_bf16 ", "position + level embedding add of the interaction stage", "test_batched_frames_equal_single_frame_runs"),
-    (r"^add_aligned_bilinear ", "FPN top-down / mask-branch upsample-add between context buffers", "test_batched_frames_equal_single_frame_runs"),
-    (r"^pos_embed$", "learned position embedding table lives in the context", "test_tiny_320_vs_reference_golden"),
-    (r"^gemm:.* remap=1 stacked=[01]$", "outF row remap of the head outputs (out_hw) is set by the engine only", "test_batched_frames_equal_single_frame_runs"),
-    (r"^gemm:.* remap=[01] stacked=1$", "stacked samples (M != Mper): per-sample statistics slots and conv halos", "test_batched_frames_equal_single_frame_runs"),
-    (r"^gemm:splitk_reduce .* stacked=1$", "stacked samples (M != Mper) in the split-K reduce", "test_batched_frames_equal_single_frame_runs"),
-    (r"^msda_fused fmt=(bf16|h2) ", "operand-format output of the fused sampler (uni_msda_tokens is fp32 only)", "test_batched_frames_equal_single_frame_runs"),
 ]
 
-
 def gemm_twin(tag):
-    """a context-only GEMM / split-K reduce tag with the row-remap and stacked-sample switches at 0: the same template instantiation on one
-    sample, which must have a case of its own (only the per-sample arithmetic needs a context)"""
+    """a GEMM / split-K reduce tag with the row-remap and stacked-sample switches at 0: the same template instantiation on one sample.  The
+    census closure asks for it for every GEMM tag parked in CTX_ONLY; none may be parked there any more (uni_gemm_stacked sets both switches)"""
     return re.sub(r"\bremap=1\b", "remap=0", re.sub(r"\bstacked=1\b", "stacked=0", tag))
 
 

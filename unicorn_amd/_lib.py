@@ -129,6 +129,14 @@ PROTOS = {
     "uni_gemm_ex": (c_i, [c_f, c_i, c_f, C.c_float, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_i,
                           C.c_void_p]),
     "uni_cast_f32": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, C.c_void_p]),
+    "uni_gemm_stacked": (c_i, [c_f, c_i, c_f, C.c_float] + [c_i] * 11 + [c_f, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i,
+                               C.c_void_p]),
+    "uni_cast_operand_pair_ex": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, C.c_void_p]),
+    "uni_pixel_shuffle_ex": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p]),
+    "uni_add_pos_ex": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, C.c_void_p]),
+    "uni_add_aligned_bilinear_ex": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
+    "uni_pos_embed_ex": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
+    "uni_msda_tokens_ex": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, C.c_void_p]),
     "uni_stem": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_f, C.c_void_p]),
 }
 # fp32 / fp64 operator pairs whose two entries take the same arguments (device pointers travel as void*): the `_f64` prototype is the fp32 one.

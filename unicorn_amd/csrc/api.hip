@@ -62,6 +62,25 @@ static int gemm_geometry(GemmArgs& g, const char* what, const void* A, int lda, 
     UNI_REQUIRE(g.M == M, "%s: M=%d does not match conv geometry (%d)", what, M, g.M);
     return 0;
 }
+// partial-tile slab of the split-K path for the context-free entries (uni_gemm_h2, uni_gemm_stacked): one grow-only buffer PER DEVICE
+// (the engine takes its slabs from the context workspace; these entries have no context)
+static int gemm_entry_slab(float** slab, size_t need) {
+    static std::mutex mu;
+    static std::map<int, std::pair<float*, size_t>> slabs;
+    int dev = 0;
+    UNI_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    auto& sl = slabs[dev];
+    if (need > sl.second) {
+        UNI_CHECK_HIP(hipDeviceSynchronize());
+        if (sl.first) (void)hipFree(sl.first);
+        sl = {nullptr, 0};
+        UNI_CHECK_HIP(hipMalloc(&sl.first, need));
+        sl.second = need;
+    }
+    *slab = sl.first;
+    return 0;
+}
 #define API(expr) do { int _rc = (expr); if (_rc) return _rc; return post_launch(); } while (0)
 
 extern "C" {
@@ -589,6 +608,41 @@ int uni_gemm_ex(const void* A, int lda, const void* w_packed, float wscale, int 
     g.wscale = fmt == FMT_H2 ? wscale : 1.f;
     API(launch_gemm(g, S(stream)));
 }
+int uni_gemm_stacked(const void* A, int lda, const void* w_packed, float wscale, int fmt, int B, int M, int N, int Hin, int Win, int Cin, int KH, int KW,
+                     int stride, int pad, const float* bias, int act, int act_col0, const float* residual, int ldr, float* outF, int ldf, int out_hw,
+                     int out_stride, int out_off, int outF_rows, void* outB, int ldb, double* gn_stats, int cpg, int splitk, int force_cfg,
+                     uni_stream_t stream) {
+    UNI_REQUIRE(A && w_packed && (outF || outB), "gemm_stacked: NULL argument");
+    UNI_REQUIRE(fmt >= 0 && fmt <= 2 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && Cin > 0 && N > 0 && Hin > 0 && Win > 0, "gemm_stacked: fmt=%d / bad geometry", fmt);
+    UNI_REQUIRE(act_col0 >= 0 && act_col0 <= N && force_cfg >= 0 && force_cfg < 1000, "gemm_stacked: act_col0=%d force_cfg=%d (tile configuration only)", act_col0, force_cfg);
+    UNI_REQUIRE(B >= 1 && B < 128, "gemm_stacked: B=%d (1 .. 127 samples)", B);
+    UNI_REQUIRE(M > 0 && M % B == 0, "gemm_stacked: M=%d is not a multiple of B=%d", M, B);
+    GemmArgs g;
+    if (int rc = gemm_geometry(g, "gemm_stacked", A, lda, w_packed, M / B, N, Hin, Win, Cin, KH, KW, stride, pad)) return rc;      // Hin, Win: per sample
+    g.Mper = g.M; g.M = M;
+    UNI_REQUIRE(lda >= Cin && (!residual || ldr >= N) && (!outF || ldf >= N) && (!outB || ldb >= N), "gemm_stacked: lda=%d ldr=%d ldf=%d ldb=%d", lda, ldr, ldf, ldb);
+    UNI_REQUIRE(out_hw >= 0 && out_stride >= 0 && out_off >= 0 && outF_rows >= 0, "gemm_stacked: out_hw=%d out_stride=%d out_off=%d outF_rows=%d", out_hw, out_stride, out_off, outF_rows);
+    if (out_hw > 0) {     // the engine's remap rule: row -> (row / out_hw) * out_stride + out_off + row % out_hw
+        UNI_REQUIRE(outF && M % out_hw == 0 && out_stride >= out_hw, "gemm_stacked: row remap needs out_f32, M=%d a multiple of out_hw=%d and out_stride=%d >= out_hw", M, out_hw, out_stride);
+        UNI_REQUIRE((long)(M / out_hw - 1) * out_stride + out_off + out_hw <= (long)outF_rows, "gemm_stacked: the remapped rows end behind outF_rows=%d", outF_rows);
+    } else if (outF) {
+        UNI_REQUIRE(outF_rows >= M, "gemm_stacked: outF_rows=%d < M=%d", outF_rows, M);
+    }
+    if (gn_stats) UNI_REQUIRE(cpg > 0 && N % cpg == 0 && N / cpg <= 32 && act == ACT_NONE, "gemm_stacked: statistics need cpg=%d to divide N into at most 32 groups and no activation", cpg);
+    UNI_REQUIRE(splitk >= 0 && splitk <= 64, "gemm_stacked: splitk=%d", splitk);
+    g.bias = bias; g.act = act; g.act_col0 = act_col0; g.res = residual; g.ldr = ldr; g.outF = outF; g.ldf = ldf;
+    g.out_hw = out_hw; g.out_stride = out_hw ? out_stride : 0; g.out_off = out_hw ? out_off : 0;
+    g.outB = reinterpret_cast<bf16*>(outB); g.ldb = ldb; g.stats = gn_stats; g.cpg = cpg; g.force_cfg = force_cfg; g.b32 = fmt;
+    g.wscale = fmt == FMT_H2 ? wscale : 1.f;
+    if (splitk > 1) {     // launch_gemm_h2's conditions, before the slab is taken
+        UNI_REQUIRE(fmt == FMT_H2 && outF && !outB && act == ACT_NONE && !out_hw, "gemm_stacked: split-K needs f16x2 operands, fp32 output only, no activation, no row remap");
+        UNI_REQUIRE(N % 8 == 0 && ldf % 4 == 0 && ((uintptr_t)outF & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0) &&
+                    (!residual || (ldr % 4 == 0 && ((uintptr_t)residual & 15) == 0)), "gemm_stacked: split-K needs the staged epilogue (N %% 8, ldf / ldr %% 4, 16-byte aligned pointers)");
+        g.splitk = splitk;
+        if (int rc = gemm_entry_slab(&g.slab, (size_t)splitk * M * N * sizeof(float))) return rc;
+    }
+    API(launch_gemm(g, S(stream)));
+}
 int uni_pack_weight_h2(const float* w, int N, int Cin, int KH, int KW, void* out, float* wscale_out) {
     UNI_REQUIRE(w && out && wscale_out && N > 0 && Cin > 0, "pack_weight_h2: bad argument");
     float mx = 0.f;
@@ -611,23 +665,8 @@ int uni_gemm_h2(const void* A, int lda, const void* w_packed, float wscale, int 
     g.splitk = force_cfg / 1000000;
     g.force_cfg = force_cfg % 1000;
     g.Mper = g.M;
-    if (g.splitk > 1) {                       // partial-tile slab of the split-K path: one grow-only buffer PER DEVICE for this test / bench entry
-        static std::mutex mu;                 // (the engine takes its slabs from the context workspace; this entry has no context)
-        static std::map<int, std::pair<float*, size_t>> slabs;
-        int dev = 0;
-        UNI_CHECK_HIP(hipGetDevice(&dev));
-        const size_t need = (size_t)g.splitk * g.M * g.N * sizeof(float);
-        std::lock_guard<std::mutex> lk(mu);
-        auto& sl = slabs[dev];
-        if (need > sl.second) {
-            UNI_CHECK_HIP(hipDeviceSynchronize());
-            if (sl.first) (void)hipFree(sl.first);
-            sl = {nullptr, 0};
-            UNI_CHECK_HIP(hipMalloc(&sl.first, need));
-            sl.second = need;
-        }
-        g.slab = sl.first;
-    }
+    if (g.splitk > 1)
+        if (int rc = gemm_entry_slab(&g.slab, (size_t)g.splitk * g.M * g.N * sizeof(float))) return rc;
     API(launch_gemm(g, S(stream)));
 }
 size_t uni_mlp_blob_bytes(int C) { return mlp_fused_supported(C) ? mlp_blob_bytes(C) : 0; }
@@ -722,6 +761,41 @@ int uni_msda_tokens(const float* value, const float* offaw, int ldo, int B, int 
     MsdaFusedArgs m;
     m.value = value; m.offaw = offaw; m.ldo = ldo; m.h = h; m.w = w; m.B = B;
     m.out = reinterpret_cast<bf16*>(out); m.b32 = FMT_F32;
+    API(launch_msda_fused(m, S(stream)));
+}
+// ---- context-free entries of the glue launchers the engine runs between context buffers (arguments as the launchers of kernels.h; fmt =
+// operand format of `out`).  The divisibility and alignment the kernels rely on are checked here: the launchers themselves trust the engine.
+int uni_cast_operand_pair_ex(const float* x0, const float* x1, void* out, int B, int hw, int C, int fmt, uni_stream_t stream) {
+    UNI_REQUIRE(x0 && x1 && out && B > 0 && hw > 0 && C > 0 && C % 8 == 0 && fmt >= 0 && fmt <= 2, "cast_operand_pair_ex: B=%d hw=%d C=%d fmt=%d", B, hw, C, fmt);
+    UNI_REQUIRE((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)out) & 15) == 0, "cast_operand_pair_ex: pointers must be 16-byte aligned");
+    API(launch_cast_operand_pair(x0, x1, reinterpret_cast<bf16*>(out), hw, C, B, S(stream), fmt));
+}
+int uni_pixel_shuffle_ex(const float* x, void* out, int B, int h, int w, int C, int fmt, uni_stream_t stream) {
+    UNI_REQUIRE(x && out && B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0 && fmt >= 0 && fmt <= 2, "pixel_shuffle_ex: B=%d h=%d w=%d C=%d fmt=%d", B, h, w, C, fmt);
+    UNI_REQUIRE(fmt != FMT_H2 || C % 32 == 0, "pixel_shuffle_ex: f16x2 rows need C / 4 = %d a multiple of 8", C / 4);
+    API(launch_pixel_shuffle_bf16(x, reinterpret_cast<bf16*>(out), h, w, C, S(stream), fmt, B));
+}
+int uni_add_pos_ex(const float* src, const float* pos0, const float* pos1, const float* lvl, void* out, int B, int hw, int C, int fmt,
+                   uni_stream_t stream) {
+    UNI_REQUIRE(src && pos0 && pos1 && lvl && out && B > 0 && hw > 0 && C > 0 && C % 8 == 0 && fmt >= 0 && fmt <= 2, "add_pos_ex: B=%d hw=%d C=%d fmt=%d", B, hw, C, fmt);
+    UNI_REQUIRE((((uintptr_t)src | (uintptr_t)pos0 | (uintptr_t)pos1 | (uintptr_t)lvl | (uintptr_t)out) & 15) == 0, "add_pos_ex: pointers must be 16-byte aligned");
+    API(launch_add_pos_bf16(src, pos0, pos1, lvl, reinterpret_cast<bf16*>(out), hw, C, S(stream), fmt, B));
+}
+int uni_add_aligned_bilinear_ex(const float* src, int B, int h, int w, int C, int factor, float* dst, uni_stream_t stream) {
+    UNI_REQUIRE(src && dst && B > 0 && B < 65536 && h > 0 && w > 0 && C > 0 && C % 4 == 0 && factor >= 1, "add_aligned_bilinear_ex: B=%d h=%d w=%d C=%d factor=%d", B, h, w, C, factor);
+    UNI_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "add_aligned_bilinear_ex: pointers must be 16-byte aligned");
+    API(launch_add_aligned_bilinear(src, h, w, C, factor, dst, S(stream), B));
+}
+int uni_pos_embed_ex(const float* row_embed, const float* col_embed, int sz, int nf, int h, int w, float* out_nhwc, uni_stream_t stream) {
+    UNI_REQUIRE(row_embed && col_embed && out_nhwc && sz > 0 && nf > 0 && h > 0 && w > 0 && (long)h * w * 2 * nf < (1L << 31), "pos_embed_ex: sz=%d nf=%d h=%d w=%d", sz, nf, h, w);
+    API(launch_pos_embed(row_embed, col_embed, sz, nf, out_nhwc, h, w, S(stream)));
+}
+int uni_msda_tokens_ex(const float* value, const float* offaw, int ldo, int B, int h, int w, void* out, int fmt, uni_stream_t stream) {
+    UNI_REQUIRE(value && offaw && out && B > 0 && h > 0 && w > 0 && ldo >= 192 && fmt >= 0 && fmt <= 2, "msda_tokens_ex: bad argument (fmt=%d)", fmt);
+    UNI_REQUIRE((((uintptr_t)value | (uintptr_t)out) & 15) == 0, "msda_tokens_ex: value / out must be 16-byte aligned");
+    MsdaFusedArgs m;
+    m.value = value; m.offaw = offaw; m.ldo = ldo; m.h = h; m.w = w; m.B = B;
+    m.out = reinterpret_cast<bf16*>(out); m.b32 = fmt;
     API(launch_msda_fused(m, S(stream)));
 }
 int uni_groupnorm_act(const float* x, const double* stats, const float* gamma, const float* beta, float eps, int M, int C, int G,
