@@ -662,7 +662,7 @@ size_t uni_mlp_blob_bytes(int C);
 int uni_mlp_pack(const float* w1_host, const float* w2_host, const float* gamma_host, int C, int layout, void* blob_host,
                  float* ws1_out, float* ws2_out);
 int uni_mlp_fused(const void* a_h2, int lda, const void* blob_dev, const float* b1, const float* b2, float ws1, float ws2,
-                  const float* residual, int ldr, float* out, int ldo, void* out_h2, int ldb, int M, int C, int layout, int dbg,
+                  const float* residual, int ldr, float* out, int ldo, void* out_h2, int ldb, int M, int C, int layout,
                   uni_stream_t stream);
 int uni_layernorm(const float* x, int ldx, const float* gamma, const float* beta, float eps, int M, int C, float* outF,
                   uint16_t* outB, uni_stream_t stream);

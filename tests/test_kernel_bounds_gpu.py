@@ -645,14 +645,14 @@ def test_mlp_fused(L, C_, M, layout, alias, with_outb):
         ldr = ldo
     pout = res.clone()
     poutb = torch.zeros((M, C_), device=DEV, dtype=torch.int32) if with_outb else None
-    L.check(L.lib().uni_mlp_fused(P(A), C_, P(blob), P(b1d), P(b2d), ws1, ws2, P(pout), C_, P(pout), C_, P(poutb), C_, M, C_, layout, 0,
+    L.check(L.lib().uni_mlp_fused(P(A), C_, P(blob), P(b1d), P(b2d), ws1, ws2, P(pout), C_, P(pout), C_, P(poutb), C_, M, C_, layout,
                                   L.stream_ptr()), "mlp_fused")
     gA, gbl, gb1, gb2 = gin("a_h2", A, ld=lda, poison="nan16"), gin("blob", blob.view(torch.float16), poison="nan16"), gin("b1", b1d), gin("b2", b2d)
     go = gout("out", M, C_, torch.float32, ld=ldo, init=res if alias else None)
     gr = None if alias else gin("residual", res, ld=ldr)
     gob = gout("out_h2", M, C_, torch.int32, ld=ldb) if with_outb else None
     L.check(L.lib().uni_mlp_fused(P(gA), lda, P(gbl), P(gb1), P(gb2), ws1, ws2, P(go if alias else gr), ldr, P(go), ldo, P(gob), ldb, M, C_,
-                                  layout, 0, L.stream_ptr()), "mlp_fused")
+                                  layout, L.stream_ptr()), "mlp_fused")
     sync_check(gA, gbl, gb1, gb2, go, gr, gob)
     go.check_equal(pout)
     got = go.payload().double()

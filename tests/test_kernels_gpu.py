@@ -1025,7 +1025,7 @@ def test_mlp_fused(L, C_, M, layout, with_outb):
     outb = torch.zeros((M + pad, C_), device="cuda", dtype=torch.int32) if with_outb else None
     b1d, b2d = b1.cuda(), (gamma * b2).cuda()
     L.check(L.lib().uni_mlp_fused(L.ptr(A), C_, L.ptr(blob), L.ptr(b1d), L.ptr(b2d), ws1, ws2, L.ptr(out), C_,
-                                  L.ptr(out), C_, L.ptr(outb), C_, M, C_, layout, 0, L.stream_ptr()), "mlp_fused")
+                                  L.ptr(out), C_, L.ptr(outb), C_, M, C_, layout, L.stream_ptr()), "mlp_fused")
     torch.cuda.synchronize()
     got = out[:M].cpu().double()
     scale = max(1.0, ref.abs().max().item())
@@ -1055,7 +1055,7 @@ def test_mlp_fused_matches_unfused_pair(L):
     fused = res.clone()
     b1d, b2d = b1.cuda(), (gamma * b2).cuda()
     L.check(L.lib().uni_mlp_fused(L.ptr(A), C_, L.ptr(blob), L.ptr(b1d), L.ptr(b2d), ws1, ws2, L.ptr(fused), C_,
-                                  L.ptr(fused), C_, None, 0, M, C_, 0, 0, L.stream_ptr()), "mlp_fused")
+                                  L.ptr(fused), C_, None, 0, M, C_, 0, L.stream_ptr()), "mlp_fused")
     W1p, s1 = pack_weight_h2(L, w1.reshape(4 * C_, C_, 1, 1))
     W2p, s2 = pack_weight_h2(L, (gamma[:, None] * w2).reshape(C_, 4 * C_, 1, 1))
     hid = torch.zeros((M, 4 * C_), device="cuda", dtype=torch.int32)

@@ -376,7 +376,7 @@ def run_mlp(L, a, bound):
     outb = torch.zeros((M + 64, C_), device="cuda", dtype=torch.int32) if a["outB"] else None
     b1d, b2d = b1.cuda(), (gamma * b2).cuda()
     L.check(L.lib().uni_mlp_fused(L.ptr(A), C_, L.ptr(blob_d), L.ptr(b1d), L.ptr(b2d), s1.value, s2.value, L.ptr(out), C_, L.ptr(out), C_, L.ptr(outb), C_, M, C_,
-                                  layout, 0, L.stream_ptr()), "mlp_fused")
+                                  layout, L.stream_ptr()), "mlp_fused")
     torch.cuda.synchronize()
     assert (out[M:] == 777.0).all() and (outb is None or (outb[M:] == 0).all())
     scale = max(1.0, ref.abs().max().item())

@@ -378,10 +378,10 @@ CASE_LIST += [
     _simple("stem 4px CG=48 S=5 batched=0", "uni_stem_ex", dict(C=192, B=1, H=16, W=32), "oracle fp64: F.conv2d(stride 4) + ln_channels_first", 2e-4, "test_stem"),
     _simple("stem 1px CG=24 S=10 batched=0", "uni_stem_ex", dict(C=96, B=1, H=16, W=20), "oracle fp64: F.conv2d(stride 4) + ln_channels_first", 2e-4, "test_stem"),      # W % 16 != 0 (not dispatched: every census width is a multiple of 16)
     _simple("stem 4px CG=48 S=5 batched=1", "uni_stem_ex", dict(C=192, B=2, H=16, W=32), "oracle fp64: F.conv2d(stride 4) + ln_channels_first", 2e-4, "test_stem"),
-    _simple("mlp_fused layout=0 C=96 outB=0 dbg=0", "uni_mlp_fused", dict(C=96, M=300, layout=0, outB=False), "torch fp64 on the f16x2-decoded operand", 4e-6, "test_mlp_fused"),
-    _simple("mlp_fused layout=1 C=192 outB=0 dbg=0", "uni_mlp_fused", dict(C=192, M=300, layout=1, outB=False), "torch fp64 on the f16x2-decoded operand", 4e-6, "test_mlp_fused"),
-    _simple("mlp_fused layout=1 C=256 outB=0 dbg=0", "uni_mlp_fused", dict(C=256, M=300, layout=1, outB=False), "torch fp64 on the f16x2-decoded operand", 4e-6, "test_mlp_fused"),
-    _simple("mlp_fused layout=1 C=256 outB=1 dbg=0", "uni_mlp_fused", dict(C=256, M=300, layout=1, outB=True), "torch fp64 on the f16x2-decoded operand", 4e-6, "test_mlp_fused"),
+    _simple("mlp_fused layout=0 C=96 outB=0", "uni_mlp_fused", dict(C=96, M=300, layout=0, outB=False), "torch fp64 on the f16x2-decoded operand", 4e-6, "test_mlp_fused"),
+    _simple("mlp_fused layout=1 C=192 outB=0", "uni_mlp_fused", dict(C=192, M=300, layout=1, outB=False), "torch fp64 on the f16x2-decoded operand", 4e-6, "test_mlp_fused"),
+    _simple("mlp_fused layout=1 C=256 outB=0", "uni_mlp_fused", dict(C=256, M=300, layout=1, outB=False), "torch fp64 on the f16x2-decoded operand", 4e-6, "test_mlp_fused"),
+    _simple("mlp_fused layout=1 C=256 outB=1", "uni_mlp_fused", dict(C=256, M=300, layout=1, outB=True), "torch fp64 on the f16x2-decoded operand", 4e-6, "test_mlp_fused"),
     _simple("msda_fused fmt=f32 batched=0", "uni_msda_tokens", dict(B=1, h=7, w=5), "oracle fp64: msda_core on softmax weights and ref + off / (W, H)", 2e-5, "test_msda_wave_kernel_tokens"),
     _simple("prior_pyramid", "uni_prior_pyramid", dict(K=3, H8=44, W8=76), "oracle fp64: prior_pyramid", 1e-6, "test_prior_pyramid_label_map"),
     _simple("decode batched=0", "uni_decode_outputs", dict(B=1, H=320, W=352, nch=6), "oracle fp64: decode_outputs", 1e-5, "test_decode_outputs_device"),

@@ -1,5 +1,4 @@
-"""Interaction stage (bottleneck + deformable encoder layer, MSDA inside) for B frame pairs at 800x1280; UNI_MSDA_V1=1 selects the
-round-1 lane-per-channel sampler for A/B."""
+"""Interaction stage (bottleneck + deformable encoder layer, MSDA inside) for B frame pairs at 800x1280."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -16,4 +15,4 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 e0.record()
 for _ in range(10): m(seq_dict0=d0, seq_dict1=d1, mode="interaction")
 e1.record(); torch.cuda.synchronize()
-print("interaction B=%d: %.3f ms per call (%s sampler)" % (B, e0.elapsed_time(e1) / 10, "lane-per-channel" if os.environ.get("UNI_MSDA_V1") else "wave-per-(token,head)"))
+print("interaction B=%d: %.3f ms per call" % (B, e0.elapsed_time(e1) / 10))

@@ -1,6 +1,7 @@
 """Fused ConvNeXt MLP (mlp_fused.hip) vs the two launches it replaces (uni_gemm_h2: pwconv1 + GELU, pwconv2 + residual) on the
-shapes of the 800x1280 large model at GEMM_SCALE frames per launch.  TF = fp32-equivalent TFLOP/s over both GEMMs.
-    python tools/mlp_bench.py [dbg ...]        dbg: 0 full kernel, 1 no DMA, 2 no MFMA (C = 192 only)"""
+shapes of the 800x1280 large / tiny models at GEMM_SCALE frames per launch: layout 0 (32-row waves) and, where it exists, layout 1 (16-row
+waves), each with its largest deviation from the two-launch result.  TF = fp32-equivalent TFLOP/s over both GEMMs.
+    python tools/mlp_bench.py"""
 import ctypes as C
 import os
 import sys
@@ -15,7 +16,6 @@ lib = L.lib()
 SCALE = int(os.environ.get("GEMM_SCALE", "16"))
 SHAPES = [("stage0 C=192", 192, 64000), ("head.l0 C=256", 256, 16000), ("head.l1 C=256", 256, 4000), ("tiny.s0 C=96", 96, 64000),
           ("tiny.s1 C=192", 192, 16000)]
-dbgs = [int(a) for a in sys.argv[1:]] or [0]
 
 
 def timeit(fn, n=6, warm=3):
@@ -70,16 +70,10 @@ for name, Cc, m1 in SHAPES:
     t_un = timeit(unfused)
     line = "%-16s M=%8d | unfused %7.1f us %6.1f TF |" % (name, M, t_un * 1e3, flop / t_un / 1e9)
     for lay in sorted(blobs):
-        for d in dbgs:
-            if d and Cc != 192:
-                continue
-            def fused():
-                L.check(lib.uni_mlp_fused(L.ptr(A), Cc, L.ptr(blobs[lay]), L.ptr(b1d), L.ptr(b2d), s1.value, s2.value, L.ptr(res), Cc, L.ptr(out), Cc,
-                                          None, 0, M, Cc, lay, d, L.stream_ptr()), "mlp_fused")
-            t = timeit(fused)
-            line += " L%d[dbg%d] %7.1f us %6.1f TF |" % (lay, d, t * 1e3, flop / t / 1e9)
-            if d == 0:
-                torch.cuda.synchronize()
-                err = (out - out2).abs().max().item()
-                line += " maxdiff %.2e |" % err
+        def fused():
+            L.check(lib.uni_mlp_fused(L.ptr(A), Cc, L.ptr(blobs[lay]), L.ptr(b1d), L.ptr(b2d), s1.value, s2.value, L.ptr(res), Cc, L.ptr(out), Cc,
+                                      None, 0, M, Cc, lay, L.stream_ptr()), "mlp_fused")
+        t = timeit(fused)
+        torch.cuda.synchronize()
+        line += " L%d %7.1f us %6.1f TF maxdiff %.2e |" % (lay, t * 1e3, flop / t / 1e9, (out - out2).abs().max().item())
     print(line, flush=True)

@@ -679,11 +679,11 @@ int uni_mlp_pack(const float* w1, const float* w2, const float* gamma, int C, in
     return 0;
 }
 int uni_mlp_fused(const void* A, int lda, const void* blob, const float* b1, const float* b2, float ws1, float ws2, const float* residual,
-                  int ldr, float* out, int ldo, void* outB, int ldb, int M, int C, int layout, int dbg, uni_stream_t stream) {
+                  int ldr, float* out, int ldo, void* outB, int ldb, int M, int C, int layout, uni_stream_t stream) {
     MlpArgs a;
     a.layout = layout;
     a.A = A; a.lda = lda; a.blob = blob; a.b1 = b1; a.b2 = b2; a.ws1 = ws1; a.ws2 = ws2; a.res = residual; a.ldr = ldr;
-    a.out = out; a.ldo = ldo; a.outB = outB; a.ldb = ldb; a.M = M; a.C = C; a.dbg = dbg;
+    a.out = out; a.ldo = ldo; a.outB = outB; a.ldb = ldb; a.M = M; a.C = C;
     API(launch_mlp_fused(a, S(stream)));
 }
 int uni_cast_h2(const float* x, int ldx, void* out, int ldo, int M, int C, uni_stream_t stream) {

@@ -160,6 +160,15 @@ static inline int act_elem_bytes(int fmt) { return fmt == FMT_BF16 ? 2 : 4; }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// CU count of the current device for the persistent launchers' grids: 256 where the device reports none, 0 where the query itself fails
+// (the caller decides: an error, or a default).  Callers cache it and round it their own way.
+static inline int uni_device_cus() {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+}
+
 // Guard for per-DEVICE one-time setup on the launch path (hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device property: a
 // `static bool` would leave the second GPU of a process without the opt-in, and an unguarded call is a driver call per launch).
 // run(setup) calls `setup` (-> hipError_t) until it has SUCCEEDED once per (guard, current device): the device's bit is set only after the

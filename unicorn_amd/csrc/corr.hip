@@ -9,7 +9,6 @@
 // The reference axis is additionally split across blocks (flash-decoding style) to fill 256 CUs; a tiny
 // second kernel merges the (max, sum, acc) partials.
 #include "kernels.h"
-#include <cstdlib>
 
 namespace {
 constexpr int CD = 128;      // embedding dim (unicorn.py:41-44)
@@ -540,10 +539,8 @@ __global__ void corr_merge_kernel(const float* __restrict__ ws, float* __restric
 int corr_slots(int precision) {     // co-resident blocks on the device: 2 x 4-wave blocks (fp32) / 1 x 8-wave block (split) per CU
     static int ncu = 0;
     if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                  ? prop.multiProcessorCount : 256;
+        const int n = uni_device_cus();
+        ncu = n ? n : 256;
     }
     return precision ? ncu : 2 * ncu;
 }
@@ -552,13 +549,8 @@ int corr_slots(int precision) {     // co-resident blocks on the device: 2 x 4-w
 // = 5 at 800x1280, 16 % quantisation loss.)
 int pick_nsplit(int R, int Q, int precision = 0, int B = 1) {
     const int nqb = cdiv(Q, precision ? QB2 : QB) * B;
-    static const char* env = getenv("UNI_CORR_BLOCKS");
     int maxs = R / 256;               // keep >= 8 tiles per split
     if (maxs < 1) maxs = 1;
-    if (env) {
-        int ns = cdiv(atoi(env), nqb);
-        return ns > maxs ? maxs : (ns < 1 ? 1 : ns);
-    }
     const int slots = corr_slots(precision);
     int best = 1;
     long best_cost = -1;

@@ -538,7 +538,7 @@ static GemmArgs conv_args(const PConv& p, ActPtr A, int lda, int Hin, int Win, i
 static int choose_splitk(const uni_ctx* c, const GemmArgs& g) {
     static const bool off = getenv("UNI_NO_SPLITK") != nullptr;
     if (off || c->b32 != FMT_H2 || g.N < 128 || g.N % 4 != 0 || g.K % 32 != 0) return 1;
-    const bool conv = g.KH != 1 || g.KW != 1 || g.stride != 1 || g.pad != 0;
+    const bool conv = gemm_is_conv(g);
     const long tiles = (long)cdiv(g.M, 128) * cdiv(g.N, 128);
     const int nk = g.K / 32;
     // tools/gemm_b1_bench.py on the single-frame shapes: 3x3 convolutions gain 25-50 % from ~400 blocks of >= 12 K steps (4000 x 384 x 3456:
@@ -828,10 +828,8 @@ int engine_head(uni_ctx* c, const float* fpn0, const float* fpn1, const float* f
     }
     // The three FPN levels are independent until the decode: run them concurrently (the stride-16/32 levels are
     // far too small to fill 256 CUs on their own).  Level k gets its own stream and a disjoint workspace slice.
-    static const bool no_fork = getenv("UNI_NO_FORK") != nullptr;     // A/B switch
-    const bool fork = c->aux[0] && c->aux[1] && c->aux[2] && !c->prof_on && !no_fork;   // serialised while event-profiling so per-kernel times are not inflated by overlap
-    static const bool no_fork_mb = getenv("UNI_NO_FORK_MB") != nullptr;                 // A/B switch: mask branch after the levels, on the caller's stream
-    const bool fork_mb = fork && cfg.mask && !no_fork_mb;
+    const bool fork = c->aux[0] && c->aux[1] && c->aux[2] && !c->prof_on;   // serialised while event-profiling so per-kernel times are not inflated by overlap
+    const bool fork_mb = fork && cfg.mask;
     const int njoin = fork_mb ? 3 : 2;
     hipStream_t s_main = s;
     // an error inside the forked region must not leave the auxiliary streams unjoined (the caller's stream would otherwise race the

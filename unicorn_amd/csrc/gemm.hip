@@ -23,7 +23,6 @@
 //    the 32 pixel lanes -> LDS -> one double atomic per group per block).
 //  * Blocks are remapped so each XCD (private 4 MiB L2) owns a contiguous range of M panels.
 #include "kernels.h"
-#include <cstdlib>
 
 __device__ u32x4 g_zero_page = {0u, 0u, 0u, 0u};
 
@@ -345,7 +344,7 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
     if (a.b32 == FMT_H2) return launch_gemm_h2(a, s);
     UNI_REQUIRE(a.K % (a.b32 == FMT_F32 ? 4 : 8) == 0 && a.Kpad % 64 == 0 && a.Kpad >= a.K, "gemm: K=%d Kpad=%d", a.K, a.Kpad);
     UNI_REQUIRE(a.lda % (a.b32 == FMT_F32 ? 4 : 8) == 0 && ((uintptr_t)a.A & 15) == 0, "gemm: lda=%d / A must be 16-byte aligned", a.lda);
-    const bool conv = a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0;
+    const bool conv = gemm_is_conv(a);
     if (a.b32 == FMT_F32) {
         if (conv) UNI_REQUIRE(a.Cin % 4 == 0 && a.K == a.KH * a.KW * a.Cin && a.Wout < 4096 && a.Mper / a.Wout < 4096, "gemm(f32): conv K mismatch / map too large");
         if (a.stats) UNI_REQUIRE(a.cpg > 0 && 128 / a.cpg + 2 <= 64, "gemm: cpg=%d unsupported", a.cpg);
@@ -369,7 +368,6 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
                 (!a.outF || (a.ldf % 4 == 0 && al16(a.outF))) && (!a.outB || (a.ldb % 8 == 0 && al16(a.outB))) &&
                 !((a.force_cfg / 1000) & 32);
     }
-    static const bool no44 = getenv("UNI_NO44") != nullptr, no_p44 = getenv("UNI_NO_P44") != nullptr;   // A/B switches (read once)
     const long b44 = (long)cdiv(a.M, 256) * cdiv(a.N, 256);
     const long b22 = (long)cdiv(a.M, 128) * cdiv(a.N, 128);
     const long b21 = (long)cdiv(a.M, 128) * cdiv(a.N, 64);
@@ -378,28 +376,27 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
     int cfg = a.force_cfg % 1000;
     if (cfg == 0) {
         if (a.N <= 64) cfg = (cdiv(a.M, 128) >= 256) ? 21 : 11;
-        else if (util44 >= 0.74 && (b44 >= 1500 || (b44 >= 384 && a.K >= 512)) && !no44) cfg = 44;
+        else if (util44 >= 0.74 && (b44 >= 1500 || (b44 >= 384 && a.K >= 512))) cfg = 44;
         else if (b22 >= 512) cfg = 22;
         else if (conv) cfg = b22 >= 400 ? 22 : (b12 >= 400 ? 12 : 11);
         else cfg = b21 >= 400 ? 21 : 11;
     }
 #define GO(WM, WN, TM, TN, BK) return conv ? launch_cfg<WM, WN, TM, TN, BK, true>(a, s) : launch_cfg<WM, WN, TM, TN, BK, false>(a, s)
     // 256-wide problems with whole rounds of tiles go to the persistent ping-pong kernel (gemm_h2q.hip, the bf16 instantiations;
-    // 188 forces it, UNI_NO_H2Q = A/B switch back to the kernels below)
+    // 188 forces it)
     {
-        static const bool no_q = getenv("UNI_NO_H2Q") != nullptr;
         const bool rounds = b44 >= 384 || (b44 >= 180 && (double)b44 / (cdiv((int)b44, 256) * 256.0) >= 0.7);
         // measured per shape against the kernels below (profiles/r02e_bf16_gemm_shapes.txt): with ONE MFMA per product the 8-MFMA phases are
         // shorter than the LDS / DMA phases, so the schedule only wins where the K loop is long and the A operand streams plainly:
         // plain GEMMs with K >= 1024 (-5..-15 %); implicit GEMMs (+3..10 %) and K <= 768 layers (0..+8 %) stay where they were
         const bool pays = !conv && !a.stats && a.K >= 1024;
-        if (cfg == 188 || (a.force_cfg % 1000 == 0 && !no_q && pays && a.N > 64 && util44 >= 0.74 && rounds && a.epi && gemm_h2q_supported(a))) {
+        if (cfg == 188 || (a.force_cfg % 1000 == 0 && pays && a.N > 64 && util44 >= 0.74 && rounds && a.epi && gemm_h2q_supported(a))) {
             if (!gemm_h2q_supported(a)) { uni_set_error("gemm: ping-pong variant does not support this problem"); return -1; }
             return launch_gemm_h2q(a, s);
         }
     }
     // plain GEMMs that would take the 256x256 tile go to the persistent variant (gemm_p44.hip): -5..-20 % on the MLP shapes
-    if (cfg == 44 && a.force_cfg % 1000 == 0 && gemm_p44_supported(a) && !no_p44) cfg = 144;
+    if (cfg == 44 && a.force_cfg % 1000 == 0 && gemm_p44_supported(a)) cfg = 144;
     if (cfg == 144 && !gemm_p44_supported(a)) cfg = 44;
     if (cfg == 144) return launch_gemm_p44(a, s);
     if (!a.epi && (cfg == 44 || cfg == 42 || cfg == 24)) cfg = 22;

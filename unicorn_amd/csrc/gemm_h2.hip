@@ -309,10 +309,13 @@ static bool h2_epi_ok(const GemmArgs& a) {
 // small problems (<= 1600 tiles of 64 x 64: the single-frame shapes, the stride-32 level of a batch) run on the deep-pipeline tiles of
 // gemm_h2d.hip: 64 x 64 with 3 slices in flight and 3 blocks per CU up to 800 tiles, 64 x 128 (2 blocks per CU) above
 // (tools/gemm_b1_bench.py, profiles/r03b_b1_gemm_tile_sweep.txt).  Returns 0 (not a deep problem) or the tile configuration.
-// UNI_NO_H2D = A/B switch.
-int gemm_h2d_choice(const GemmArgs& a_in) {
+// UNI_NO_H2D = A/B switch (also of the 256 x 192 tiles in launch_gemm_h2).
+static bool h2d_off() {
     static const bool off = getenv("UNI_NO_H2D") != nullptr;
-    if (off || a_in.b32 != FMT_H2) return 0;
+    return off;
+}
+int gemm_h2d_choice(const GemmArgs& a_in) {
+    if (h2d_off() || a_in.b32 != FMT_H2) return 0;
     GemmArgs a = a_in;
     a.epi = h2_epi_ok(a);
     if (!gemm_h2d_supported(a, 331)) return 0;
@@ -320,7 +323,7 @@ int gemm_h2d_choice(const GemmArgs& a_in) {
     // long-K plain GEMMs with hundreds of 64 x 64 tiles are bound by the L2 -> LDS path on those (4000 x 768 x 3072 = 756 tiles x 96 slices
     // x 16 KiB = 1.16 GB per launch, ~14.5 TB/s): 128 x 96 / 128 x 128 tiles move 0.6x / 0.5x the bytes, one per CU is enough when they
     // fill one round (in the model, per frame: 74 us on 256 tiles of 128 x 96 vs 85 us before, 89 us on 64 x 64)
-    const bool conv = a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0;
+    const bool conv = gemm_is_conv(a);
     if (!conv && a.K >= 2048 && t64 > 400 && t64 <= 800) {
         const long t96 = (long)cdiv(a.M, 128) * cdiv(a.N, 96), t128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128);
         if (a.N % 96 == 0 && t96 > 192 && t96 <= 256) return 323;
@@ -334,7 +337,7 @@ int gemm_h2d_choice(const GemmArgs& a_in) {
 // called by launch_gemm (gemm.hip) for FMT_H2 problems after the common argument checks
 int launch_gemm_h2(const GemmArgs& a_in, hipStream_t s) {
     GemmArgs a = a_in;
-    const bool conv = a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0;
+    const bool conv = gemm_is_conv(a);
     UNI_REQUIRE(a.K % 8 == 0 && a.Kpad % 32 == 0 && a.lda % 8 == 0, "gemm(h2): K=%d Kpad=%d lda=%d", a.K, a.Kpad, a.lda);
     if (conv) UNI_REQUIRE(a.Cin % 8 == 0 && a.K == a.KH * a.KW * a.Cin && a.Wout < 4096 && a.Mper / a.Wout < 4096, "gemm(h2): conv K mismatch / map too large");
     if (a.stats) UNI_REQUIRE(a.cpg > 0 && 128 / a.cpg + 2 <= 64 && a.act == ACT_NONE, "gemm(h2): cpg=%d / activation with GroupNorm statistics", a.cpg);
@@ -361,8 +364,7 @@ int launch_gemm_h2(const GemmArgs& a_in, hipStream_t s) {
             GemmArgs g = gemm_splitk_partial_args(a);
             g.splitk = 0;
             const int nks = a.K / 32;
-            static const bool no_q = getenv("UNI_NO_H2Q") != nullptr;
-            if (!no_q && a.N > 64 && a.K % 32 == 0 && nks % a.splitk == 0 && nks / a.splitk >= 2 && gemm_h2q_supported(g)) return launch_gemm_h2q(a, s);
+            if (a.N > 64 && a.K % 32 == 0 && nks % a.splitk == 0 && nks / a.splitk >= 2 && gemm_h2q_supported(g)) return launch_gemm_h2q(a, s);
             UNI_REQUIRE(cfg != 188, "gemm(h2): ping-pong split-K does not support this problem");
         }
         if (gemm_h2d_has_cfg(cfg)) return launch_gemm_h2d(a, cfg, conv, s);
@@ -382,22 +384,18 @@ int launch_gemm_h2(const GemmArgs& a_in, hipStream_t s) {
     if (!a.epi && cfg == 44) cfg = 22;
     // 256-wide problems whose N is a multiple of 192 but pads the 256 x 256 tiles (N = 192, 384: a quarter of the MFMA work on zeros) or
     // leaves the last round of them mostly empty: 256 x 192 tiles of the deep kernel (8 waves, 2 slots; ~0.82 of the ping-pong kernel's
-    // rate per useful flop).  Rounds-aware cost: rounds x tile area / efficiency.  UNI_NO_H2D_192 = A/B switch.
+    // rate per useful flop).  Rounds-aware cost: rounds x tile area / efficiency.
     if (a.force_cfg % 1000 == 0 && cfg == 44 && a.N % 192 == 0 && gemm_h2d_supported(a, 346)) {
-        static const bool off = getenv("UNI_NO_H2D_192") != nullptr || getenv("UNI_NO_H2D") != nullptr;
         const long t192 = (long)cdiv(a.M, 256) * (a.N / 192);
         const double cost_q = (double)cdiv((int)b44, 256) * 65536.0, cost_192 = (double)cdiv((int)t192, 256) * 49152.0 / 0.82;
-        if (!off && cost_192 < 0.97 * cost_q) return launch_gemm_h2d(a, 346, conv, s);
+        if (!h2d_off() && cost_192 < 0.97 * cost_q) return launch_gemm_h2d(a, 346, conv, s);
     }
     if (a.force_cfg % 1000 == 0 && cfg != 44) {
         const int d = gemm_h2d_choice(a);
         if (d) return launch_gemm_h2d(a, d, conv, s);
     }
-    // problems that take the 256 x 256 tile go to the persistent ping-pong kernel (gemm_h2q.hip, cfg 188) where it covers them; UNI_NO_H2Q = A/B switch
-    if (cfg == 44 && a.force_cfg % 1000 == 0) {
-        static const bool no_q = getenv("UNI_NO_H2Q") != nullptr;
-        if (!no_q && gemm_h2q_supported(a)) cfg = 188;
-    }
+    // problems that take the 256 x 256 tile go to the persistent ping-pong kernel (gemm_h2q.hip, cfg 188) where it covers them
+    if (cfg == 44 && a.force_cfg % 1000 == 0 && gemm_h2q_supported(a)) cfg = 188;
     if (cfg == 188) return gemm_h2q_supported(a) ? launch_gemm_h2q(a, s) : (uni_set_error("gemm(h2): ping-pong variant does not support this problem"), -1);
 #define GOH(WM, WN, TM, TN) return conv ? launch_h2_cfg<WM, WN, TM, TN, true>(a, s) : launch_h2_cfg<WM, WN, TM, TN, false>(a, s)
     switch (cfg) {

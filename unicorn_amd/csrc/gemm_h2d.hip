@@ -13,7 +13,6 @@
 // Same operand format, loader geometry, swizzle, epilogue (gemm_epi.h) and split-K protocol (slab + splitk_reduce_kernel) as
 // gemm_h2.hip; results are bit-identical to gemm_h2_kernel's for the same K order (same MFMA sequence per accumulator).
 #include "kernels.h"
-#include <cstdlib>
 
 #define D_LDS(addr) (*reinterpret_cast<const __attribute__((address_space(3))) f16x8*>((size_t)(addr)))
 
@@ -317,7 +316,7 @@ bool gemm_h2d_has_cfg(int cfg) { return cfg == 322 || cfg == 323 || cfg == 331 |
 
 // what the descriptor addressing covers (everything else stays on gemm_h2_kernel)
 bool gemm_h2d_supported(const GemmArgs& a, int cfg) {
-    const bool conv = a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0;
+    const bool conv = gemm_is_conv(a);
     if (!gemm_h2d_has_cfg(cfg) || a.b32 != FMT_H2 || !a.epi || a.K % 32 != 0 || a.K < 64) return false;
     const long rows = cfg == 346 ? 256 : 128;    // tallest tile of the configuration (A rows / weight rows addressed from one descriptor base)
     if (rows * a.lda * 4 >= (1L << 30) || rows * a.Kpad * 4 >= (1L << 30)) return false;
@@ -340,10 +339,9 @@ int launch_gemm_h2d(const GemmArgs& a, int cfg, bool conv, hipStream_t s) {
     // 422 / 423 = 322 / 323 with producer waves (SPEC); launches they do not cover (GroupNorm statistics, K ranges) take the 4-wave build.
     // NOT the launcher's choice: in the model the producer build is SLOWER (stage-2 pwconv2 of one frame 76.9 -> 88.7 us, 9.74 -> 9.90 ms per
     // frame, same box) although the skeleton probe gains 12 % -- with real (random) operands, the epilogue and 8 waves at every barrier the
-    // extra waves cost more than the issue stalls they remove.  Kept as a tested configuration (bit-identical) and behind UNI_H2D_SPEC=1.
-    static const bool want_spec = getenv("UNI_H2D_SPEC") != nullptr;
+    // extra waves cost more than the issue stalls they remove.  Kept as a tested configuration (bit-identical), reached through force_cfg only.
     const bool plain = !a.stats && a.splitk <= 1;
-    const bool spec = plain && (cfg == 422 || cfg == 423 || (want_spec && a.force_cfg % 1000 == 0 && (cfg == 322 || cfg == 323)));
+    const bool spec = plain && (cfg == 422 || cfg == 423);
     if (cfg == 422) cfg = 322;
     if (cfg == 423) cfg = 323;
 #define GOS(WM, WN, TM, TN, NST) return conv ? launch_h2d_spec<WM, WN, TM, TN, true, NST>(a, s) : launch_h2d_spec<WM, WN, TM, TN, false, NST>(a, s)

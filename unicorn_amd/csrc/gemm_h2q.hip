@@ -445,7 +445,7 @@ static int launch_h2q_inst(const GemmArgs& a, int grid, hipStream_t s) {
 // plain GEMMs: what the older persistent kernels take minus the LayerNorm fold; implicit GEMMs (3x3 / strided convs) and
 // GroupNorm-statistics problems: step-aligned taps (Cin a multiple of the 32 / 64 k of a step), fp32 output, no activation window
 bool gemm_h2q_supported(const GemmArgs& a) {
-    const bool conv = a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0;
+    const bool conv = gemm_is_conv(a);
     if (a.b32 != FMT_H2 && a.b32 != FMT_BF16) return false;
     const int ks = a.b32 == FMT_H2 ? 32 : 64, eb = a.b32 == FMT_H2 ? 4 : 2;
     if (!a.epi || a.K % ks != 0 || a.K < 2 * ks || a.act_col0 != 0) return false;
@@ -467,7 +467,7 @@ bool gemm_h2q_supported(const GemmArgs& a) {
 template <int FMT>
 static int launch_h2q_fmt(const GemmArgs& a, int grid, hipStream_t s) {
     const bool f = a.outF != nullptr;
-    const bool conv = a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0;
+    const bool conv = gemm_is_conv(a);
     if (a.stats) return conv ? launch_h2q_inst<ACT_NONE, true, true, true, FMT>(a, grid, s) : launch_h2q_inst<ACT_NONE, true, false, true, FMT>(a, grid, s);
     if (conv) {
         if (a.act == ACT_RELU) return f ? launch_h2q_inst<ACT_RELU, true, true, false, FMT>(a, grid, s) : launch_h2q_inst<ACT_RELU, false, true, false, FMT>(a, grid, s);
@@ -483,11 +483,9 @@ static int launch_h2q_fmt(const GemmArgs& a, int grid, hipStream_t s) {
 int launch_gemm_h2q(const GemmArgs& a, hipStream_t s) {
     static int ncu = 0;
     if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-        ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        ncu -= ncu % 8;
+        const int n = uni_device_cus();
+        if (!n) return -1;
+        ncu = n - n % 8;
     }
     const int sk = a.splitk > 1 ? a.splitk : 1;
     const int ntiles = cdiv(a.M, BM) * cdiv(a.N, BN) * sk;

@@ -253,7 +253,7 @@ static int launch_p44_inst(const GemmArgs& a, int grid, hipStream_t s) {
 }
 
 bool gemm_p44_supported(const GemmArgs& a) {      // plain GEMM, K % 64 == 0, bias, none/relu/gelu on every column, aligned operands
-    const bool conv = a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0;
+    const bool conv = gemm_is_conv(a);
     return !conv && !a.stats && a.b32 == FMT_BF16 && a.epi && a.K == a.Kpad && a.bias && a.act_col0 == 0 && a.out_hw == 0 &&
            (a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_GELU) && (a.outF || a.outB) && (a.outF || !a.res);
 }
@@ -261,11 +261,9 @@ bool gemm_p44_supported(const GemmArgs& a) {      // plain GEMM, K % 64 == 0, bi
 int launch_gemm_p44(const GemmArgs& a, hipStream_t s) {
     static int ncu = 0;
     if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-        ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        ncu -= ncu % 8;
+        const int n = uni_device_cus();
+        if (!n) return -1;
+        ncu = n - n % 8;
     }
     const int ntiles = cdiv(a.M, BM) * cdiv(a.N, BN);
     const int grid = ntiles < ncu ? (ntiles + 7) / 8 * 8 : ncu;

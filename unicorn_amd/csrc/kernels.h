@@ -28,6 +28,8 @@ struct GemmArgs {
     int dbg = 0;                              // ablation switches for tools/gemm_bench.py (1 = no DMA after tile 0, 2 = no MFMA)
     int epi = 0;                              // set by launch_gemm: 1 = LDS-staged, row-coalesced epilogue stores
 };
+// implicit GEMM (gathered A operand) as opposed to a plain one (1x1 / stride 1 / no padding)
+static inline bool gemm_is_conv(const GemmArgs& a) { return a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0; }
 // variant trace tag of one GEMM launch (common.h: uni_variant_note).  family = the kernel, cfg = its tile configuration; then every
 // launch-uniform switch that changes index arithmetic or the store path: implicit conv, GroupNorm statistics, K ranges, staged epilogue,
 // which outputs exist, residual, activation (+ column window), outF row remap, stacked samples.
@@ -69,7 +71,6 @@ struct MlpArgs {
     void* outB = nullptr; int ldb = 0;        // optional f16x2 copy of the result
     int M = 0, C = 0;
     int layout = 0;                           // 0: 32-row waves (4 per block, blob of mlp_pack_host); 1: 16-row waves (8 per block, mlp_pack16_host)
-    int dbg = 0;                              // ablation switches (tools/mlp_bench.py, C = 192): 1 no DMA, 2 no MFMA, 16 no GELU arithmetic, 8 (any C) every block starts its weight stream at hidden block 0
 };
 int launch_mlp_fused(const MlpArgs& a, hipStream_t s);
 bool mlp_fused_supported(int C);

@@ -72,7 +72,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 // CH = accumulator chains of GEMM1 (2: even / odd k slices; 1 where the registers do not allow the second one)
-template <int C, int CH, bool OUTB, int DBG>
+template <int C, int CH, bool OUTB>
 __global__ __launch_bounds__(64 * MW, 1) void mlp_fused_kernel(MlpArgs p) {
     using G = Geo<C>;
     constexpr int NS = G::NS, NH = G::NH, NJ = G::NJ, PB = G::PB, IPW = G::IPW, NSLOT = G::NSLOT, NP = G::NP;
@@ -97,13 +97,13 @@ __global__ __launch_bounds__(64 * MW, 1) void mlp_fused_kernel(MlpArgs p) {
     // W1_{h0} | W1_{h0+1} W2_{h0} | ... | W1_{h0-1} W2_{h0-2} | W2_{h0-1}  (indices mod NH) = blob positions 2 h0, then 2 h0 + 2, 2 h0 + 3, ...
     // cyclically, and 2 h0 + 1 last.  The blocks of one XCD (blockIdx & 7 fixed) spread their h0 over the stream: all CUs reading
     // the same 24 KB at the same time would sit on the few L2 channels that hold it (4-KiB channel interleave).
-    const int h0 = (p.dbg & 8) ? 0 : (int)(((blockIdx.x >> 3) * 13u + (blockIdx.x & 7) * 5u) % NH);
+    const int h0 = (int)(((blockIdx.x >> 3) * 13u + (blockIdx.x & 7) * 5u) % NH);
     const int q_first = 2 * h0, q_last = 2 * h0 + 1;
     auto hb_of = [&](int step) __attribute__((always_inline)) { const int v = h0 + step; return v >= NH ? v - NH : v; };
     int p_issue = 0, src_q = q_first, wr_slot = 0;   // next piece to request: its index, its position in the blob, its slot
     auto issue_piece_part = [&](auto II) __attribute__((always_inline)) {      // request II of the IPW of the next piece
         constexpr int i = decltype(II)::value;
-        const int so = (p_issue < total && !(DBG & 1)) ? src_q * PB : 0x40000000;
+        const int so = p_issue < total ? src_q * PB : 0x40000000;
         char* dst = smem + wr_slot * PB + wave * 1024;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(dst + i * 4096), 16, vo_w, so + i * 4096, 0, 0);
     };
@@ -192,9 +192,7 @@ __global__ __launch_bounds__(64 * MW, 1) void mlp_fused_kernel(MlpArgs p) {
             G4(t[e] = b4[e]);
             G4(x[e] = a[0][4 * q + e]);
             if (CH == 2) { G4(x[e] += a[CH - 1][4 * q + e]); }
-            if (DBG & 16) { G4(w[e] = x[e]); }
             GPIN(x); GPIN(t);
-        } else if constexpr ((DBG & 16) != 0 && k < 18) {      // ablation: no GELU / split arithmetic
         } else if constexpr (k == 1) { G4(x[e] = fmaf(x[e], ws1, t[e])); GPIN(x); }
         else if constexpr (k == 2) { G4(e_[e] = fabsf(x[e]) * 0.84932180028801904f); GPIN(e_); }
         else if constexpr (k == 3) { G4(e_[e] = -e_[e] * e_[e]); GPIN(e_); }
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(64 * MW, 1) void mlp_fused_kernel(MlpArgs p) {
                 constexpr int k = decltype(Kk)::value;
                 constexpr int w = k & 1, term = k >> 1;
                 // terms: lo.hi, hi.lo, hi.hi
-                if (!(DBG & 2)) mfma(2 * pp + w, term == 0 ? wf[pp & 1][w][1] : wf[pp & 1][w][0], term);
+                mfma(2 * pp + w, term == 0 ? wf[pp & 1][w][1] : wf[pp & 1][w][0], term);
                 if constexpr (k == 1 && pp + 1 < NPAIR) load(std::integral_constant<int, pp + 1>{});
                 filler(std::integral_constant<int, pp * 6 + k>{});
                 __builtin_amdgcn_sched_barrier(0);
@@ -362,10 +360,8 @@ __global__ __launch_bounds__(64 * MW, 1) void mlp_fused_kernel(MlpArgs p) {
                     f32x4 v;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaf(acc2[j][4 * g + e], ws2, b4[e]) + rv[j][g][e];
-                    if (!(DBG & 4)) {
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_o, vo_o + (32 * j + 8 * g) * 4, 0, 0);
-                        if (OUTB && row < p.M) act_store4(p.outB, (size_t)row * p.ldb + 32 * j + 8 * g + 4 * fh, v[0], v[1], v[2], v[3], FMT_H2);
-                    }
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_o, vo_o + (32 * j + 8 * g) * 4, 0, 0);
+                    if (OUTB && row < p.M) act_store4(p.outB, (size_t)row * p.ldb + 32 * j + 8 * g + 4 * fh, v[0], v[1], v[2], v[3], FMT_H2);
                 }
             }
         }
@@ -405,7 +401,7 @@ struct Geo16 {
 #define F_MFMA16(w, a, c) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, a, c, 0, 0, 0)
 }  // namespace
 
-template <int C, bool OUTB, int DBG>
+template <int C, bool OUTB>
 __global__ __launch_bounds__(64 * MW16, 2) void mlp_fused16_kernel(MlpArgs p) {
     using G = Geo16<C>;
     constexpr int NS = G::NS, NH = G::NH, NJ = G::NJ, PB = G::PB, IPW = G::IPW, NSLOT = G::NSLOT, NP = G::NP;
@@ -423,13 +419,13 @@ __global__ __launch_bounds__(64 * MW16, 2) void mlp_fused16_kernel(MlpArgs p) {
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.blob), 0, NP * PB, 0x00020000);
     const int vo_w = lane * 16 + wave * 1024;
     const int lds0 = (int)(size_t)(__attribute__((address_space(3))) char*)smem;
-    const int h0 = (p.dbg & 8) ? 0 : (int)(((blockIdx.x >> 3) * 13u + (blockIdx.x & 7) * 5u) % NH);
+    const int h0 = (int)(((blockIdx.x >> 3) * 13u + (blockIdx.x & 7) * 5u) % NH);
     const int q_first = 2 * h0, q_last = 2 * h0 + 1;
     auto hb_of = [&](int step) __attribute__((always_inline)) { const int v = h0 + step; return v >= NH ? v - NH : v; };
     int p_issue = 0, src_q = q_first, wr_slot = 0;
     auto issue_piece_part = [&](auto II) __attribute__((always_inline)) {
         constexpr int i = decltype(II)::value;
-        const int so = (p_issue < total && !(DBG & 1)) ? src_q * PB : 0x40000000;
+        const int so = p_issue < total ? src_q * PB : 0x40000000;
         char* dst = smem + wr_slot * PB + wave * 1024;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(dst + i * 8192), 16, vo_w, so + i * 8192, 0, 0);
     };
@@ -499,9 +495,7 @@ __global__ __launch_bounds__(64 * MW16, 2) void mlp_fused16_kernel(MlpArgs p) {
             const f32x4 b4 = F_LDSF(bias_rd + (32 * hb + 16 * ub) * 4);
             G4(t[e] = b4[e]);
             G4(x[e] = a[ub][e]);
-            if (DBG & 16) { G4(w[e] = x[e]); }
             GPIN(x); GPIN(t);
-        } else if constexpr ((DBG & 16) != 0 && k < 18) {
         } else if constexpr (k == 1) { G4(x[e] = fmaf(x[e], ws1, t[e])); GPIN(x); }
         else if constexpr (k == 2) { G4(e_[e] = fabsf(x[e]) * 0.84932180028801904f); GPIN(e_); }
         else if constexpr (k == 3) { G4(e_[e] = -e_[e] * e_[e]); GPIN(e_); }
@@ -551,7 +545,7 @@ __global__ __launch_bounds__(64 * MW16, 2) void mlp_fused16_kernel(MlpArgs p) {
             static_for<0, 6>([&](auto Kk) __attribute__((always_inline)) {
                 constexpr int k = decltype(Kk)::value;
                 constexpr int w = k & 1, term = k >> 1;
-                if (!(DBG & 2)) mfma(2 * pp + w, term == 0 ? wf[pp & 1][w][1] : wf[pp & 1][w][0], term);
+                mfma(2 * pp + w, term == 0 ? wf[pp & 1][w][1] : wf[pp & 1][w][0], term);
                 if constexpr (k == 1 && pp + 1 < NPAIR) load(std::integral_constant<int, pp + 1>{});
                 filler(std::integral_constant<int, pp * 6 + k>{});
                 __builtin_amdgcn_sched_barrier(0);
@@ -756,39 +750,28 @@ void mlp_pack16_host(const float* w1, const float* w2, const float* gamma, int C
 }
 bool mlp_fused16_supported(int C) { return C == 192 || C == 256; }
 
-template <int C, bool OUTB, int DBG>
+template <int C, bool OUTB>
 static int launch_mlp16_k(const MlpArgs& a, int grid, hipStream_t s) {
     constexpr int lds = Geo16<C>::LDS;
     static DevOnce attr_once;
-    UNI_LDS_OPTIN(attr_once, "mlp_fused16", lds, reinterpret_cast<const void*>(&mlp_fused16_kernel<C, OUTB, DBG>));
-    uni_variant_note("mlp_fused layout=1 C=%d outB=%d dbg=%d", C, (int)OUTB, DBG);
-    hipLaunchKernelGGL((mlp_fused16_kernel<C, OUTB, DBG>), dim3(grid), dim3(64 * MW16), lds, s, a);
+    UNI_LDS_OPTIN(attr_once, "mlp_fused16", lds, reinterpret_cast<const void*>(&mlp_fused16_kernel<C, OUTB>));
+    uni_variant_note("mlp_fused layout=1 C=%d outB=%d", C, (int)OUTB);
+    hipLaunchKernelGGL((mlp_fused16_kernel<C, OUTB>), dim3(grid), dim3(64 * MW16), lds, s, a);
     return 0;
 }
 
-template <int C, int CH, bool OUTB, int DBG>
+template <int C, int CH, bool OUTB>
 static int launch_mlp_k(const MlpArgs& a, int grid, hipStream_t s) {
     constexpr int lds = Geo<C>::LDS;
     static DevOnce attr_once;
-    UNI_LDS_OPTIN(attr_once, "mlp_fused", lds, reinterpret_cast<const void*>(&mlp_fused_kernel<C, CH, OUTB, DBG>));
-    uni_variant_note("mlp_fused layout=0 C=%d outB=%d dbg=%d", C, (int)OUTB, DBG);
-    hipLaunchKernelGGL((mlp_fused_kernel<C, CH, OUTB, DBG>), dim3(grid), dim3(64 * MW), lds, s, a);
+    UNI_LDS_OPTIN(attr_once, "mlp_fused", lds, reinterpret_cast<const void*>(&mlp_fused_kernel<C, CH, OUTB>));
+    uni_variant_note("mlp_fused layout=0 C=%d outB=%d", C, (int)OUTB);
+    hipLaunchKernelGGL((mlp_fused_kernel<C, CH, OUTB>), dim3(grid), dim3(64 * MW), lds, s, a);
     return 0;
 }
 template <int C, int CH>
 static int launch_mlp_inst(const MlpArgs& a, int grid, hipStream_t s) {
-    if (a.dbg && C == 192 && !a.outB) {     // ablations for tools/mlp_bench.py, C = 192 only
-        switch (a.dbg) {
-            case 1: return launch_mlp_k<192, 2, false, 1>(a, grid, s);
-            case 2: return launch_mlp_k<192, 2, false, 2>(a, grid, s);
-            case 3: return launch_mlp_k<192, 2, false, 3>(a, grid, s);
-            case 4: return launch_mlp_k<192, 2, false, 4>(a, grid, s);
-            case 16: return launch_mlp_k<192, 2, false, 16>(a, grid, s);
-            case 17: return launch_mlp_k<192, 2, false, 17>(a, grid, s);
-            default: break;
-        }
-    }
-    return a.outB ? launch_mlp_k<C, CH, true, 0>(a, grid, s) : launch_mlp_k<C, CH, false, 0>(a, grid, s);
+    return a.outB ? launch_mlp_k<C, CH, true>(a, grid, s) : launch_mlp_k<C, CH, false>(a, grid, s);
 }
 
 int launch_mlp_fused(const MlpArgs& a, hipStream_t s) {
@@ -800,24 +783,15 @@ int launch_mlp_fused(const MlpArgs& a, hipStream_t s) {
     UNI_REQUIRE((long)BMF * a.lda * 4 < (1L << 31) && (long)BMF * a.ldo * 4 < (1L << 31), "mlp_fused: row stride too large");
     static int ncu = 0;
     if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-        ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        ncu = uni_device_cus();
+        if (!ncu) return -1;
     }
     const int ntiles = cdiv(a.M, BMF);
     const int grid = ntiles < ncu ? ntiles : ncu;
     if (a.layout == 1) {      // 16-row waves, two per SIMD (blob of mlp_pack16_host)
         UNI_REQUIRE(mlp_fused16_supported(a.C), "mlp_fused: the 16-row variant supports C = 192 / 256 (got %d)", a.C);
-        const int d = a.dbg & ~8;
-        if (a.C == 192) {
-            if (a.outB) return launch_mlp16_k<192, true, 0>(a, grid, s);
-            if (d == 1) return launch_mlp16_k<192, false, 1>(a, grid, s);
-            if (d == 16) return launch_mlp16_k<192, false, 16>(a, grid, s);
-            if (d == 17) return launch_mlp16_k<192, false, 17>(a, grid, s);
-            return launch_mlp16_k<192, false, 0>(a, grid, s);
-        }
-        return a.outB ? launch_mlp16_k<256, true, 0>(a, grid, s) : launch_mlp16_k<256, false, 0>(a, grid, s);
+        if (a.C == 192) return a.outB ? launch_mlp16_k<192, true>(a, grid, s) : launch_mlp16_k<192, false>(a, grid, s);
+        return a.outB ? launch_mlp16_k<256, true>(a, grid, s) : launch_mlp16_k<256, false>(a, grid, s);
     }
     switch (a.C) {
         case 96: return launch_mlp_inst<96, 2>(a, grid, s);
