@@ -1233,3 +1233,45 @@ def test_rle_device_strings_decode_through_the_independent_reader(L):
         strs = rle_encode(torch.from_numpy(np.stack([m for _, m in group])).cuda())
         for (n, m), s in zip(group, strs):
             assert np.array_equal(sr.coco_rle_string_to_mask(s, *shape), m), (n, shape, s)
+
+
+def test_gemm_descriptor_kernels_stop_at_the_tap_decode_bound(L):
+    """The descriptor-addressed implicit GEMMs (gemm_h2d / gemm_h2q) decode a K step into (tap, channel step) by multiplication, exact up to
+    TAP_DECODE_MAX_CS = 102 K steps per tap (csrc/tile_index.h; tools/tile_index_check.cpp proves the bound).  One sample, a 5 x 6 map, 3x3 /
+    stride 1 / pad 1, N = 32 (M = 30) through uni_gemm_stacked, reference and tolerance of the stacked cases (tests/variant_cases.py: batched
+    fp64 F.conv2d, output pre-filled, complement held to the fill): Cin = 102 * 32 forced to the 64 x 64 deep tile runs there; Cin = 103 * 32
+    is computed by a kernel that decodes with true divisions, and forcing a descriptor kernel onto it is refused before any launch."""
+    import variant_cases as vc
+    from test_variant_census_gpu import _cast_h2, _pack_h2, traced
+    lib, N, FILL = L.lib(), 32, -777.0
+
+    def call(cs, cfg):
+        Cin = cs * 32
+        a = vc._gemms("h2", "h2d", 22113, cfg, 1, 0, 0, 1, 0, 0, 0, (0, 0, Cin, N, 3, 1, 1), (5, 6, 1))["args"]
+        P = vc.gemm_stacked_problem(a)
+        rows = P["x"].permute(0, 2, 3, 1).reshape(30, Cin).contiguous().cuda()
+        A = _cast_h2(L, rows)
+        Wp, wscale = _pack_h2(L, P["w"])
+        outF = torch.full((a["outF_rows"], a["ldf"]), FILL, device="cuda")
+        bias = P["bias"].cuda()
+        rc, tags = traced(L, lambda: lib.uni_gemm_stacked(L.ptr(A), Cin, L.ptr(Wp), wscale, 2, 1, P["M"], N, 5, 6, Cin, 3, 3, 1, 1, L.ptr(bias), 0, 0, None, N + 4,
+                                                          L.ptr(outF), a["ldf"], 0, 0, 0, a["outF_rows"], None, N + 8, None, 0, 0, cfg, L.stream_ptr()))
+        return rc, tags, outF.cpu().double(), P
+
+    def held(got, P, what):
+        assert P["M"] == 30
+        assert bool((got[30:] == FILL).all()) and bool((got[:, N:] == FILL).all()), what + ": written outside the 30 rows x 32 columns"
+        err = (got[:30, :N] - P["exp"]).abs()
+        print("%s: max err / tolerance %.3f" % (what, (err / P["tol"]).max().item()))
+        assert bool((err <= P["tol"]).all()), what
+
+    rc, tags, got, P = call(102, 331)              # the proven end of the decode's range
+    assert rc == 0 and len(tags) == 1 and next(iter(tags)).startswith("gemm:h2d cfg=22113 "), (rc, tags)
+    held(got, P, "Cin = 102 * 32, deep tile 331")
+    rc, tags, got, P = call(103, 0)                # the launcher's own choice: neither descriptor kernel
+    assert rc == 0 and len(tags) == 1 and not next(iter(tags)).startswith(("gemm:h2d", "gemm:h2q")), (rc, tags)
+    held(got, P, "Cin = 103 * 32, heuristic")
+    for cfg in (331, 188):                         # forced onto the deep tile / the ping-pong kernel: an error code, no launch, nothing written
+        rc, tags, got, P = call(103, cfg)
+        assert rc != 0 and lib.uni_last_error(), cfg
+        assert tags == {} and bool((got == FILL).all()), (cfg, tags)

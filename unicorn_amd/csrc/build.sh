@@ -39,6 +39,12 @@ man = {"sources": {os.path.basename(p): sha(p) for p in srcs},
 json.dump(man, open(os.path.join(out, "build_manifest.json"), "w"), indent=1, sort_keys=True)
 print("wrote %s/build_manifest.json (%d sources)" % (out, len(srcs)))
 EOF
+# host check of the index arithmetic in tile_index.h (tools/tile_index_check.cpp; tests/test_tile_order_cpu.py runs it): plain C++, so a failure is fatal
+mkdir -p ../../tools/build
+if [ ! -f ../../tools/build/tile_index_check ] || [ ../../tools/tile_index_check.cpp -nt ../../tools/build/tile_index_check ] || [ tile_index.h -nt ../../tools/build/tile_index_check ]; then
+  g++ -O2 -std=c++17 -Wall -Wextra ../../tools/tile_index_check.cpp -o ../../tools/build/tile_index_check
+  echo "built tools/build/tile_index_check"
+fi
 # standalone measurement program (tools/feed_probe.hip: which path feeds a CU; profiles/r05_feed_probe.txt) -- not part of the library:
 # built last and non-fatally (a probe that does not compile on another ROCm must not leave the libraries unbuilt)
 mkdir -p ../../tools/build

@@ -84,6 +84,12 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// orders the LDS writes of a wave before its own later LDS reads (other lanes' data): wave-local, no workgroup barrier (LDS is in-order per wave)
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // "act" buffers hold GEMM operands.  Three formats (wave-uniform `fmt`, historically named b32 in the arg structs):
 //   FMT_BF16  bf16 elements (2 B)                                   - 1 MFMA per product

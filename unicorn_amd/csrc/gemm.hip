@@ -22,22 +22,12 @@
 //  * GroupNorm statistics of the raw conv output are reduced in the epilogue (reduce-scatter butterfly over
 //    the 32 pixel lanes -> LDS -> one double atomic per group per block).
 //  * Blocks are remapped so each XCD (private 4 MiB L2) owns a contiguous range of M panels.
-#include "kernels.h"
-
-__device__ u32x4 g_zero_page = {0u, 0u, 0u, 0u};
-
-#define GLDS16(gptr, lptr)                                                                             \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),            \
-                                     (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
-
-#define OPAQUE64(x)                                      \
-    do {                                                 \
-        int _lo = (int)(x), _hi = (int)((x) >> 32);      \
-        asm volatile("" : "+v"(_lo), "+v"(_hi));         \
-        (x) = ((long)_hi << 32) | (unsigned)_lo;         \
-    } while (0)
-
 #include "gemm_epi.h"
+
+// 16 bytes of zeros: what an out-of-image / K-tail lane reads instead of its operand.  One definition per translation unit that reads it (no
+// relocatable device code), with external linkage: as an internal-linkage definition in gemm_dev.h it moves the schedule of the kernels'
+// prologues (profiles/gemm_shared_index.txt).
+__device__ u32x4 g_zero_page = {0u, 0u, 0u, 0u};
 
 template <int WM, int WN, int TM, int TN, int BK, bool CONV, bool STATS, int NSTG = 2>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
@@ -58,28 +48,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
 
-    // ---- XCD-aware bijective block remap (block b runs on XCD b%8) ----
+    // XCD-contiguous block remap, then the L2-friendly super-tile order (tile_index.h)
     const int nbn = (p.N + BN - 1) / BN;
     const int nwg = gridDim.x;
-    int L;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
-    // L2-friendly tile order: N is cut into chunks of 8 tiles; inside a chunk tiles run M-major, so the ~64 blocks
-    // resident on one XCD form an (8 M-panels x 8 N-tiles) super-tile that shares 16 operand K-slices per step.
-    int bm, bn;
-    {
-        const int nbm = (p.M + BM - 1) / BM;
-        constexpr int GN = 8;
-        const int per_chunk = nbm * GN;
-        const int c = L / per_chunk;
-        const int wc = min(GN, nbn - c * GN);
-        const int rem = L - c * per_chunk;
-        bm = rem / wc;
-        bn = c * GN + rem - bm * wc;
-    }
-    const int m0 = bm * BM, n0 = bn * BN;
+    const TilePos tp = supertile_pos(xcd_remap(blockIdx.x, nwg), (p.M + BM - 1) / BM, nbn);
+    const int m0 = tp.bm * BM, n0 = tp.bn * BN;
     if ((p.dbg & 64) && (blockIdx.x & 8) && blockIdx.x < 256) {   // experiment: de-phase half of the first-round blocks
         for (int z = 0; z < (p.dbg >> 8); ++z) __builtin_amdgcn_s_sleep(127);
     }
@@ -96,13 +69,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     for (int i = 0; i < A_PC; ++i) {
         int m = m0 + RPP * (wave + NW * i) + lrow;
         m = m < p.M ? m : p.M - 1;
-        if (CONV) {
-            int b = m / p.Mper, q = m - b * p.Mper;        // sample, pixel within the sample
-            int oy = q / p.Wout, ox = q - oy * p.Wout;
-            a_pix[i] = (b << 24) | (oy << 12) | ox;
-        } else {
-            a_pix[i] = m;
-        }
+        a_pix[i] = CONV ? conv_pixel(p, m) : m;
     }
     const bf16* wbase = p.W + (size_t)(n0 + RPP * wave + lrow) * p.Kpad + lch * 8;
 
@@ -117,32 +84,24 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
             int ky = tap / p.KW, kx = tap - ky * p.KW;
 #pragma unroll
             for (int i = 0; i < A_PC; ++i) {
-                int bb = a_pix[i] >> 24, oy = (a_pix[i] >> 12) & 0xfff, ox = a_pix[i] & 0xfff;
-                int iy = oy * p.stride - p.pad + ky, ix = ox * p.stride - p.pad + kx;
-                bool ok = kok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-                long off = ok ? (long)(((size_t)((bb * p.Hin + iy) * p.Win + ix) * p.lda + c) * sizeof(bf16)) : zoff;
-                OPAQUE64(off);   // keep ONE DMA per piece (hipcc otherwise splits the select into exec-masked branches)
-                GLDS16(abase + off, adst + i * NW * 1024);
+                long off = conv_src_offset<sizeof(bf16)>(p, a_pix[i], ky, kx, c, kok, 0, zoff);
+                opaque64(off);
+                lds_dma16(abase + off, adst + i * NW * 1024);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < A_PC; ++i) {
                 long off = kok ? (long)(((size_t)a_pix[i] * p.lda + k) * sizeof(bf16)) : zoff;
-                OPAQUE64(off);
-                GLDS16(abase + off, adst + i * NW * 1024);
+                opaque64(off);
+                lds_dma16(abase + off, adst + i * NW * 1024);
             }
         }
 #pragma unroll
-        for (int i = 0; i < B_PC; ++i) GLDS16(wbase + (size_t)i * NW * RPP * p.Kpad + kt * BK, bdst + i * NW * 1024);
+        for (int i = 0; i < B_PC; ++i) lds_dma16(wbase + (size_t)i * NW * RPP * p.Kpad + kt * BK, bdst + i * NW * 1024);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    ACC_CLEAR(acc, TM, TN);
 
     const int nk = p.Kpad / BK;
     const int fr = lane & 31;          // fragment row within a 32-row sub-tile
@@ -162,10 +121,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
             buf = kt % NSTG;
             const int rem = nk - 1 - kt;             // stages after this one
             const int fly = rem < DEPTH - 1 ? rem : DEPTH - 1;   // stages allowed to stay in flight
-            if (fly >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PCW) : "memory");
-            else if (fly == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PCW) : "memory");
-            else if (fly == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(1 * PCW) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (fly >= 3) wait_vmcnt<3 * PCW>();
+            else if (fly == 2) wait_vmcnt<2 * PCW>();
+            else if (fly == 1) wait_vmcnt<1 * PCW>();
+            else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();            // stage kt landed for every wave; everyone is done with stage kt-1
             asm volatile("" ::: "memory");
             if (kt + DEPTH < nk) issue(kt + DEPTH, (kt + DEPTH) % NSTG);
@@ -236,11 +195,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int nbn = (p.N + BN - 1) / BN;
     const int nwg = gridDim.x;
-    int L;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int L = xcd_remap(blockIdx.x, nwg);
     const int bm = L / nbn, bn = L % nbn;
     const int m0 = bm * BM, n0 = bn * BN;
     const int lrow = lane >> 3;
@@ -254,13 +209,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs p) {
     for (int i = 0; i < 2; ++i) {
         int m = m0 + 8 * (wave + 4 * i) + lrow;
         m = m < p.M ? m : p.M - 1;
-        if (CONV) {
-            int b = m / p.Mper, q = m - b * p.Mper;        // sample, pixel within the sample
-            int oy = q / p.Wout, ox = q - oy * p.Wout;
-            a_pix[i] = (b << 24) | (oy << 12) | ox;
-        } else {
-            a_pix[i] = m;
-        }
+        a_pix[i] = CONV ? conv_pixel(p, m) : m;
     }
     const float* wbase = W + (size_t)(n0 + 8 * wave + lrow) * p.Kpad + lch * 4;
     auto issue = [&](int kt, int buf) {
@@ -279,22 +228,18 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs p) {
         for (int i = 0; i < 2; ++i) {
             long off;
             if (CONV) {
-                int bb = a_pix[i] >> 24, oy = (a_pix[i] >> 12) & 0xfff, ox = a_pix[i] & 0xfff;
-                int iy = oy * p.stride - p.pad + ky, ix = ox * p.stride - p.pad + kx;
-                bool ok = kok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-                off = ok ? (long)(((size_t)((bb * p.Hin + iy) * p.Win + ix) * p.lda + c) * sizeof(float)) : zoff;
+                off = conv_src_offset<sizeof(float)>(p, a_pix[i], ky, kx, c, kok, 0, zoff);
             } else {
                 off = kok ? (long)(((size_t)a_pix[i] * p.lda + k) * sizeof(float)) : zoff;
             }
-            OPAQUE64(off);
-            GLDS16(abase + off, adst + i * 4096);
+            opaque64(off);
+            lds_dma16(abase + off, adst + i * 4096);
         }
 #pragma unroll
-        for (int i = 0; i < 2; ++i) GLDS16(wbase + (size_t)i * 32 * p.Kpad + kt * BKF, bdst + i * 4096);
+        for (int i = 0; i < 2; ++i) lds_dma16(wbase + (size_t)i * 32 * p.Kpad + kt * BKF, bdst + i * 4096);
     };
     f32x16 acc[1][1];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
+    ACC_CLEAR(acc, 1, 1);
     const int nk = p.Kpad / BKF;
     const int fr = lane & 31, fh = lane >> 5;
     issue(0, 0);

@@ -2,7 +2,7 @@
 // The accumulator layout is the same for every operand format (C/D of v_mfma_f32_32x32x*), so bias / activation /
 // residual / fp32 + operand-format outputs / GroupNorm statistics are written once here.
 #pragma once
-#include "kernels.h"
+#include "gemm_dev.h"
 #include <type_traits>
 
 // ---- LDS-staged stores.  The MFMA leaves each lane with 4-channel quads of ONE pixel row, so direct stores touch
@@ -10,12 +10,7 @@
 // idle (measured: 40-80 % on top of the K loop for the ConvNeXt MLP shapes).  Instead every wave transposes its
 // 32 x (32 TN) accumulator slab through a private fp32 LDS tile (XOR-swizzled float4 chunks, conflict-free both ways;
 // the operand buffers are dead by now) and writes whole rows: a wave instruction covers 8 full 128-B lines (bf16) or
-// 4 x 256 B (fp32); residual reads are coalesced the same way.  Only wave-local ordering is needed (in-order LDS).
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// 4 x 256 B (fp32); residual reads are coalesced the same way.  Only wave-local ordering is needed (wave_lds_fence, common.h).
 template <int WM, int WN, int TM, int TN, bool STATS>
 __device__ __forceinline__ void gemm_store_staged(const GemmArgs& p, f32x16 (&acc)[TM][TN], int m0, int n0, int wm, int wn,
                                                   int lane, char* smem) {

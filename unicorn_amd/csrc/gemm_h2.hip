@@ -22,19 +22,9 @@
 #include <cstdlib>
 #include <cstring>
 
-__device__ u32x4 g_zero_page_h2 = {0u, 0u, 0u, 0u};
-
-#define GLDS16H(gptr, lptr)                                                                            \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),            \
-                                     (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
-#define OPAQUE64H(x)                                     \
-    do {                                                 \
-        int _lo = (int)(x), _hi = (int)((x) >> 32);      \
-        asm volatile("" : "+v"(_lo), "+v"(_hi));         \
-        (x) = ((long)_hi << 32) | (unsigned)_lo;         \
-    } while (0)
-
 #include "gemm_epi.h"
+
+__device__ u32x4 g_zero_page_h2 = {0u, 0u, 0u, 0u};      // (see gemm.hip)
 
 template <int WM, int WN, int TM, int TN, bool CONV, bool STATS, int BKE = 32>
 __global__ __launch_bounds__(64 * WM * WN, (BKE == 16 ? 2 : 1)) void gemm_h2_kernel(GemmArgs p) {
@@ -43,7 +33,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BKE == 16 ? 2 : 1)) void gemm_h2_ker
     constexpr int ROWB = 4 * BKE;            // LDS row bytes = BKE (k per step: 32 or 16) x (2 B hi + 2 B lo)
     constexpr int CPR = ROWB / 16;           // 16-B chunks per LDS row (8 or 4)
     constexpr int RPP = 64 / CPR;            // rows per 1-KiB DMA piece (8 or 16)
-    constexpr int SW = BKE == 32 ? 1 : 2;    // swizzle: chunk' = chunk ^ ((row >> SW) & (CPR-1))  (256-B bank period, see gemm.hip)
+    constexpr int SW = BKE == 32 ? 1 : 2;    // swizzle: chunk' = chunk ^ ((row >> SW) & (CPR-1))  (256-B bank period, see the header of gemm.hip)
     constexpr int A_PC = BM / RPP / NW, B_PC = BN / RPP / NW;
     static_assert(A_PC >= 1 && B_PC >= 1, "tile too small for the wave grid");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -55,25 +45,11 @@ __global__ __launch_bounds__(64 * WM * WN, (BKE == 16 ? 2 : 1)) void gemm_h2_ker
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
 
+    // XCD-contiguous block remap, then the L2-friendly super-tile order (tile_index.h)
     const int nbn = (p.N + BN - 1) / BN;
     const int nwg = gridDim.x;
-    int L;
-    {   // XCD-aware bijective block remap (block b runs on XCD b % 8)
-        const int b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
-    int bm, bn;
-    {   // super-tile order: chunks of 8 N tiles, M-major inside a chunk (see gemm.hip)
-        const int nbm = (p.M + BM - 1) / BM;
-        constexpr int GN = 8;
-        const int per_chunk = nbm * GN;
-        const int c = L / per_chunk;
-        const int wc = min(GN, nbn - c * GN);
-        const int rem = L - c * per_chunk;
-        bm = rem / wc;
-        bn = c * GN + rem - bm * wc;
-    }
-    const int m0 = bm * BM, n0 = bn * BN;
+    const TilePos tp = supertile_pos(xcd_remap(blockIdx.x, nwg), (p.M + BM - 1) / BM, nbn);
+    const int m0 = tp.bm * BM, n0 = tp.bn * BN;
 
     // ---- per-lane DMA sources: lane -> row lane/8 of its piece, physical chunk lane%8, logical chunk = phys ^ ((row>>1)&7);
     // logical chunk lc -> k group lc>>1 (8 k), half lc&1 (0 = hi, 1 = lo)
@@ -87,13 +63,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BKE == 16 ? 2 : 1)) void gemm_h2_ker
     for (int i = 0; i < A_PC; ++i) {
         int m = m0 + RPP * (wave + NW * i) + lrow;
         m = m < p.M ? m : p.M - 1;
-        if (CONV) {
-            int b = m / p.Mper, q = m - b * p.Mper;
-            int oy = q / p.Wout, ox = q - oy * p.Wout;
-            a_pix[i] = (b << 24) | (oy << 12) | ox;
-        } else {
-            a_pix[i] = m;
-        }
+        a_pix[i] = CONV ? conv_pixel(p, m) : m;
     }
     const char* wbase = reinterpret_cast<const char*>(p.W) + ((size_t)(n0 + RPP * wave + lrow) * p.Kpad) * 4 + lch * 16;
 
@@ -108,38 +78,30 @@ __global__ __launch_bounds__(64 * WM * WN, (BKE == 16 ? 2 : 1)) void gemm_h2_ker
             int ky = tap / p.KW, kx = tap - ky * p.KW;
 #pragma unroll
             for (int i = 0; i < A_PC; ++i) {
-                int bb = a_pix[i] >> 24, oy = (a_pix[i] >> 12) & 0xfff, ox = a_pix[i] & 0xfff;
-                int iy = oy * p.stride - p.pad + ky, ix = ox * p.stride - p.pad + kx;
-                bool ok = kok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-                long off = ok ? (long)(((size_t)((bb * p.Hin + iy) * p.Win + ix) * p.lda + c) * 4 + half * 16) : zoff;
-                OPAQUE64H(off);
-                GLDS16H(abase + off, adst + i * NW * 1024);
+                long off = conv_src_offset<4>(p, a_pix[i], ky, kx, c, kok, half, zoff);
+                opaque64(off);
+                lds_dma16(abase + off, adst + i * NW * 1024);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < A_PC; ++i) {
                 long off = kok ? (long)(((size_t)a_pix[i] * p.lda + k) * 4 + half * 16) : zoff;
-                OPAQUE64H(off);
-                GLDS16H(abase + off, adst + i * NW * 1024);
+                opaque64(off);
+                lds_dma16(abase + off, adst + i * NW * 1024);
             }
         }
 #pragma unroll
-        for (int i = 0; i < B_PC; ++i) GLDS16H(wbase + ((size_t)i * NW * RPP * p.Kpad + (size_t)kt * BKE) * 4, bdst + i * NW * 1024);
+        for (int i = 0; i < B_PC; ++i) lds_dma16(wbase + ((size_t)i * NW * RPP * p.Kpad + (size_t)kt * BKE) * 4, bdst + i * NW * 1024);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    ACC_CLEAR(acc, TM, TN);
 
     int kt0 = 0, nk = (p.K + BKE - 1) / BKE;           // the packed weights are zero beyond K (Kpad >= roundup(K, 64))
     if (p.splitk > 1) {                                // split-K: this block owns K steps [kt0, nk) of its tile
-        const int per = (nk + p.splitk - 1) / p.splitk;
-        kt0 = blockIdx.y * per;
-        nk = min(nk, kt0 + per);       // an empty range (kt0 >= nk) still stores its (zero) partial tile: the reduce kernel reads every slab
+        const KRange kr = splitk_range(nk, p.splitk, blockIdx.y);      // an empty range (kt0 >= nk) still stores its (zero) partial tile: the reduce kernel reads every slab
+        kt0 = kr.kt0;
+        nk = kr.nk;
     }
     const int fr = lane & 31, fh = lane >> 5;
     if (kt0 < nk) issue(kt0, 0);

@@ -12,23 +12,7 @@
 // 8 waves, 256 x 192 with 2 slots (the 256-wide problems whose N = 192 k would pad the ping-pong kernel's 256 x 256 tiles).
 // Same operand format, loader geometry, swizzle, epilogue (gemm_epi.h) and split-K protocol (slab + splitk_reduce_kernel) as
 // gemm_h2.hip; results are bit-identical to gemm_h2_kernel's for the same K order (same MFMA sequence per accumulator).
-#include "kernels.h"
-
-#define D_LDS(addr) (*reinterpret_cast<const __attribute__((address_space(3))) f16x8*>((size_t)(addr)))
-
 #include "gemm_epi.h"
-
-namespace {
-__device__ __forceinline__ void d_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-template <int N>
-__device__ __forceinline__ void d_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-}  // namespace
 
 // SPEC (round 5, 4-wave tiles only): the block carries 4 MORE waves that do nothing but issue the LDS-DMA requests -- one producer and one
 // consumer per SIMD.  With one wave per SIMD the 7 requests of a K step sit in the same in-order instruction stream as the MFMAs: a request
@@ -59,27 +43,13 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1), ((WM * WN > 4 || SPE
     const int wave = SPEC ? (wave_all & (NW - 1)) : wave_all;      // a producer issues the pieces of the consumer with the same index
     const int wm = wave / WN, wn = wave % WN;
 
+    // XCD-contiguous block remap, then the super-tile order (tile_index.h): the blocks of an XCD share A rows and a window of W in its L2
     const int nbn = (p.N + BN - 1) / BN;
     const int nwg = gridDim.x;
-    int L;
-    {   // XCD-aware bijective block remap (block b runs on XCD b % 8)
-        const int b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
-    int bm, bn;
-    {   // chunks of 8 N tiles, M-major inside a chunk: the blocks of an XCD share A rows and a window of W in its L2
-        const int nbm = (p.M + BM - 1) / BM;
-        constexpr int GN = 8;
-        const int per_chunk = nbm * GN;
-        const int c = L / per_chunk;
-        const int wc = min(GN, nbn - c * GN);
-        const int rem = L - c * per_chunk;
-        bm = rem / wc;
-        bn = c * GN + rem - bm * wc;
-    }
-    const int m0 = bm * BM, n0 = bn * BN;
+    const TilePos tp = supertile_pos(xcd_remap(blockIdx.x, nwg), (p.M + BM - 1) / BM, nbn);
+    const int m0 = tp.bm * BM, n0 = tp.bn * BN;
 
-    // ---- DMA (the addressing of gemm_h2q.hip): `buffer_load_dwordx4 ... lds` through one descriptor per operand; wave w fills the
+    // ---- DMA (descriptor addressing, gemm_dev.h): `buffer_load_dwordx4 ... lds` through one descriptor per operand; wave w fills the
     // 1-KiB pieces w, w + NW, ... (8 rows each); lane -> row lane / 8 of the piece, physical 16-B chunk lane % 8, which holds the
     // row's LOGICAL chunk lch = phys ^ ((row >> 1) & 7) (k group lch >> 1, half lch & 1).  Per-lane offsets are constant, the K step
     // (and the conv tap) travel in the scalar offset; rows past M / N and taps outside the image present an offset beyond
@@ -103,7 +73,7 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1), ((WM * WN > 4 || SPE
         for (int i = 0; i < A_PC; ++i) voa[i] = (RPP * (wave + NW * i) + lrow) * lda4 + lch * 16;
     } else {
         // the descriptor starts (pad, pad) pixels before the tile's first input pixel; per-lane offset = the lane's pixel relative to
-        // that (26 bits) | 6 flag bits: bit ky = input row of tap row ky inside the image, bit 3 + kx the same for the column
+        // that (26 bits) | 6 flag bits: bit ky = input row of tap row ky inside the image, bit 3 + kx the same for the column (gemm_dev.h)
         const int b0 = m0 / p.Mper, q0 = m0 - b0 * p.Mper, oy0 = q0 / p.Wout, ox0 = q0 - oy0 * p.Wout;
         const int pix0 = (b0 * p.Hin + oy0 * p.stride) * p.Win + ox0 * p.stride;
         rs_a = __builtin_amdgcn_make_buffer_rsrc(abase + ((long)pix0 - (p.pad * p.Win + p.pad)) * lda4, 0, 0x7ffffff0, 0x00020000);
@@ -125,10 +95,8 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1), ((WM * WN > 4 || SPE
         }
     }
     const int cs = CONV ? p.Cin / BKE : 1;           // K steps per tap (Cin % 32 == 0: a K step = 32 channels of ONE tap)
-    const int csm = 65536 / cs + 1;                  // kt / cs = (kt * csm) >> 16 for kt < 9 cs <= 2^12 (launcher checks)
-    const int kwm = p.KW == 3 ? 11 : p.KW == 2 ? 16 : 32;   // tap / KW = (tap * kwm) >> 5 for tap < 9
-#define D_DMA(rs, vo, soff, dst) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst), 16, vo, soff, 0, 0)
+    const int csm = tap_csm(cs);                     // the tap decode of tile_index.h: exact for cs <= TAP_DECODE_MAX_CS (gemm_h2d_supported)
+    const int kwm = tap_kwm(p.KW);
     // `live` false (past the end of the K range): the requests still go out, with offsets beyond num_records -- the number of
     // requests in flight stays constant, so the K loop has ONE wait count and no branch around the DMA
     auto issue = [&](int kt, int slot, bool live) __attribute__((always_inline)) {
@@ -136,34 +104,29 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1), ((WM * WN > 4 || SPE
         char* bdst = adst + BM * ROWB;
         if (!CONV) {
 #pragma unroll
-            for (int i = 0; i < A_PC; ++i) D_DMA(rs_a, live ? voa[i] : 0x7fffffff, kt * ROWB, adst + i * NW * 1024);
+            for (int i = 0; i < A_PC; ++i) lds_dma16_buf(rs_a, adst + i * NW * 1024, live ? voa[i] : DESC_OUT_OF_RANGE, kt * ROWB);
         } else {
-            const int tap = (kt * csm) >> 16, cstep = kt - tap * cs;
-            const int ky = (tap * kwm) >> 5, kx = tap - ky * p.KW;
+            const int tap = tap_index(kt, csm), cstep = kt - tap * cs;
+            const int ky = tap_row(tap, kwm), kx = tap - ky * p.KW;
             const int soff = live ? (ky * p.Win + kx) * lda4 + cstep * ROWB : 0;
 #pragma unroll
             for (int i = 0; i < A_PC; ++i) {
                 const bool ok = live && ((voa[i] >> (26 + ky)) & (voa[i] >> (29 + kx)) & 1) != 0;
-                D_DMA(rs_a, ok ? (voa[i] & 0x03ffffff) : 0x7fffffff, soff, adst + i * NW * 1024);
+                lds_dma16_buf(rs_a, adst + i * NW * 1024, ok ? (voa[i] & DESC_OFFSET_MASK) : DESC_OUT_OF_RANGE, soff);
             }
         }
 #pragma unroll
-        for (int i = 0; i < B_PC; ++i) D_DMA(rs_b, live ? vob[i] : 0x7fffffff, kt * ROWB, bdst + i * NW * 1024);
+        for (int i = 0; i < B_PC; ++i) lds_dma16_buf(rs_b, bdst + i * NW * 1024, live ? vob[i] : DESC_OUT_OF_RANGE, kt * ROWB);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    ACC_CLEAR(acc, TM, TN);
 
     int kt0 = 0, nk = (p.K + BKE - 1) / BKE;           // the packed weights are zero beyond K (Kpad >= roundup(K, 64))
     if (p.splitk > 1) {                                // split-K: this block owns K steps [kt0, nk) of its tile (empty range: zero partials)
-        const int per = (nk + p.splitk - 1) / p.splitk;
-        kt0 = blockIdx.y * per;
-        nk = min(nk, kt0 + per);
+        const KRange kr = splitk_range(nk, p.splitk, blockIdx.y);
+        kt0 = kr.kt0;
+        nk = kr.nk;
     }
     // fragment addresses inside a stage: row r, logical chunk ch at (ch ^ ((r >> 1) & 7)) * 16
     const int fr = lane & 31, fh = lane >> 5;
@@ -183,14 +146,14 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1), ((WM * WN > 4 || SPE
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int sw = (arow[i] >> 1) & 7, ra = sbase + arow[i] * ROWB;
-            ah[set][i] = D_LDS(ra + ((ch ^ sw) << 4));
-            al[set][i] = D_LDS(ra + (((ch + 1) ^ sw) << 4));
+            ah[set][i] = lds_read_f16x8(ra + ((ch ^ sw) << 4));
+            al[set][i] = lds_read_f16x8(ra + (((ch + 1) ^ sw) << 4));
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int sw = (brow[j] >> 1) & 7, rb = sbase + brow[j] * ROWB;
-            bh[set][j] = D_LDS(rb + ((ch ^ sw) << 4));
-            bl[set][j] = D_LDS(rb + (((ch + 1) ^ sw) << 4));
+            bh[set][j] = lds_read_f16x8(rb + ((ch ^ sw) << 4));
+            bl[set][j] = lds_read_f16x8(rb + (((ch + 1) ^ sw) << 4));
         }
     };
     // swapped operands (weights = MFMA A): lane -> pixel row, 4 consecutive channels per accumulator quad
@@ -212,7 +175,7 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1), ((WM * WN > 4 || SPE
     int rd = 0, wr = NST - 1;
     __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0): no scalar load pending at the loop head, so the waits on the fragment reads inside can be counted
     for (int kt = kt0; kt < nk; ++kt) {
-        if (!SPEC || producer) d_wait_vm<(NST - 2) * PER>();   // slice kt landed (this wave's share); NST - 2 younger ones stay in flight
+        if (!SPEC || producer) wait_vmcnt<(NST - 2) * PER>();   // slice kt landed (this wave's share); NST - 2 younger ones stay in flight
         __builtin_amdgcn_s_waitcnt(0xc07f);                // lgkmcnt(0): this wave's reads of slice kt-1 are complete (its slot is requested below)
         d_barrier();                                       // ... everybody's share; everybody is done with the slot of slice kt-1
         const int sbase = lds0 + rd * STAGE;
@@ -257,12 +220,12 @@ __global__ __launch_bounds__(64 * WM * WN * (SPEC ? 2 : 1), ((WM * WN > 4 || SPE
         __builtin_amdgcn_sched_barrier(0);
     }
     if (SPEC && producer) {      // every request (the dead ones past the K range too) has landed; leave through the epilogue's first barrier
-        d_wait_vm<0>();
+        wait_vmcnt<0>();
         __syncthreads();
         return;
     }
     mma(1, 0); mma(1, 1); mma(1, 2);
-    d_wait_vm<0>();
+    wait_vmcnt<0>();
     if (p.wscale != 1.f) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -321,7 +284,7 @@ bool gemm_h2d_supported(const GemmArgs& a, int cfg) {
     const long rows = cfg == 346 ? 256 : 128;    // tallest tile of the configuration (A rows / weight rows addressed from one descriptor base)
     if (rows * a.lda * 4 >= (1L << 30) || rows * a.Kpad * 4 >= (1L << 30)) return false;
     if (conv) {
-        if (a.Cin % 32 != 0 || a.KH > 3 || a.KW > 3 || a.K != a.KH * a.KW * a.Cin || a.Cin / 32 > 448) return false;
+        if (a.Cin % 32 != 0 || a.KH > 3 || a.KW > 3 || a.K != a.KH * a.KW * a.Cin || a.Cin / 32 > TAP_DECODE_MAX_CS) return false;
         // the input pixels of one row tile must lie within 2^26 bytes of its first one (the per-lane offsets carry 6 flag bits)
         const long span_pix = (rows / a.Wout + 2) * a.stride * a.Win + rows * a.stride + 3L * a.Win;
         if (span_pix * a.lda * 4 >= (1L << 26)) return false;

@@ -37,35 +37,14 @@ struct Tile { int m0, n0, k0, split; };      // k0: first K step of the unit (sp
 // A side of a tile: buffer descriptor + per-lane offsets [half][piece]; CONV: byte offset (< 2^26, launcher checks) | validity bits << 26.
 // (At namespace scope: a struct local to the kernel template makes hipcc drop the host stubs of its instantiations.)
 struct ATile { __amdgpu_buffer_rsrc_t rs; int vo[2][2]; };
-// unit u of a split-K launch = (K range u / ntiles, tile u % ntiles): neighbouring units are different tiles of the same K range (shared panels)
+// work unit u (tile_index.h: supertile_split_pos) of a launch with nku K steps per unit
 __device__ __forceinline__ Tile tile_of(int u, int nbm, int nbn, int nku) {
-    const int ntiles = nbm * nbn;
-    const int split = u / ntiles, L = u - split * ntiles;
-    constexpr int GN = 8;           // N is cut into chunks of 8 tiles; inside a chunk tiles run M-major (see gemm.hip)
-    const int per_chunk = nbm * GN;
-    const int c = L / per_chunk;
-    const int wc = min(GN, nbn - c * GN);
-    const int rem = L - c * per_chunk;
-    const int bm = rem / wc;
-    return {bm * BM, (c * GN + rem - bm * wc) * BN, split * nku, split};
-}
-__device__ __forceinline__ void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// raw workgroup barrier that neither the IR optimiser nor the machine scheduler moves anything across
-__device__ __forceinline__ void phase_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
+    const SplitTilePos t = supertile_split_pos(u, nbm, nbn, BM, BN);
+    return {t.bm, t.bn, t.split * nku, t.split};
 }
 }  // namespace
 
 #define Q_WAIT_LDS() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define Q_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
 // FMT = FMT_H2: split-f16 operands, 32 k per step, 3 MFMAs per product; FMT = FMT_BF16: the bf16 twin on the same schedule -- 64 k per
 // step in the same 128-byte rows, 4 k slices, 1 MFMA per product (its 8-MFMA phases are shorter than the LDS/DMA phases: that
@@ -82,17 +61,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
     const int fr = lane & 31, fh = lane >> 5;
 
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
+    const int nunits = nbm * nbn * (p.splitk > 1 ? p.splitk : 1);      // work units = tiles x K ranges
     int first, stride, count;
-    {
-        const int ntiles = nbm * nbn * (p.splitk > 1 ? p.splitk : 1);      // work units
-        const int x = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        const int cnt = q + (x < r ? 1 : 0);
-        first = start + slot;
-        stride = nslots;
-        count = slot < cnt ? (cnt - slot + nslots - 1) / nslots : 0;
-    }
+    persistent_units(blockIdx.x, gridDim.x, nunits, first, stride, count);
     if (count == 0) return;
 
     // ---- DMA: wave w fills pieces w and w + 8 (8 rows = 1 KiB each) of every half-tile; lane -> row lane / 8 of the piece, 16-byte
@@ -110,10 +81,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
         for (int i = 0; i < 2; ++i) vob[h][i] = ((wave >> 2) * 64 + 8 * (wave & 3) + lrow + 128 * i + 32 * h) * ldw4 + lch * 16;     // tile column
     const int arow = 8 * wave + lrow;                // tile row of piece i, half h: arow + 128 i + 64 h
     // A side of one tile.  Plain GEMM: the descriptor starts at the tile's first row, per-lane offsets are tile independent.
-    // Implicit GEMM (CONV; Cin % 32 == 0, so a K step = 32 channels of ONE tap): the descriptor starts (pad, pad) pixels before the
-    // tile's first input pixel, the per-lane offset is the lane's pixel relative to that, the tap (ky, kx) and the channel block
-    // travel in the scalar offset ((ky Win + kx) lda + c) -- never negative -- and a lane whose tap falls outside the image (or
-    // whose row is past M) presents an offset beyond num_records: the buffer load returns zeros, which IS the zero padding.
+    // Implicit GEMM (CONV; Cin a multiple of KS, so a K step = KS channels of ONE tap): the descriptor addressing described in gemm_dev.h.
     auto make_a = [&](Tile tl, ATile& c) __attribute__((always_inline)) {
         char* abase = const_cast<char*>(reinterpret_cast<const char*>(p.A));
         if (!CONV) {
@@ -151,30 +119,28 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.W)) + (long)tl.n0 * ldw4, 0, BN * ldw4, 0x00020000);
     };
     const int cs = CONV ? p.Cin / KS : 1;            // K steps per tap
-    const int csm = 65536 / cs + 1;                  // fk / cs = (fk * csm) >> 16 for fk < 9 cs <= 2^12 (launcher checks)
-    const int kwm = p.KW == 3 ? 11 : p.KW == 2 ? 16 : 32;   // tap / KW = (tap * kwm) >> 5 for tap < 9
-#define Q_DMA(rs, vo, soff, dst) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst), 16, vo, soff, 0, 0)
+    const int csm = tap_csm(cs);                     // the tap decode of tile_index.h: exact for cs <= TAP_DECODE_MAX_CS (gemm_h2q_supported)
+    const int kwm = tap_kwm(p.KW);
     auto issueA = [&](int h, int par, int kt, const ATile& c) __attribute__((always_inline)) {
         char* dst = smem + par * STAGE + h * HALF + wave * 1024;
         if (!CONV) {
-            Q_DMA(c.rs, c.vo[h][0], kt * ROWB, dst);
-            Q_DMA(c.rs, c.vo[h][1], kt * ROWB, dst + 8192);
+            lds_dma16_buf(c.rs, dst, c.vo[h][0], kt * ROWB);
+            lds_dma16_buf(c.rs, dst + 8192, c.vo[h][1], kt * ROWB);
         } else {
-            const int tap = (kt * csm) >> 16, cstep = kt - tap * cs;
-            const int ky = (tap * kwm) >> 5, kx = tap - ky * p.KW;
+            const int tap = tap_index(kt, csm), cstep = kt - tap * cs;
+            const int ky = tap_row(tap, kwm), kx = tap - ky * p.KW;
             const int soff = (ky * p.Win + kx) * lda4 + cstep * ROWB;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const bool ok = ((c.vo[h][i] >> (26 + ky)) & (c.vo[h][i] >> (29 + kx)) & 1) != 0;
-                Q_DMA(c.rs, ok ? (c.vo[h][i] & 0x03ffffff) : 0x7fffffff, soff, dst + i * 8192);
+                lds_dma16_buf(c.rs, dst + i * 8192, ok ? (c.vo[h][i] & DESC_OFFSET_MASK) : DESC_OUT_OF_RANGE, soff);
             }
         }
     };
     auto issueB = [&](int h, int par, int kt, __amdgpu_buffer_rsrc_t rs) __attribute__((always_inline)) {
         char* dst = smem + par * STAGE + (2 + h) * HALF + wave * 1024;
-        Q_DMA(rs, vob[h][0], kt * ROWB, dst);
-        Q_DMA(rs, vob[h][1], kt * ROWB, dst + 8192);
+        lds_dma16_buf(rs, dst, vob[h][0], kt * ROWB);
+        lds_dma16_buf(rs, dst + 8192, vob[h][1], kt * ROWB);
     };
 
     // ---- fragment reads: group `grp` reads rows 64 grp + 32 i + fr of an A half, wave column wc rows 32 wc + fr of a B half;
@@ -188,7 +154,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
     if (lds0 != 0) __builtin_trap();                 // the stage toggle below XORs bit 16 of the addresses: the dynamic LDS block must start at 0
     int ra4[4] = {lds0 + a_rd + ((q0 ^ sw) << 4), lds0 + a_rd + ((q1 ^ sw) << 4), lds0 + a_rd + ((q2 ^ sw) << 4), lds0 + a_rd + ((q3 ^ sw) << 4)};
     int rb4[4] = {lds0 + b_rd + ((q0 ^ sw) << 4), lds0 + b_rd + ((q1 ^ sw) << 4), lds0 + b_rd + ((q2 ^ sw) << 4), lds0 + b_rd + ((q3 ^ sw) << 4)};
-#define Q_LDS(addr, off) (*reinterpret_cast<const __attribute__((address_space(3))) f16x8*>((size_t)((addr) + (off))))
 
     f32x16 acc[4][2];
     // fragment registers [.][0..3]: f16x2 = (hi, lo) of k slice 0, (hi, lo) of k slice 1; bf16 = k slices 0..3.  B fragments of both
@@ -204,8 +169,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
 
 #define Q_LD_A(h)                                                                                   \
     _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int q = 0; q < 4; ++q)      \
-        fa[i][q] = Q_LDS(ra4[q], (h) * HALF + i * 32 * ROWB);
-#define Q_LD_B(h) _Pragma("unroll") for (int q = 0; q < 4; ++q) fb[h][q] = Q_LDS(rb4[q], (h) * HALF);
+        fa[i][q] = lds_read_f16x8(ra4[q] + (h) * HALF + i * 32 * ROWB);
+#define Q_LD_B(h) _Pragma("unroll") for (int q = 0; q < 4; ++q) fb[h][q] = lds_read_f16x8(rb4[q] + (h) * HALF);
     // quadrant (HA, HB): accumulator tiles (2 HA + i, HB); per k slice the two cross terms first, then hi.hi
 #define Q_MF16(b, a, c) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, c, 0, 0, 0)
 #define Q_MB16(b, a, c) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), c, 0, 0, 0)
@@ -245,18 +210,13 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
         Q_FUT(1);
         issueA(0, 1, fk, fa); issueB(1, 1, fk, fb); issueA(1, 1, fk, fa);
     }
-    Q_WAIT_VM(6);
+    wait_vmcnt<6>();
     phase_barrier();
     if (grp == 1) phase_barrier();                    // the second group runs one barrier behind
     int par = 0;
 #pragma unroll 1
     for (int t = 0; t < count; ++t) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        ACC_CLEAR(acc, 4, 2);
 #pragma unroll 1
         for (int kt = 0; kt < nk; ++kt) {
             {   // phase 1
@@ -284,7 +244,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
             }
             {   // phase 4 (B0 is still in registers)
                 if (!(p.dbg & 1)) { Q_FUT(2); issueB(1, par, fk, fb); issueA(1, par, fk, fa); }
-                Q_WAIT_VM(6);
+                wait_vmcnt<6>();
                 Q_WAIT_LDS();
                 phase_barrier();
                 if (!(p.dbg & 2)) { Q_MFMA(1, 0); }
@@ -377,7 +337,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
                     for (int e = 0; e < 4; ++e) v[e] = act_fast<ACT>(fmaf(acc[i][j][4 * g + e], ws, bv[4 * g + e]));
                     *reinterpret_cast<f32x4*>(st + fr * 128 + (((2 * g + fh) ^ (fr & 7)) << 4)) = v;
                 }
-                wave_fence();
+                wave_lds_fence();
                 if (OUTF) {        // fp32 (+ residual) output, optional operand-format copy: 4 channels per lane, 8 rows per instruction
                     const int c = lane & 7, rr = lane >> 3;
                     const int col = nw0 + j * 32 + 4 * c;
@@ -420,7 +380,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
                         }
                     }
                 }
-                wave_fence();
+                wave_lds_fence();
             }
         }
         if (STATS) {
@@ -429,7 +389,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
             if (grp == 1) phase_barrier();
         }
     }
-    Q_WAIT_VM(0);                                     // the stream's last requests (never consumed) must not outlive the block's LDS
+    wait_vmcnt<0>();                                     // the stream's last requests (never consumed) must not outlive the block's LDS
     if (grp == 0) phase_barrier();                    // barrier count of the two groups evens out
 }
 
@@ -454,7 +414,7 @@ bool gemm_h2q_supported(const GemmArgs& a) {
         return a.out_hw == 0 && (a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_GELU) && (a.outF || a.outB) && (a.outF || !a.res);   // (bias optional)
     }
     if (conv) {
-        if (a.Cin % ks != 0 || a.KH > 3 || a.KW > 3 || a.K != a.KH * a.KW * a.Cin || a.Cin / ks > 448) return false;
+        if (a.Cin % ks != 0 || a.KH > 3 || a.KW > 3 || a.K != a.KH * a.KW * a.Cin || a.Cin / ks > TAP_DECODE_MAX_CS) return false;
         // the input pixels of one 256-row tile must lie within 2^26 bytes of its first one (the per-lane offsets carry 6 flag bits)
         const long span_pix = ((long)BM / a.Wout + 2) * a.stride * a.Win + (long)BM * a.stride + 3L * a.Win;
         if (span_pix * a.lda * eb >= (1L << 26)) return false;

@@ -11,13 +11,7 @@
 //     [32][32] otherwise) and only issues its stores; they drain under the next tile's K loop;
 //   * tile order: XCD-contiguous ranges, blocks of one XCD take consecutive tiles (operand panels shared in its L2).
 // The K loop itself is unchanged (one barrier per step).
-#include "kernels.h"
-
-__device__ u32x4 g_zero_page_p44 = {0u, 0u, 0u, 0u};
-
-#define GLDS16Q(gptr, lptr)                                                                            \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),            \
-                                     (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
+#include "gemm_dev.h"
 
 namespace {
 constexpr int WM = 4, WN = 4, TM = 2, TN = 2, NW = WM * WN;
@@ -27,19 +21,9 @@ constexpr int A_PC = BM / RPP / NW, B_PC = BN / RPP / NW;          // 2 + 2 piec
 constexpr int LDS_BYTES = 2 * (BM + BN) * BK * 2;                  // 131072
 
 struct Tile { int m0, n0; };
-__device__ __forceinline__ Tile tile_of(int L, int nbm, int nbn) {
-    constexpr int GN = 8;           // N is cut into chunks of 8 tiles; inside a chunk tiles run M-major (see gemm.hip)
-    const int per_chunk = nbm * GN;
-    const int c = L / per_chunk;
-    const int wc = min(GN, nbn - c * GN);
-    const int rem = L - c * per_chunk;
-    const int bm = rem / wc;
-    return {bm * BM, (c * GN + rem - bm * wc) * BN};
-}
-__device__ __forceinline__ void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+__device__ __forceinline__ Tile tile_of(int L, int nbm, int nbn) {      // super-tile order (tile_index.h)
+    const TilePos t = supertile_pos(L, nbm, nbn, BM, BN);
+    return {t.bm, t.bn};
 }
 }  // namespace
 
@@ -57,20 +41,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_p44_kernel(GemmArgs p) {
     const int fr = lane & 31, fh = lane >> 5;
 
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
+    const int ntiles = nbm * nbn;
     int first, stride, count;
-    {
-        const int ntiles = nbm * nbn;
-        const int x = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        const int cnt = q + (x < r ? 1 : 0);
-        first = start + slot;
-        stride = nslots;
-        count = slot < cnt ? (cnt - slot + nslots - 1) / nslots : 0;
-    }
+    persistent_units(blockIdx.x, gridDim.x, ntiles, first, stride, count);
     if (count == 0) return;
 
-    // ---- per-lane DMA sources (swizzle on the source side, see gemm.hip) ----
+    // ---- per-lane DMA sources (swizzle on the source side, see the header of gemm.hip) ----
     const int lrow = lane / CPR;
     const int lch = (lane % CPR) ^ (((RPP * wave + lrow) >> 1) & (CPR - 1));
     const char* abase = reinterpret_cast<const char*>(p.A) + lch * 16;
@@ -91,9 +67,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_p44_kernel(GemmArgs p) {
         char* adst = reinterpret_cast<char*>(As + buf * BM * BK) + wave * 1024;
         char* bdst = reinterpret_cast<char*>(Bs + buf * BN * BK) + wave * 1024;
 #pragma unroll
-        for (int i = 0; i < A_PC; ++i) GLDS16Q(abase + aoff[i] + kt * (BK * 2), adst + i * NW * 1024);
+        for (int i = 0; i < A_PC; ++i) lds_dma16(abase + aoff[i] + kt * (BK * 2), adst + i * NW * 1024);
 #pragma unroll
-        for (int i = 0; i < B_PC; ++i) GLDS16Q(wbase + woff[i] + kt * (BK * 2), bdst + i * NW * 1024);
+        for (int i = 0; i < B_PC; ++i) lds_dma16(wbase + woff[i] + kt * (BK * 2), bdst + i * NW * 1024);
     };
 
     f32x16 acc[TM][TN];
@@ -105,12 +81,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_p44_kernel(GemmArgs p) {
     issue(0, 0);
 #pragma unroll 1
     for (int t = 0; t < count; ++t) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        ACC_CLEAR(acc, TM, TN);
 #pragma unroll 1
         for (int kt = 0; kt < nk; ++kt) {
             __syncthreads();                          // K slice landed; every wave is done with the other buffer (and its staging)
@@ -195,7 +166,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_p44_kernel(GemmArgs p) {
                         *reinterpret_cast<u32x2*>(st + fr * 128 + chunk * 16 + fh * 8) = o2;
                     }
                 }
-                wave_fence();
+                wave_lds_fence();
                 const int q = lane & 7, rr = lane >> 3;
                 const int col = nw0 + 8 * q;
 #pragma unroll
@@ -204,7 +175,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_p44_kernel(GemmArgs p) {
                     const u32x4 o4 = *reinterpret_cast<const u32x4*>(st + r * 128 + ((q ^ ((r >> 1) & 7)) << 4));
                     if (row < p.M && col < p.N) *reinterpret_cast<u32x4*>(p.outB + (size_t)row * p.ldb + col) = o4;
                 }
-                wave_fence();
+                wave_lds_fence();
             } else {
                 // fp32 [32 rows][32 cols] per 32-column block j (128-B rows); float4 chunks XOR-swizzled with row & 7
                 const bool has_res = p.res != nullptr, has_b = p.outB != nullptr;
@@ -219,7 +190,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_p44_kernel(GemmArgs p) {
                         for (int e = 0; e < 4; ++e) v[e] = act_fast<ACT>(acc[i][j][4 * g + e] + b4[e]);
                         *reinterpret_cast<f32x4*>(st + fr * 128 + (((2 * g + fh) ^ (fr & 7)) << 4)) = v;
                     }
-                    wave_fence();
+                    wave_lds_fence();
                     const int c = lane & 7, rr = lane >> 3;
                     const int col = nw0 + j * 32 + 4 * c;
 #pragma unroll
@@ -236,7 +207,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_p44_kernel(GemmArgs p) {
                             }
                         }
                     }
-                    wave_fence();
+                    wave_lds_fence();
                 }
             }
         }

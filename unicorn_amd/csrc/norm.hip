@@ -6,6 +6,7 @@
 // All statistics in fp32 with a two-pass (mean, then centred variance) reduction; deterministic
 // (no float atomics).  NHWC everywhere so a wave's lanes walk the channel axis (coalesced 16-B accesses).
 #include "kernels.h"
+#include "tile_index.h"
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm: one wave per row, the row lives in registers (C <= 1536 -> <= 6 float4 per lane)
@@ -285,11 +286,7 @@ __global__ __launch_bounds__(512) void dwconv7_ln_kernel(DwLnArgs p, int S, int 
     const int cg = tid % CG, sl = tid / CG;
     // XCD-aware remap (block b runs on XCD b%8, private L2): give each XCD a contiguous band of strips/rows so the
     // 7-row halo re-reads hit its own L2 instead of every XCD pulling the whole map through the fabric.
-    int blk;
-    {
-        const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
     const int strip = blk * S + sl;
     const bool active = sl < S && strip < nstrips;
     const int yg = active ? strip / spr : 0;                    // row over the whole batch
@@ -403,11 +400,7 @@ __global__ __launch_bounds__(384) void dwconv7_ln2_kernel(DwLnArgs p, int S, int
     extern __shared__ float lds[];
     const int tid = threadIdx.x;
     const int cg = tid % CG, sl = tid / CG;
-    int blk;
-    {
-        const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
     const int strip = blk * S + sl;
     const bool active = sl < S && strip < nstrips;
     const int HP = (p.H + 1) >> 1;                               // row pairs per image
@@ -547,6 +540,8 @@ __global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S,
     const bool lane_ok = PACK || cg0 < CG;
     const int cg = lane_ok ? cg0 : 0;                            // idle lanes shadow channel group 0 and store nothing
     const int kso = ks * PX * C;                                 // the lane's strip in elements from the group's first pixel
+    // the block's strip groups first, first + step, ...: persistent_units of tile_index.h, written out here -- through the function one of the
+    // nine builds (C = 384, unpacked) is scheduled differently (profiles/gemm_shared_index.txt); tools/tile_index_check.cpp checks the function
     int first, step, count;
     {
         const int nblk = (nstrips + S - 1) / S;
@@ -595,7 +590,7 @@ __global__ __launch_bounds__(NW * 64) void dwconv7_lnb_kernel(DwLnArgs p, int S,
         float* rb = red + buf * (NSLOT * 16);
         if ((lane & ((1 << LG) - 1)) == 0) rb[((wv * 64 + lane) / G) * 16 + ((lane >> LG) & 15)] = t;
         // a strip that is ONE wave (C <= 256) needs no block barrier: the strips of a block are independent
-        if (wps == 1) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+        if (wps == 1) wave_lds_fence();
         else __syncthreads();
 #pragma unroll
         for (int o = 0; o < 16; ++o) tot[o] = 0.f;
@@ -833,11 +828,7 @@ __global__ __launch_bounds__(C) void dwconv7_lns_kernel(DwLnArgs p, int spr, int
     const int tid = threadIdx.x, lane = tid & 63;
     const int g = __builtin_amdgcn_readfirstlane(tid / CG);            // row group (wave-uniform: CG is a multiple of 64)
     const int cg = tid - g * CG, wv = cg >> 6;
-    int blk;
-    {
-        const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
     if (blk >= nstrips) return;                                        // (whole block)
     const int HP = (p.H + 1) >> 1;
     const int yg = blk / spr, x0 = (blk - yg * spr) * PX;
