@@ -485,6 +485,42 @@ int uni_block_tail_fwd_f64(const void* y, int y_dtype, const double* residual, i
 int uni_block_tail_bwd_f64(const void* y, int y_dtype, const double* grad_out, int nchw, const double* gamma, const double* scale, int B, int H,
                            int W, int C, void* grad_y, double* grad_gamma, void* workspace, size_t workspace_bytes, uni_stream_t stream);
 
+/* The channels-first LayerNorm between the ConvNeXt stages for TRAINING (unicorn/models/backbone/convnext.py:160-184, the
+ * data_format == "channels_first" branch: u = x.mean(1), s = (x - u).pow(2).mean(1), x = (x - u) / sqrt(s + eps), weight[:, None, None] * x +
+ * bias[:, None, None]), forward and backward for a whole batch: one launch forward, at most two backward, no host synchronisation, no
+ * read-back, no allocation, no atomics.  Operator only: the model-level engine stays inference only.
+ *   x, y, grad_y, grad_x  (B, C, H, W) maps, all four in ONE memory layout: nchw == 0: dense [B][H][W][C] (channels-last memory), nchw != 0:
+ *                         dense [B][C][H][W].  Both are read and written in place.  x_dtype: 0 = the type of the form (fp32, fp64 in the _f64
+ *                         form), 1 = fp16, 2 = bf16 (fp32 form only) is the type of x and grad_x; y and grad_y have the type of the form.
+ *                         Conversion in registers, all arithmetic fp32 (fp64).
+ *   weight, bias, grad_weight, grad_bias  [C]
+ *   stats                 [B H W][2] = mean and 1 / sqrt(var + eps) of every pixel, written by the forward, read by the backward
+ *   uni_lncf_train_fwd  y = weight * (x - mean) * rstd + bias; the variance is the mean of (x - mean)^2: a second pass over registers, and where
+ *                       a block's waves share the channels of a pixel (nchw) the pairwise mean / M2 update of such two-pass parts.  Writes y
+ *                       and stats COMPLETELY.
+ *   uni_lncf_train_bwd  xhat = (x - mean) * rstd, t = grad_y * weight: grad_x = rstd * (t - mean_c t - xhat * mean_c (t * xhat)),
+ *                       grad_weight[c] = sum over n, h, w of grad_y * xhat, grad_bias[c] = sum of grad_y, each written COMPLETELY.  grad_x and
+ *                       the pair grad_weight / grad_bias may be NULL: that part is skipped (the reduce launch too when the pair is NULL; the
+ *                       workspace may then be NULL and is not touched), what is computed has the same bits as in the full call.
+ * One writer per element, fixed summation orders (the lanes of a block in a fixed tree, blocks in ascending order in double): two calls give
+ * the same bits.
+ * Limits: B, H, W >= 1, C % 4 == 0, 4 <= C <= 2048, B H W < 2^31 (element offsets are 64-bit), pointers 16-byte aligned (H W need not be a
+ * multiple of anything: the rows of a channel plane are read element-wise); other shapes are refused with an error string and
+ * uni_lncf_train_workspace_bytes returns 0 for them.
+ * workspace (backward with grad_weight / grad_bias only): 16-byte aligned device scratch of >= uni_lncf_train_workspace_bytes(B, H, W, C) bytes
+ * (fp32; the _f64 form needs twice that) = 4 * 1024 * 2 C: at most 1024 blocks write one row of [2][C] partial sums each.  Nothing is kept in
+ * it between calls. */
+size_t uni_lncf_train_workspace_bytes(int B, int H, int W, int C);
+int uni_lncf_train_fwd(const void* x, int x_dtype, int nchw, const float* weight, const float* bias, double eps, int B, int H, int W, int C,
+                       float* y, float* stats, uni_stream_t stream);
+int uni_lncf_train_bwd(const void* x, int x_dtype, int nchw, const float* weight, const float* stats, const float* grad_y, int B, int H, int W,
+                       int C, void* grad_x, float* grad_weight, float* grad_bias, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_lncf_train_fwd_f64(const void* x, int x_dtype, int nchw, const double* weight, const double* bias, double eps, int B, int H, int W,
+                           int C, double* y, double* stats, uni_stream_t stream);
+int uni_lncf_train_bwd_f64(const void* x, int x_dtype, int nchw, const double* weight, const double* stats, const double* grad_y, int B, int H,
+                           int W, int C, void* grad_x, double* grad_weight, double* grad_bias, void* workspace, size_t workspace_bytes,
+                           uni_stream_t stream);
+
 /* What stands around the label propagation in the SOT / VOS TRAINING losses (unicorn/models/unicorn.py:315-337 compute_loss_sot, :339-390
  * compute_loss_vos) for a whole BATCH, without a host synchronisation, a read-back or an allocation; the number of launches does not
  * depend on the data.  The propagation itself is uni_corr_softmax_pv_lse / _bwd on the label rows these entries produce.

@@ -532,6 +532,22 @@ size_t uni_block_tail_workspace_bytes(int B, int H, int W, int C) { return block
         API(launch_block_tail_bwd<T>(a, grad_y, grad_gamma, workspace, workspace_bytes, S(stream)));                                               \
     }
 UNI_PAIR(DEF_BLOCK_TAIL)
+size_t uni_lncf_train_workspace_bytes(int B, int H, int W, int C) { return lncf_train_workspace_bytes(B, H, W, C); }
+#define DEF_LNCF_TRAIN(SFX, T)                                                                                                                     \
+    int uni_lncf_train_fwd##SFX(const void* x, int x_dtype, int nchw, const T* weight, const T* bias, double eps, int B, int H, int W, int C,      \
+                                T* y, T* stats, uni_stream_t stream) {                                                                             \
+        UNI_REQUIRE(x && weight && bias && y && stats, "lncf_train_fwd" #SFX ": NULL argument");                                                   \
+        const LncfArgs<T> a{x, x_dtype, nchw, weight, bias, eps, B, H, W, C};                                                                      \
+        API(launch_lncf_train_fwd<T>(a, y, stats, S(stream)));                                                                                     \
+    }                                                                                                                                              \
+    int uni_lncf_train_bwd##SFX(const void* x, int x_dtype, int nchw, const T* weight, const T* stats, const T* grad_y, int B, int H, int W,       \
+                                int C, void* grad_x, T* grad_weight, T* grad_bias, void* workspace, size_t workspace_bytes,                        \
+                                uni_stream_t stream) {                                                                                             \
+        UNI_REQUIRE(x && weight && stats && grad_y, "lncf_train_bwd" #SFX ": NULL argument");                                                      \
+        const LncfArgs<T> a{x, x_dtype, nchw, weight, nullptr, 0.0, B, H, W, C};                                                                   \
+        API(launch_lncf_train_bwd<T>(a, stats, grad_y, grad_x, grad_weight, grad_bias, workspace, workspace_bytes, S(stream)));                    \
+    }
+UNI_PAIR(DEF_LNCF_TRAIN)
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

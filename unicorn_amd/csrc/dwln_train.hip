@@ -6,7 +6,8 @@
 //   dwln_conv_kernel<MODE 2>  backward pass B (data): dx = conv(du) with the flipped window
 //   dwln_dw_kernel            backward pass B (weights): one channel per lane, the 7x7 window of x and the 49 + 1 sums in registers while the
 //                             wave walks a strip of one row; the four waves of a block are added through LDS -> per-block partials
-//   dwln_reduce_kernel        partials -> dw [49][C], db, dgamma, dbeta: rows in ascending order, double accumulation
+//   dwln_reduce_kernel        partials -> dw [49][C], db, dgamma, dbeta: rows in ascending order, double accumulation (dwln_reduce.h, shared
+//                             with lncf_train.hip)
 //
 // The three conv modes share one mapping: a lane owns 4 consecutive channels (16-byte loads, coalesced over C) of a strip of PXT pixels of one
 // row; the C / 4 lanes of a strip are whole waves (`slot`), so a sum over C is a wave butterfly plus the slot's waves through LDS in ascending order.
@@ -14,6 +15,7 @@
 // image only, so nothing of a neighbouring image enters a halo.  Every output element has one writer, no atomics: bitwise reproducible.
 // Element offsets are 64-bit; pixel and strip indices are int (B H W < 2^31 is required).
 #include "kernels.h"
+#include "dwln_reduce.h"
 
 template <typename T>
 using dv4 = T __attribute__((ext_vector_type(4)));
@@ -262,35 +264,6 @@ __global__ __launch_bounds__(256) void dwln_dw_kernel(const T* __restrict__ x, c
     }
     if (cok)
         for (int k = wave; k < 50; k += 4) part[((size_t)blockIdx.x * 50 + k) * C + c] = sm[k * 64 + lane];
-}
-
-// out[n] = sum over the R rows of part [R][N], rows in ascending order inside each of the four waves, then the waves in ascending order; double sums
-struct DwlnRJob {
-    const void* part;
-    void *out1, *out2;                          // column n -> out1[n] for n < n1, else out2[n - n1]
-    int R, N, n1, blocks;
-};
-template <typename T>
-__global__ __launch_bounds__(256) void dwln_reduce_kernel(DwlnRJob j0, DwlnRJob j1) {
-    __shared__ double sm[4][64];
-    const bool first = (int)blockIdx.x < j0.blocks;
-    const int b = first ? blockIdx.x : blockIdx.x - j0.blocks;
-    const T* part = reinterpret_cast<const T*>(first ? j0.part : j1.part);
-    T* out1 = reinterpret_cast<T*>(first ? j0.out1 : j1.out1);
-    T* out2 = reinterpret_cast<T*>(first ? j0.out2 : j1.out2);
-    const int R = first ? j0.R : j1.R, N = first ? j0.N : j1.N, n1 = first ? j0.n1 : j1.n1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = b * 64 + lane;
-    double a = 0;
-    if (n < N)
-        for (int r = wave; r < R; r += 4) a += (double)part[(size_t)r * N + n];
-    sm[wave][lane] = a;
-    __syncthreads();
-    if (wave == 0 && n < N) {
-        a = ((sm[0][lane] + sm[1][lane]) + sm[2][lane]) + sm[3][lane];
-        if (n < n1) out1[n] = (T)a;
-        else out2[n - n1] = (T)a;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host

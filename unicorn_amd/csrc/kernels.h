@@ -366,6 +366,26 @@ template <typename T>
 int launch_block_tail_fwd(const BtArgs<T>& a, T* out, hipStream_t s);
 template <typename T>
 int launch_block_tail_bwd(const BtArgs<T>& a, void* gy, T* ggamma, void* ws, size_t ws_bytes, hipStream_t s);
+// lncf_train.hip: the channels-first LayerNorm between the ConvNeXt stages for TRAINING (convnext.py:160-184): y = weight[c] * (x - u) * rstd +
+// bias[c] over the channels of every pixel, forward + backward, fp32 (x / grad_x fp32, fp16 or bf16) and fp64, one launch forward and at most
+// two backward, no host read-back, no atomics.  x, y, gy, gx are (B, C, H, W) maps in channels-last memory [B][H][W][C] or, with nchw != 0,
+// NCHW-contiguous [B][C][H][W], all four in the same layout; y and gy have the type T, gx the type of x; stats [B H W][2] (mean, rstd) is
+// written by the forward for the backward.  gx and the pair gw / gb may be NULL (not computed; the workspace is then not touched).
+// C % 4 == 0, 4 <= C <= 2048, B H W < 2^31.  Workspace (backward with gw / gb only): lncf_train_workspace_bytes for fp32, twice that for fp64.
+size_t lncf_train_workspace_bytes(int B, int H, int W, int C);
+template <typename T>
+struct LncfArgs {
+    const void* x;
+    int x_dtype;                                // 0: the type T, 1 fp16, 2 bf16 (fp32 form only)
+    int nchw;
+    const T *w, *bias;                          // bias: forward only
+    double eps;                                 // forward only (the backward reads rstd)
+    int B, H, W, C;
+};
+template <typename T>
+int launch_lncf_train_fwd(const LncfArgs<T>& a, T* y, T* stats, hipStream_t s);
+template <typename T>
+int launch_lncf_train_bwd(const LncfArgs<T>& a, const T* stats, const T* gy, void* gx, T* gw, T* gb, void* ws, size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

@@ -1,0 +1,527 @@
+// The channels-first LayerNorm of the ConvNeXt backbone for TRAINING (convnext.py:160-184, data_format == "channels_first"): forward with per-pixel
+// statistics and a deterministic backward, fp32 (x / grad_x fp32, fp16 or bf16, converted in registers; all arithmetic fp32) and fp64.
+//
+//   forward   u = mean_c x, rstd = 1 / sqrt(mean_c (x - u)^2 + eps), y[n][c][h][w] = weight[c] * (x - u) * rstd + bias[c], stats [B H W][2] = u, rstd
+//   backward  xhat = (x - u) * rstd, t = grad_y * weight, grad_x = rstd * (t - mean_c t - xhat * mean_c (t * xhat)),
+//             part[block][2][C] = the block's sums of grad_y * xhat and of grad_y
+//
+//   lncf_cl_kernel<V, NV, MODE>    channels-last memory [B][H][W][C]: a pixel belongs to G lanes of ONE wave (G a power of two, 1 .. 64); a lane owns
+//                                  NV vectors of V consecutive channels (vector k of lane g = channels (k G + g) V ...; V = 4, or 8 for half x with
+//                                  C % 8 == 0: 16-byte loads of x either way), so the row of a pixel is in registers, x is read once, the variance
+//                                  is the second pass over registers and a sum over C is a butterfly over the G lanes: no LDS, no barrier.  A
+//                                  block of four waves takes 256 / G pixels at once (C = 96: G = 8, NV = 3, 32 pixels).
+//   lncf_nchw_kernel<CH, KEEP, MODE>  NCHW-contiguous memory: a tile = 64 consecutive pixels of one image (lane = pixel: a wave reads 64 consecutive
+//                                  elements of a channel plane, whatever H W is: no alignment is assumed and a tile ends with its image), the eight
+//                                  waves of a block split the channels (wave w owns c = w, w + 8, ...).  KEEP: the slice of <= CH channels stays in
+//                                  registers (C <= 256: x is read once, two-pass variance per slice).  Otherwise (wider C) the slice is walked in chunks
+//                                  of CH channels, two-pass inside a chunk, and x is read a second time for the output.  Chunks and slices are
+//                                  combined with the pairwise mean / M2 update (Chan et al.), the slices through LDS in ascending wave order.
+//   dwln_reduce_kernel             partials [R][2][C] -> grad_weight, grad_bias (dwln_reduce.h)
+//
+// mode 0 = forward, 1 = backward.  Every output element has one writer, no atomics, fixed summation orders: bitwise reproducible.  Element
+// offsets are 64-bit; pixel, group and tile indices fit 32 bits (B H W < 2^31 is required).
+#include "kernels.h"
+#include "dwln_reduce.h"
+#include <type_traits>
+
+constexpr int LNCF_MAX_C = 2048;
+constexpr int LNCF_ROWS = 1024;                 // at most this many blocks (= rows of partials)
+constexpr int LNCF_NW = 8;                      // NCHW path: waves of a block
+
+template <typename T>
+struct LncfK {                                  // kernel arguments (by value)
+    const void* x;
+    const T *w, *bias, *gy, *stats_in;
+    T *y, *stats_out;
+    void* gx;                                   // the element type of x
+    T* part;
+    T eps;
+    int HW, C;
+    long long M;                                // B H W
+};
+
+// V consecutive elements in accesses of 16 bytes, converted to / from the math type
+template <typename E, int V, typename T>
+__device__ __forceinline__ void lncf_load(const E* p, T (&v)[V]) {
+    constexpr int N = 16 / sizeof(E) < V ? 16 / sizeof(E) : V;
+    using vec = E __attribute__((ext_vector_type(N)));
+#pragma unroll
+    for (int k = 0; k < V / N; ++k) {
+        const vec t = *reinterpret_cast<const vec*>(p + k * N);
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[k * N + i] = (T)t[i];
+    }
+}
+template <typename E, int V, typename T>
+__device__ __forceinline__ void lncf_store(E* p, const T (&v)[V]) {
+    constexpr int N = 16 / sizeof(E) < V ? 16 / sizeof(E) : V;
+    using vec = E __attribute__((ext_vector_type(N)));
+#pragma unroll
+    for (int k = 0; k < V / N; ++k) {
+        vec t;
+#pragma unroll
+        for (int i = 0; i < N; ++i) t[i] = (E)v[k * N + i];
+        *reinterpret_cast<vec*>(p + k * N) = t;
+    }
+}
+
+// sum over the G lanes of a pixel (G a power of two, the lanes are consecutive): xor butterfly, every lane gets the total
+template <typename T>
+__device__ __forceinline__ T lncf_group_sum(T v, int G) {
+    for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+extern __shared__ double lncf_dyn_lds[];
+
+template <typename T, typename XT, int V, int NV, int MODE>
+__global__ __launch_bounds__(256) void lncf_cl_kernel(LncfK<T> p, int G, int lgG, unsigned ngroups) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = tid & (G - 1), slot = tid >> lgG, PPB = 256 >> lgG;
+    const int C = p.C, nvec = C / V;
+    const T cnt = T(C);
+    bool vok[NV];
+    int c[NV];
+    T wv[NV][V], bv[NV][V], dg[NV][V], db[NV][V];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int vec = k * G + g;
+        vok[k] = vec < nvec;
+        c[k] = vec * V;
+#pragma unroll
+        for (int j = 0; j < V; ++j) wv[k][j] = bv[k][j] = dg[k][j] = db[k][j] = T(0);
+        if (vok[k]) {
+            lncf_load<T, V>(p.w + c[k], wv[k]);
+            if (MODE == 0) lncf_load<T, V>(p.bias + c[k], bv[k]);
+        }
+    }
+    for (unsigned grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+        const long long pix = (long long)grp * PPB + slot;
+        const bool live = pix < p.M;            // the same in the G lanes of a pixel
+        const size_t e = (size_t)pix * C;
+        T xv[NV][V];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) xv[k][j] = T(0);
+            if (live && vok[k]) lncf_load<XT, V>(reinterpret_cast<const XT*>(p.x) + e + c[k], xv[k]);
+        }
+        if (MODE == 0) {
+            T s = 0;
+#pragma unroll
+            for (int k = 0; k < NV; ++k)
+#pragma unroll
+                for (int j = 0; j < V; ++j) s += xv[k][j];
+            const T mean = lncf_group_sum(s, G) / cnt;
+            T q = 0;
+#pragma unroll
+            for (int k = 0; k < NV; ++k)
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    xv[k][j] = vok[k] ? xv[k][j] - mean : T(0);
+                    q += xv[k][j] * xv[k][j];
+                }
+            const T rstd = T(1) / sqrt(lncf_group_sum(q, G) / cnt + p.eps);
+            if (live) {
+#pragma unroll
+                for (int k = 0; k < NV; ++k) {
+                    if (!vok[k]) continue;
+                    T r[V];
+#pragma unroll
+                    for (int j = 0; j < V; ++j) r[j] = (xv[k][j] * rstd) * wv[k][j] + bv[k][j];
+                    lncf_store<T, V>(p.y + e + c[k], r);
+                }
+                if (g == 0) {
+                    p.stats_out[(size_t)pix * 2] = mean;
+                    p.stats_out[(size_t)pix * 2 + 1] = rstd;
+                }
+            }
+        } else {
+            T gv[NV][V];
+            T mean = 0, rstd = 0;
+            if (live) {
+                mean = p.stats_in[(size_t)pix * 2];
+                rstd = p.stats_in[(size_t)pix * 2 + 1];
+            }
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) gv[k][j] = T(0);
+                if (live && vok[k]) lncf_load<T, V>(p.gy + e + c[k], gv[k]);
+            }
+            T s1 = 0, s2 = 0;
+#pragma unroll
+            for (int k = 0; k < NV; ++k)
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const T xh = vok[k] ? (xv[k][j] - mean) * rstd : T(0);
+                    const T t = gv[k][j] * wv[k][j];
+                    if (p.part) {
+                        dg[k][j] += gv[k][j] * xh;
+                        db[k][j] += gv[k][j];
+                    }
+                    s1 += t;
+                    s2 += t * xh;
+                    xv[k][j] = xh;
+                    gv[k][j] = t;
+                }
+            if (p.gx) {
+                const T a = lncf_group_sum(s1, G) / cnt, b = lncf_group_sum(s2, G) / cnt;
+                if (live) {
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) {
+                        if (!vok[k]) continue;
+                        T r[V];
+#pragma unroll
+                        for (int j = 0; j < V; ++j) r[j] = rstd * (gv[k][j] - a - xv[k][j] * b);
+                        lncf_store<XT, V>(reinterpret_cast<XT*>(p.gx) + e + c[k], r);
+                    }
+                }
+            }
+        }
+    }
+    if (MODE == 1 && p.part) {                  // the pixel slots of a wave by butterfly, then the four waves in ascending order -> one row [2][C];
+        double* sg = lncf_dyn_lds;              // in double: a lane's own sum has few terms, the sum over the lanes has many
+        for (int w = 0; w < 4; ++w) {
+            if (wave == w) {
+#pragma unroll
+                for (int k = 0; k < NV; ++k) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) {
+                        double a = (double)dg[k][j], b = (double)db[k][j];
+                        for (int o = G; o < 64; o <<= 1) {
+                            a += __shfl_xor(a, o, 64);
+                            b += __shfl_xor(b, o, 64);
+                        }
+                        if (lane < G && vok[k]) {
+                            sg[c[k] + j] = (w ? sg[c[k] + j] : 0.0) + a;
+                            sg[C + c[k] + j] = (w ? sg[C + c[k] + j] : 0.0) + b;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        for (int i = tid; i < 2 * C; i += 256) p.part[(size_t)blockIdx.x * 2 * C + i] = (T)sg[i];
+    }
+}
+
+// channels of wave w of the NCHW path: c = w, w + LNCF_NW, ... < C
+__device__ __forceinline__ int lncf_slice(int C, int w) { return (C - w + LNCF_NW - 1) / LNCF_NW; }
+
+// (na, mean, m2) of a set of na values <- that set and a set of nb > 0 values with mean mb and sum of squared deviations qb
+template <typename T>
+__device__ __forceinline__ void lncf_merge(T& na, T& mean, T& m2, T nb, T mb, T qb) {
+    const T nn = na + nb, d = mb - mean;
+    mean += d * (nb / nn);
+    m2 += qb + d * d * (na * nb / nn);
+    na = nn;
+}
+
+// up to CH values of one lane's channel slice from k0 on: v[j] = element (k0 + j) of the slice (0 beyond nb or outside the image)
+template <typename T, typename E, int CH>
+__device__ __forceinline__ void lncf_chunk_load(const E* base, size_t HW, int wave, int k0, int nb, bool ok, T (&v)[CH]) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        v[j] = T(0);
+        if (j < nb && ok) v[j] = (T)base[(size_t)((k0 + j) * LNCF_NW + wave) * HW];
+    }
+}
+
+template <typename T, typename XT, int CH, bool KEEP, int MODE>
+__global__ __launch_bounds__(512) void lncf_nchw_kernel(LncfK<T> p, unsigned tpi, unsigned ntiles) {
+    __shared__ T sm[2][2][LNCF_NW][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int C = p.C, HW = p.HW;
+    const int ks = lncf_slice(C, wave);         // may be 0 (C < 8)
+    const T cnt = T(C);
+    // backward with partials.  KEEP: a lane sums its pixels of the block's tiles in registers.  Otherwise the 64 pixels of a tile are summed by
+    // butterfly (in double) and the tiles in ascending order in acc [2][C] (LDS, double; channel c is touched by lane 0 of wave c % 8 only).
+    T dgr[KEEP ? CH : 1], dbr[KEEP ? CH : 1];
+#pragma unroll
+    for (int j = 0; j < (KEEP ? CH : 1); ++j) dgr[j] = dbr[j] = T(0);
+    double* acc = lncf_dyn_lds;
+    if (MODE == 1 && !KEEP && p.part) {
+        for (int i = tid; i < 2 * C; i += 512) acc[i] = 0.0;
+        __syncthreads();
+    }
+    int it = 0;
+    for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x, ++it) {
+        const unsigned n = t / tpi;
+        const long long q = (long long)(t - n * tpi) * 64 + lane;
+        const bool ok = q < HW;
+        const size_t img = (size_t)n * C * HW + (size_t)q, pix = (size_t)n * HW + (size_t)q;
+        const XT* xp = reinterpret_cast<const XT*>(p.x) + img;
+        T(&buf)[2][LNCF_NW][64] = sm[it & 1];
+        T xv[CH];
+        if (MODE == 0) {
+            T na = 0, mw = 0, qw = 0;            // the slice of this wave
+            for (int k0 = 0; k0 < ks; k0 += CH) {
+                const int nb = ks - k0 < CH ? ks - k0 : CH;
+                lncf_chunk_load<T, XT, CH>(xp, HW, wave, k0, nb, ok, xv);
+                T s = 0;
+#pragma unroll
+                for (int j = 0; j < CH; ++j) s += xv[j];
+                const T mb = s / T(nb);
+                T qb = 0;
+#pragma unroll
+                for (int j = 0; j < CH; ++j)
+                    if (j < nb) qb += (xv[j] - mb) * (xv[j] - mb);
+                lncf_merge(na, mw, qw, T(nb), mb, qb);
+            }
+            buf[0][wave][lane] = mw;
+            buf[1][wave][lane] = qw;
+            __syncthreads();
+            T nt = 0, mean = 0, m2 = 0;
+#pragma unroll
+            for (int w = 0; w < LNCF_NW; ++w) {
+                const int nw = lncf_slice(C, w);
+                if (nw > 0) lncf_merge(nt, mean, m2, T(nw), buf[0][w][lane], buf[1][w][lane]);
+            }
+            const T rstd = T(1) / sqrt(m2 / cnt + p.eps);
+            T* yp = p.y + img;
+            for (int k0 = 0; k0 < ks; k0 += CH) {
+                const int nb = ks - k0 < CH ? ks - k0 : CH;
+                if (!KEEP) lncf_chunk_load<T, XT, CH>(xp, HW, wave, k0, nb, ok, xv);
+#pragma unroll
+                for (int j = 0; j < CH; ++j) {
+                    if (j < nb) {
+                        const int c = (k0 + j) * LNCF_NW + wave;
+                        const T r = ((xv[j] - mean) * rstd) * p.w[c] + p.bias[c];
+                        if (ok) yp[(size_t)c * HW] = r;
+                    }
+                }
+            }
+            if (wave == 0 && ok) {
+                p.stats_out[pix * 2] = mean;
+                p.stats_out[pix * 2 + 1] = rstd;
+            }
+        } else {
+            const T* gp = p.gy + img;
+            T gv[CH];
+            T mean = 0, rstd = 0;
+            if (ok) {
+                mean = p.stats_in[pix * 2];
+                rstd = p.stats_in[pix * 2 + 1];
+            }
+            T s1 = 0, s2 = 0;
+            for (int k0 = 0; k0 < ks; k0 += CH) {
+                const int nb = ks - k0 < CH ? ks - k0 : CH;
+                lncf_chunk_load<T, XT, CH>(xp, HW, wave, k0, nb, ok, xv);
+                lncf_chunk_load<T, T, CH>(gp, HW, wave, k0, nb, ok, gv);
+#pragma unroll
+                for (int j = 0; j < CH; ++j) {
+                    if (j < nb) {                // uniform in the wave
+                        const int c = (k0 + j) * LNCF_NW + wave;
+                        const T xh = (xv[j] - mean) * rstd;
+                        const T tt = gv[j] * p.w[c];
+                        s1 += tt;
+                        s2 += tt * xh;
+                        if (p.part) {
+                            if constexpr (KEEP) {
+                                dgr[j] += gv[j] * xh;
+                                dbr[j] += gv[j];
+                            } else {
+                                const double a = wave_sum((double)(gv[j] * xh)), b = wave_sum((double)gv[j]);
+                                if (lane == 0) {
+                                    acc[c] += a;
+                                    acc[C + c] += b;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            if (p.gx) {
+                buf[0][wave][lane] = s1;
+                buf[1][wave][lane] = s2;
+                __syncthreads();
+                T a = 0, b = 0;
+#pragma unroll
+                for (int w = 0; w < LNCF_NW; ++w) {
+                    a += buf[0][w][lane];
+                    b += buf[1][w][lane];
+                }
+                a /= cnt;
+                b /= cnt;
+                XT* op = reinterpret_cast<XT*>(p.gx) + img;
+                for (int k0 = 0; k0 < ks; k0 += CH) {
+                    const int nb = ks - k0 < CH ? ks - k0 : CH;
+                    if (!KEEP) {
+                        lncf_chunk_load<T, XT, CH>(xp, HW, wave, k0, nb, ok, xv);
+                        lncf_chunk_load<T, T, CH>(gp, HW, wave, k0, nb, ok, gv);
+                    }
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) {
+                        if (j < nb) {
+                            const int c = (k0 + j) * LNCF_NW + wave;
+                            const T xh = (xv[j] - mean) * rstd;
+                            const T r = rstd * (gv[j] * p.w[c] - a - xh * b);
+                            if (ok) op[(size_t)c * HW] = (XT)r;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (MODE == 1 && p.part) {                  // one row [2][C]
+        T* row = p.part + (size_t)blockIdx.x * 2 * C;
+        if constexpr (KEEP) {                   // the 64 lanes of the owning wave by butterfly, in double
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+                if (j < ks) {
+                    const double a = wave_sum((double)dgr[j]), b = wave_sum((double)dbr[j]);
+                    if (lane == 0) {
+                        row[j * LNCF_NW + wave] = (T)a;
+                        row[C + j * LNCF_NW + wave] = (T)b;
+                    }
+                }
+            }
+        } else {
+            __syncthreads();
+            for (int i = tid; i < 2 * C; i += 512) row[i] = (T)acc[i];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host
+size_t lncf_train_workspace_bytes(int B, int H, int W, int C) {
+    if (B < 1 || H < 1 || W < 1 || C < 4 || C % 4 || C > LNCF_MAX_C || (long long)B * H * W >= (1ll << 31)) return 0;
+    return (size_t)4 * LNCF_ROWS * 2 * C;
+}
+
+static bool lncf_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static const char* lncf_xname(int x_dtype, bool f64) { return f64 ? "f64" : x_dtype == 1 ? "f16" : x_dtype == 2 ? "bf16" : "f32"; }
+
+// channels-last: NV vectors per lane and G = 2^lg lanes per pixel with G NV >= nvec and the fewest idle vector slots (the smaller NV on a tie)
+static void lncf_cl_plan(int nvec, int* nv, int* lg) {
+    static const int nvs[] = {1, 2, 3, 4, 6, 8};
+    int best = 1 << 30;
+    for (int k : nvs) {
+        int l = 0;
+        while ((k << l) < nvec) ++l;
+        if (l <= 6 && (k << l) < best) {
+            best = k << l;
+            *nv = k;
+            *lg = l;
+        }
+    }
+}
+
+// launches mode MODE with the element type XT of x; *rows = the rows of partials it writes
+template <typename T, typename XT, int MODE>
+static void lncf_launch(const LncfArgs<T>& a, const LncfK<T>& k, int* rows, hipStream_t s) {
+    const char* what = MODE ? "bwd" : "fwd";
+    const char* xn = lncf_xname(a.x_dtype, sizeof(T) == 8);
+    const size_t lds = (MODE == 1 && k.part) ? (size_t)2 * a.C * sizeof(double) : 0;       // partial sums across lanes are formed in double
+    const int gx = k.gx != nullptr, gwb = k.part != nullptr;
+    if (a.nchw) {
+        const unsigned tpi = (unsigned)cdiv(k.HW, 64), ntiles = (unsigned)a.B * tpi;              // <= B H W
+        *rows = ntiles < (unsigned)LNCF_ROWS ? (int)ntiles : LNCF_ROWS;
+        if (a.C <= 16 * LNCF_NW) {
+            uni_variant_note("lncf_train %s_nchw<%s,regs=16> gx=%d gwb=%d", what, xn, gx, gwb);
+            hipLaunchKernelGGL((lncf_nchw_kernel<T, XT, 16, true, MODE>), dim3(*rows), dim3(64 * LNCF_NW), 0, s, k, tpi, ntiles);
+        } else if (sizeof(T) == 4 && a.C <= 32 * LNCF_NW) {      // fp64 (checks only): 32 x, grad_y and two sums per lane do not fit in registers
+            if constexpr (sizeof(T) == 4) {
+                uni_variant_note("lncf_train %s_nchw<%s,regs=32> gx=%d gwb=%d", what, xn, gx, gwb);
+                hipLaunchKernelGGL((lncf_nchw_kernel<T, XT, 32, true, MODE>), dim3(*rows), dim3(64 * LNCF_NW), 0, s, k, tpi, ntiles);
+            }
+        } else {
+            uni_variant_note("lncf_train %s_nchw<%s,stream=8> gx=%d gwb=%d", what, xn, gx, gwb);
+            hipLaunchKernelGGL((lncf_nchw_kernel<T, XT, 8, false, MODE>), dim3(*rows), dim3(64 * LNCF_NW), lds, s, k, tpi, ntiles);
+        }
+        return;
+    }
+    auto go = [&](auto vtag) {
+        constexpr int V = decltype(vtag)::value;
+        int nv = 1, lg = 0;
+        lncf_cl_plan(a.C / V, &nv, &lg);
+        const int ppb = 256 >> lg;
+        const unsigned ngroups = (unsigned)((k.M + ppb - 1) / ppb);
+        *rows = ngroups < (unsigned)LNCF_ROWS ? (int)ngroups : LNCF_ROWS;
+        uni_variant_note("lncf_train %s_cl<%s,V=%d,NV=%d> G=%d gx=%d gwb=%d", what, xn, V, nv, 1 << lg, gx, gwb);
+        auto run = [&](auto ntag) {
+            constexpr int NV = decltype(ntag)::value;
+            hipLaunchKernelGGL((lncf_cl_kernel<T, XT, V, NV, MODE>), dim3(*rows), dim3(256), lds, s, k, 1 << lg, lg, ngroups);
+        };
+        switch (nv) {
+            case 1: run(std::integral_constant<int, 1>()); break;
+            case 2: run(std::integral_constant<int, 2>()); break;
+            case 3: run(std::integral_constant<int, 3>()); break;
+            case 4: run(std::integral_constant<int, 4>()); break;
+            default:                            // 6 or 8: more than 256 vectors, so V = 4
+                if constexpr (V == 4) {
+                    if (nv == 6) run(std::integral_constant<int, 6>());
+                    else run(std::integral_constant<int, 8>());
+                }
+        }
+    };
+    if constexpr (sizeof(XT) == 2) {
+        if (a.C % 8 == 0) return go(std::integral_constant<int, 8>());
+    }
+    go(std::integral_constant<int, 4>());
+}
+
+template <typename T, int MODE>
+static int lncf_dispatch(const char* what, const LncfArgs<T>& a, const LncfK<T>& k, int* rows, hipStream_t s) {
+    if constexpr (sizeof(T) == 8) {
+        UNI_REQUIRE(a.x_dtype == 0, "%s: x_dtype %d: the fp64 form takes fp64 x (0) only", what, a.x_dtype);
+        lncf_launch<T, double, MODE>(a, k, rows, s);
+    } else {
+        UNI_REQUIRE(a.x_dtype >= 0 && a.x_dtype <= 2, "%s: x_dtype %d is not 0 (fp32), 1 (fp16) or 2 (bf16)", what, a.x_dtype);
+        if (a.x_dtype == 0) lncf_launch<T, float, MODE>(a, k, rows, s);
+        else if (a.x_dtype == 1) lncf_launch<T, f16, MODE>(a, k, rows, s);
+        else lncf_launch<T, bf16, MODE>(a, k, rows, s);
+    }
+    return 0;
+}
+
+template <typename T>
+static int lncf_check(const char* what, const LncfArgs<T>& a) {
+    UNI_REQUIRE(lncf_train_workspace_bytes(a.B, a.H, a.W, a.C) != 0,
+                "%s: shape B=%d H=%d W=%d C=%d is outside B, H, W >= 1, C %% 4 == 0, 4 <= C <= %d, B H W < 2^31", what, a.B, a.H, a.W, a.C, LNCF_MAX_C);
+    UNI_REQUIRE(lncf_aligned(a.x) && lncf_aligned(a.w) && lncf_aligned(a.bias), "%s: a pointer is not 16-byte aligned", what);
+    return 0;
+}
+
+template <typename T>
+int launch_lncf_train_fwd(const LncfArgs<T>& a, T* y, T* stats, hipStream_t s) {
+    if (int rc = lncf_check("lncf_train_fwd", a)) return rc;
+    UNI_REQUIRE(lncf_aligned(y) && lncf_aligned(stats), "lncf_train_fwd: a pointer is not 16-byte aligned");
+    UNI_REQUIRE(a.eps > 0, "lncf_train_fwd: eps %g is not positive", a.eps);
+    const LncfK<T> k{a.x, a.w, a.bias, nullptr, nullptr, y, stats, nullptr, nullptr, (T)a.eps, a.H * a.W, a.C, (long long)a.B * a.H * a.W};
+    int rows;
+    if (int rc = lncf_dispatch<T, 0>("lncf_train_fwd", a, k, &rows, s)) return rc;
+    UNI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int launch_lncf_train_bwd(const LncfArgs<T>& a, const T* stats, const T* gy, void* gx, T* gw, T* gb, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (int rc = lncf_check("lncf_train_bwd", a)) return rc;
+    UNI_REQUIRE((gw != nullptr) == (gb != nullptr), "lncf_train_bwd: grad_weight and grad_bias come as a pair");
+    UNI_REQUIRE(lncf_aligned(stats) && lncf_aligned(gy) && lncf_aligned(gx) && lncf_aligned(gw) && lncf_aligned(gb) && lncf_aligned(ws),
+                "lncf_train_bwd: a pointer is not 16-byte aligned");
+    if (!gx && !gw) return 0;
+    if (gw) {
+        const size_t need = lncf_train_workspace_bytes(a.B, a.H, a.W, a.C) * (sizeof(T) / 4);
+        UNI_REQUIRE(ws && ws_bytes >= need, "lncf_train_bwd: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, need);
+    }
+    T* part = gw ? reinterpret_cast<T*>(ws) : nullptr;
+    const LncfK<T> k{a.x, a.w, nullptr, gy, stats, nullptr, nullptr, gx, part, T(0), a.H * a.W, a.C, (long long)a.B * a.H * a.W};
+    int rows;
+    if (int rc = lncf_dispatch<T, 1>("lncf_train_bwd", a, k, &rows, s)) return rc;
+    if (gw) {
+        const DwlnRJob none{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+        const DwlnRJob job{part, gw, gb, rows, 2 * a.C, a.C, cdiv(2 * a.C, 64)};
+        uni_variant_note("lncf_train reduce<%s>", sizeof(T) == 8 ? "f64" : "f32");
+        hipLaunchKernelGGL((dwln_reduce_kernel<T>), dim3(job.blocks), dim3(256), 0, s, none, job);
+    }
+    UNI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+template int launch_lncf_train_fwd<float>(const LncfArgs<float>&, float*, float*, hipStream_t);
+template int launch_lncf_train_fwd<double>(const LncfArgs<double>&, double*, double*, hipStream_t);
+template int launch_lncf_train_bwd<float>(const LncfArgs<float>&, const float*, const float*, void*, float*, float*, void*, size_t, hipStream_t);
+template int launch_lncf_train_bwd<double>(const LncfArgs<double>&, const double*, const double*, void*, double*, double*, void*, size_t, hipStream_t);

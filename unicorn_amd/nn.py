@@ -18,7 +18,11 @@ fuse_block_tail(model) routes the close of the same block (convnext.py:49-53)
 through unicorn_amd.ops.block_tail.  `self.gamma * x` cannot be reached through a submodule, so the BLOCK gets the instance-level `forward`: it
 calls the block's own submodules in the reference's order (dwconv -> permute -> norm -> pwconv1 -> act -> pwconv2; fuse_dwconv_ln and module
 hooks keep working) and then the operator, whose output is channels-last memory: what the next block's dwconv7_ln reads in place.  The
-drop-path mask is drawn as timm's DropPath draws it, so a seeded run drops the same samples fused and unfused.  fuse_convnext applies both."""
+drop-path mask is drawn as timm's DropPath draws it, so a seeded run drops the same samples fused and unfused.  fuse_convnext applies both.
+
+fuse_layernorm_cf(model) routes the channels-first LayerNorm between the stages (convnext.py:160-184; after the stem, before each downsample
+convolution, on the stage outputs) through unicorn_amd.ops.layernorm_cf, which reads channels-last memory (the output of block_tail) and
+NCHW memory (the output of the stem convolution) in place and answers in the same layout.  fuse_backbone applies all three."""
 import torch
 
 from . import ops
@@ -178,3 +182,60 @@ def unfuse_block_tail(model):
 def fuse_convnext(model):
     """fuse_dwconv_ln + fuse_block_tail -> (blocks whose opening is fused, blocks whose close is fused)"""
     return fuse_dwconv_ln(model), fuse_block_tail(model)
+
+
+class _FusedLayerNormCF:
+    """instance-level `forward` of a channels-first LayerNorm"""
+    __slots__ = ("norm",)
+
+    def __init__(self, norm):
+        self.norm = norm
+
+    def __call__(self, x):
+        m = self.norm
+        if not (m.training and isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_cuda):
+            return type(m).forward(m, x)
+        return ops.layernorm_cf(x, m.weight, m.bias, m.eps)
+
+
+def _lncf_fusable(m):
+    if not isinstance(m, torch.nn.Module) or getattr(m, "data_format", None) != "channels_first":
+        return False
+    w, b = getattr(m, "weight", None), getattr(m, "bias", None)
+    if not isinstance(w, torch.Tensor) or not isinstance(b, torch.Tensor) or w.dim() != 1 or not isinstance(getattr(m, "eps", None), float):
+        return False
+    Cc = w.shape[0]
+    if tuple(b.shape) != (Cc,) or tuple(getattr(m, "normalized_shape", ())) != (Cc,):
+        return False
+    return Cc % 4 == 0 and 4 <= Cc <= ops.DWLN_MAX_C
+
+
+def fuse_layernorm_cf(model):
+    """Route every channels-first LayerNorm of `model` (convnext.py:160-184: data_format == "channels_first", weight and bias (C,), a float eps,
+    normalized_shape == (C,); C % 4 == 0, 4 <= C <= 2048) through unicorn_amd.ops.layernorm_cf: the module gets an instance-level `forward`
+    that is active in training mode for 4-D device tensors and calls the module's own forward otherwise.  Channels-last norms (the blocks'
+    `norm`) and nn.LayerNorm are not touched.  Module tree, parameter names and state_dict() stay as they were.  Returns the number of
+    modules fused (modules that are fused already are counted)."""
+    n = 0
+    for m in model.modules():
+        if not _lncf_fusable(m):
+            continue
+        if not isinstance(m.__dict__.get("forward"), _FusedLayerNormCF):
+            m.forward = _FusedLayerNormCF(m)
+        n += 1
+    return n
+
+
+def unfuse_layernorm_cf(model):
+    """Remove what fuse_layernorm_cf set; returns the number of modules restored."""
+    n = 0
+    for m in model.modules():
+        if isinstance(m.__dict__.get("forward"), _FusedLayerNormCF):
+            del m.__dict__["forward"]
+            n += 1
+    return n
+
+
+def fuse_backbone(model):
+    """fuse_convnext + fuse_layernorm_cf -> (blocks whose opening is fused, blocks whose close is fused, channels-first norms fused)"""
+    return fuse_convnext(model) + (fuse_layernorm_cf(model),)

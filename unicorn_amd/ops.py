@@ -1099,6 +1099,107 @@ def block_tail(y, residual, gamma=None, scale=None):
     return BlockTailFunction.apply(y.contiguous(), residual, None if gamma is None else gamma.contiguous(), scale)
 
 
+def _lncf_like(t, nchw, dtype):
+    """an uninitialised tensor of the shape of `t` in the memory layout `nchw` names"""
+    return torch.empty(t.shape, device=t.device, dtype=dtype, memory_format=torch.contiguous_format if nchw else torch.channels_last)
+
+
+class LayerNormCFFunction(torch.autograd.Function):
+    """The channels-first LayerNorm of the ConvNeXt backbone (convnext.py:160-184): apply(x (N,C,H,W), weight (C,), bias (C,), eps) -> y
+    (N,C,H,W) in the memory layout of x; x fp32 / fp16 / bf16 with fp32 weight and bias -> y fp32, or all fp64 (ops.layernorm_cf checks).
+    Channels-last and NCHW-contiguous memory of x are read in place, anything else is converted once to channels-last; grad_out is read in place
+    when it has the layout of x.  Saves x, weight and the (N H W, 2) statistics, never y or the normalised map.  x.grad has the dtype and layout
+    of x; only what autograd asks for is computed.  No host synchronisation, one writer per element: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        N, Cc, H, W = x.shape
+        ctx.dims = (N, Cc, H, W)
+        out_dtype = torch.promote_types(x.dtype, weight.dtype)
+        xc, nchw = _bt_layout(x)
+        ctx.nchw = nchw
+        y = _lncf_like(xc, nchw, out_dtype)
+        if N == 0:
+            ctx.save_for_backward(xc, weight)
+            return y
+        stats = torch.empty((N * H * W, 2), device=x.device, dtype=out_dtype)
+        fn, name = _entry("uni_lncf_train_fwd", out_dtype)
+        with torch.cuda.device(x.device):
+            L.check(fn(L.ptr(xc), _BT_Y_DTYPE[xc.dtype], nchw, L.ptr(weight), L.ptr(bias), float(eps), N, H, W, Cc, L.ptr(y), L.ptr(stats),
+                       L.stream_ptr()), name)
+        ctx.save_for_backward(xc, weight, stats)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        N, Cc, H, W = ctx.dims
+        nchw = ctx.nchw
+        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        xc, weight = ctx.saved_tensors[:2]
+        gx = _lncf_like(xc, nchw, xc.dtype) if need_x else None
+        gw = torch.empty_like(weight) if need_p else None
+        gb = torch.empty_like(weight) if need_p else None
+        if N == 0:
+            if need_p:
+                gw.zero_(), gb.zero_()
+        elif need_x or need_p:
+            stats = ctx.saved_tensors[2]
+            g = grad_out.contiguous() if nchw else grad_out.contiguous(memory_format=torch.channels_last)       # no copy in the layout of x
+            fn, name = _entry("uni_lncf_train_bwd", weight.dtype)
+            with torch.cuda.device(xc.device):
+                ws = None
+                if need_p:
+                    ws = torch.empty(L.lib().uni_lncf_train_workspace_bytes(N, H, W, Cc) * _ws_factor(weight.dtype), device=xc.device,
+                                     dtype=torch.uint8)
+                L.check(fn(L.ptr(xc), _BT_Y_DTYPE[xc.dtype], nchw, L.ptr(weight), L.ptr(stats), L.ptr(g), N, H, W, Cc, L.ptr(gx), L.ptr(gw),
+                           L.ptr(gb), L.ptr(ws), ws.numel() if need_p else 0, L.stream_ptr()), name)
+        return gx, gw if ctx.needs_input_grad[1] else None, gb if ctx.needs_input_grad[2] else None, None
+
+
+def layernorm_cf(x, weight, bias, eps=1e-6):
+    """The reference's LayerNorm(C, data_format="channels_first") (convnext.py:160-184) as one operator, equal in value and in all three
+    gradients: y[n, c, h, w] = weight[c] * (x[n, c, h, w] - u) / sqrt(s + eps) + bias[c] with u and s the mean and the biased variance over
+    the C channels of the pixel.
+      x             (N, C, H, W) fp32, fp16 or bf16; read in the dtype it has (no cast under autocast).  Channels-last memory (what
+                    ops.block_tail returns) and NCHW-contiguous memory (what a convolution returns) are read in place, any other strides are
+                    converted once to channels-last
+      weight, bias  (C,) fp32
+    All three fp64 is accepted for checks.  Returns y of the shape of x in the MEMORY LAYOUT of x (of its channels-last copy for other
+    strides), dtype torch.promote_types(x.dtype, weight.dtype): fp32 (fp64), what the eager lines return with or without autocast.
+    Gradients: x.grad in the dtype and layout of x, weight.grad and bias.grad (C,); grad_out is read in place when it has the layout of x,
+    otherwise it is converted once.  Autograd keeps x, weight and two numbers per pixel, neither y nor the normalised map.
+    C % 4 == 0, 4 <= C <= 2048.  N == 0 returns an empty tensor without a library call."""
+    names = ("x", "weight", "bias")
+    ts = (x, weight, bias)
+    for n, t in zip(names, ts):
+        if not isinstance(t, torch.Tensor):
+            raise L.UnicornHipError("layernorm_cf: %s is not a tensor" % n)
+    if x.dim() != 4:
+        raise L.UnicornHipError("layernorm_cf: x of shape %s is not (N, C, H, W)" % (tuple(x.shape),))
+    N, Cc, H, W = x.shape
+    for n, t in zip(names[1:], ts[1:]):
+        if tuple(t.shape) != (Cc,):
+            raise L.UnicornHipError("layernorm_cf: %s of shape %s is not (%d,)" % (n, tuple(t.shape), Cc))
+    if Cc % 4 or not 4 <= Cc <= DWLN_MAX_C:
+        raise L.UnicornHipError("layernorm_cf: C = %d is outside C %% 4 == 0, 4 <= C <= %d" % (Cc, DWLN_MAX_C))
+    if N and (H == 0 or W == 0 or N * H * W >= 1 << 31):
+        raise L.UnicornHipError("layernorm_cf: shape N=%d H=%d W=%d is outside a non-empty map with N H W < 2^31" % (N, H, W))
+    if not float(eps) > 0:
+        raise L.UnicornHipError("layernorm_cf: eps = %r is not positive" % (eps,))
+    if x.dtype == torch.float64:
+        ok = weight.dtype == bias.dtype == torch.float64
+    else:
+        ok = x.dtype in _BT_Y_DTYPE and weight.dtype == bias.dtype == torch.float32
+    if not ok:
+        raise L.UnicornHipError("layernorm_cf: dtypes %s unsupported (x fp32 / fp16 / bf16 with weight, bias fp32; or all fp64)"
+                                % ", ".join(str(t.dtype) for t in ts))
+    _need_cuda(*ts)
+    if len({t.device for t in ts}) != 1:
+        raise L.UnicornHipError("layernorm_cf: tensors on different devices")
+    return LayerNormCFFunction.apply(x, weight.contiguous(), bias.contiguous(), float(eps))
+
+
 def _prop_ws(dev, B, Kc, Q):
     need = L.lib().uni_prop_workspace_bytes(B, Kc, Q)
     if need == 0:
