@@ -20,10 +20,8 @@
 // mode 0 = forward, 1 = backward.  A sample with s[n] == 0 is not read in y (forward) or in x and y (backward): out = residual, grad_y = 0 and
 // nothing is added to grad_gamma, whatever y holds.  One writer per element, no atomics.  Element offsets are 64-bit; pixel indices are int.
 #include "kernels.h"
-#include <type_traits>
+#include "train_ops.h"
 
-constexpr int BT_MAX_C = 2048;
-constexpr int BT_ROWS = 1024;                   // at most this many blocks along the pixels (= rows of grad_gamma partials)
 constexpr int BT_TILE = 64;                     // NCHW path: pixels and channels of a tile
 template <int V>
 struct BtU { static constexpr int value = V == 8 ? 2 : 4; };      // channels-last path: steps of PP pixels whose loads are in flight together
@@ -38,31 +36,6 @@ struct BtK {                                    // kernel arguments (by value)
     int HW, C;
 };
 
-// V consecutive elements in accesses of 16 bytes (8 for four halves), converted to / from the math type
-template <typename E, int V, typename T>
-__device__ __forceinline__ void bt_load(const E* p, T (&v)[V]) {
-    constexpr int N = V * sizeof(E) >= 16 ? 16 / sizeof(E) : V;
-    using vec = E __attribute__((ext_vector_type(N)));
-#pragma unroll
-    for (int k = 0; k < V / N; ++k) {
-        const vec t = *reinterpret_cast<const vec*>(p + k * N);
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[k * N + i] = (T)t[i];
-    }
-}
-template <typename E, int V, typename T>
-__device__ __forceinline__ void bt_store(E* p, const T (&v)[V]) {
-    constexpr int N = V * sizeof(E) >= 16 ? 16 / sizeof(E) : V;
-    using vec = E __attribute__((ext_vector_type(N)));
-#pragma unroll
-    for (int k = 0; k < V / N; ++k) {
-        vec t;
-#pragma unroll
-        for (int i = 0; i < N; ++i) t[i] = (E)v[k * N + i];
-        *reinterpret_cast<vec*>(p + k * N) = t;
-    }
-}
-
 // one lane's V channels of one pixel: element offset e of out / grad_y; xv, yv = the V values of x and y (loaded by the caller where they are needed)
 template <typename T, typename YT, int V, int MODE>
 __device__ __forceinline__ void bt_pixel(const BtK<T>& p, size_t e, const T (&xv)[V], const T (&yv)[V], const T (&gam)[V], T s, bool live,
@@ -71,13 +44,13 @@ __device__ __forceinline__ void bt_pixel(const BtK<T>& p, size_t e, const T (&xv
     if (MODE == 0) {
 #pragma unroll
         for (int j = 0; j < V; ++j) r[j] = live ? xv[j] + (gam[j] * yv[j]) * s : xv[j];
-        bt_store<T, V>(p.out + e, r);
+        vec_store<T, V>(p.out + e, r);
         return;
     }
     if (p.gy) {
 #pragma unroll
         for (int j = 0; j < V; ++j) r[j] = live ? gam[j] * (xv[j] * s) : T(0);
-        bt_store<YT, V>(reinterpret_cast<YT*>(p.gy) + e, r);
+        vec_store<YT, V>(reinterpret_cast<YT*>(p.gy) + e, r);
     }
     if (live && p.part) {
 #pragma unroll
@@ -119,8 +92,8 @@ __global__ __launch_bounds__(512) void bt_cl_kernel(BtK<T> p, int CG, int PP, un
                 const long long q = q0 + u * PP;
                 ok[u] = q < p.HW;
                 e[u] = ((size_t)n * p.HW + (size_t)q) * C + c;
-                if (ok[u] && (MODE == 0 || live)) bt_load<T, V>(p.x + e[u], xv[u]);
-                if (ok[u] && live && want_y) bt_load<YT, V>(reinterpret_cast<const YT*>(p.y) + e[u], yv[u]);
+                if (ok[u] && (MODE == 0 || live)) vec_load<T, V>(p.x + e[u], xv[u]);
+                if (ok[u] && live && want_y) vec_load<YT, V>(reinterpret_cast<const YT*>(p.y) + e[u], yv[u]);
             }
 #pragma unroll
             for (int u = 0; u < BT_U; ++u)
@@ -175,7 +148,7 @@ __global__ __launch_bounds__(256) void bt_nchw_kernel(BtK<T> p, unsigned tpi, un
             const int kq = i * 16 + wave * 4 + pl;
             ok[i] = cok && kq < left;
             e[i] = ((size_t)n * HW + q0 + kq) * C + c;
-            if (ok[i] && live && want_y) bt_load<YT, 4>(reinterpret_cast<const YT*>(p.y) + e[i], yv[i]);
+            if (ok[i] && live && want_y) vec_load<YT, 4>(reinterpret_cast<const YT*>(p.y) + e[i], yv[i]);
         }
         if (MODE == 0 || live) {
             const T* plane = p.x + (size_t)n * C * HW + q0 + lane;
@@ -244,67 +217,49 @@ __global__ __launch_bounds__(1024) void bt_reduce_kernel(const T* __restrict__ p
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-size_t block_tail_workspace_bytes(int B, int H, int W, int C) {
-    if (B < 1 || H < 1 || W < 1 || C < 4 || C % 4 || C > BT_MAX_C || (long long)B * H * W >= (1ll << 31)) return 0;
-    return (size_t)4 * BT_ROWS * C;
-}
-
-static bool bt_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static const char* bt_yname(int y_dtype, bool f64) { return f64 ? "f64" : y_dtype == 1 ? "f16" : y_dtype == 2 ? "bf16" : "f32"; }
+size_t block_tail_workspace_bytes(int B, int H, int W, int C) { return train_shape_ok(B, H, W, C) ? (size_t)4 * TRAIN_ROWS * C : 0; }
 
 // launches mode MODE with the element type YT of y; *rows = the rows of partials it writes
 template <typename T, typename YT, int MODE>
 static void bt_launch(const BtArgs<T>& a, const BtK<T>& k, int* rows, hipStream_t s) {
     const char* what = MODE ? "bwd" : "fwd";
+    const char* yn = train_ename(a.y_dtype, sizeof(T) == 8);
     if (a.nchw) {
         const unsigned tpi = (unsigned)cdiv(k.HW, BT_TILE), ntiles = (unsigned)a.B * tpi;          // <= B H W
-        *rows = ntiles < (unsigned)BT_ROWS ? (int)ntiles : BT_ROWS;
-        uni_variant_note("block_tail %s_nchw<%s> gy=%d gg=%d", what, bt_yname(a.y_dtype, sizeof(T) == 8), k.gy != nullptr, k.part != nullptr);
+        *rows = train_rows(ntiles);
+        uni_variant_note("block_tail %s_nchw<%s> gy=%d gg=%d", what, yn, k.gy != nullptr, k.part != nullptr);
         hipLaunchKernelGGL((bt_nchw_kernel<T, YT, MODE>), dim3(*rows, cdiv(a.C, BT_TILE)), dim3(256), 0, s, k, tpi, ntiles);
         return;
     }
-    auto go = [&](auto vtag) {
+    train_with_vwidth<YT>(a.C, [&](auto vtag) {
         constexpr int V = decltype(vtag)::value;
         const int CG = a.C / V, PP = 512 / CG;                      // CG <= 512
         const int chunk = BtU<V>::value * PP;                       // pixels of a chunk
         const unsigned cpi = (unsigned)(((long long)k.HW + chunk - 1) / chunk);
         const unsigned nchunks = (unsigned)a.B * cpi;               // <= B H W
-        *rows = nchunks < (unsigned)BT_ROWS ? (int)nchunks : BT_ROWS;
-        uni_variant_note("block_tail %s_cl<%s,V=%d> gy=%d gg=%d", what, bt_yname(a.y_dtype, sizeof(T) == 8), V, k.gy != nullptr, k.part != nullptr);
+        *rows = train_rows(nchunks);
+        uni_variant_note("block_tail %s_cl<%s,V=%d> gy=%d gg=%d", what, yn, V, k.gy != nullptr, k.part != nullptr);
         hipLaunchKernelGGL((bt_cl_kernel<T, YT, V, MODE>), dim3(*rows), dim3((PP * CG + 63) / 64 * 64), 0, s, k, CG, PP, cpi, nchunks);
-    };
-    if constexpr (sizeof(YT) == 2) {
-        if (a.C % 8 == 0) return go(std::integral_constant<int, 8>());
-    }
-    go(std::integral_constant<int, 4>());
+    });
 }
 
 template <typename T, int MODE>
 static int bt_dispatch(const BtArgs<T>& a, const BtK<T>& k, int* rows, hipStream_t s) {
-    if constexpr (sizeof(T) == 8) {
-        UNI_REQUIRE(a.y_dtype == 0, "block_tail: y_dtype %d: the fp64 form takes fp64 y (0) only", a.y_dtype);
-        bt_launch<T, double, MODE>(a, k, rows, s);
-    } else {
-        UNI_REQUIRE(a.y_dtype >= 0 && a.y_dtype <= 2, "block_tail: y_dtype %d is not 0 (fp32), 1 (fp16) or 2 (bf16)", a.y_dtype);
-        if (a.y_dtype == 0) bt_launch<T, float, MODE>(a, k, rows, s);
-        else if (a.y_dtype == 1) bt_launch<T, f16, MODE>(a, k, rows, s);
-        else bt_launch<T, bf16, MODE>(a, k, rows, s);
-    }
-    return 0;
+    return train_with_etype<T>("block_tail", "y_dtype", a.y_dtype,
+                               [&](auto e) { bt_launch<T, typename decltype(e)::type, MODE>(a, k, rows, s); });
 }
 
 template <typename T>
 static int bt_check(const char* what, const BtArgs<T>& a) {
-    UNI_REQUIRE(block_tail_workspace_bytes(a.B, a.H, a.W, a.C) != 0,
-                "%s: shape B=%d H=%d W=%d C=%d is outside B, H, W >= 1, C %% 4 == 0, 4 <= C <= %d, B H W < 2^31", what, a.B, a.H, a.W, a.C, BT_MAX_C);
-    UNI_REQUIRE(bt_aligned(a.y) && bt_aligned(a.x), "%s: a pointer is not 16-byte aligned", what);      // gamma, scale: scalar reads
+    if (!train_shape_ok(a.B, a.H, a.W, a.C)) return train_shape_refused(what, a.B, a.H, a.W, a.C);
+    UNI_REQUIRE(aligned16(a.y) && aligned16(a.x), "%s: a pointer is not 16-byte aligned", what);      // gamma, scale: scalar reads
     return 0;
 }
 
 template <typename T>
 int launch_block_tail_fwd(const BtArgs<T>& a, T* out, hipStream_t s) {
     if (int rc = bt_check("block_tail_fwd", a)) return rc;
-    UNI_REQUIRE(bt_aligned(out), "block_tail_fwd: a pointer is not 16-byte aligned");
+    UNI_REQUIRE(aligned16(out), "block_tail_fwd: a pointer is not 16-byte aligned");
     const BtK<T> k{a.y, a.x, a.gamma, a.scale, out, nullptr, nullptr, a.H * a.W, a.C};
     int rows;
     if (int rc = bt_dispatch<T, 0>(a, k, &rows, s)) return rc;
@@ -315,18 +270,15 @@ int launch_block_tail_fwd(const BtArgs<T>& a, T* out, hipStream_t s) {
 template <typename T>
 int launch_block_tail_bwd(const BtArgs<T>& a, void* gy, T* ggamma, void* ws, size_t ws_bytes, hipStream_t s) {
     if (int rc = bt_check("block_tail_bwd", a)) return rc;
-    UNI_REQUIRE(bt_aligned(gy) && bt_aligned(ws), "block_tail_bwd: a pointer is not 16-byte aligned");
+    UNI_REQUIRE(aligned16(gy) && aligned16(ws), "block_tail_bwd: a pointer is not 16-byte aligned");
     if (!gy && !ggamma) return 0;
-    if (ggamma) {
-        const size_t need = block_tail_workspace_bytes(a.B, a.H, a.W, a.C) * (sizeof(T) / 4);
-        UNI_REQUIRE(ws && ws_bytes >= need, "block_tail_bwd: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, need);
-    }
-    T* part = ggamma ? reinterpret_cast<T*>(ws) : nullptr;
+    T* part;
+    if (int rc = train_partials("block_tail_bwd", ggamma != nullptr, ws, ws_bytes, block_tail_workspace_bytes(a.B, a.H, a.W, a.C), &part)) return rc;
     const BtK<T> k{a.y, a.x, a.gamma, a.scale, nullptr, gy, part, a.H * a.W, a.C};
     int rows;
     if (int rc = bt_dispatch<T, 1>(a, k, &rows, s)) return rc;
     if (ggamma) {
-        uni_variant_note("block_tail reduce<%s>", sizeof(T) == 8 ? "f64" : "f32");
+        uni_variant_note("block_tail reduce<%s>", train_ename(0, sizeof(T) == 8));
         hipLaunchKernelGGL((bt_reduce_kernel<T>), dim3(cdiv(a.C, 64)), dim3(1024), 0, s, (const T*)part, ggamma, rows, a.C);
     }
     UNI_CHECK_HIP(hipGetLastError());

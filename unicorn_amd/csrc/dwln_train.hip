@@ -6,7 +6,7 @@
 //   dwln_conv_kernel<MODE 2>  backward pass B (data): dx = conv(du) with the flipped window
 //   dwln_dw_kernel            backward pass B (weights): one channel per lane, the 7x7 window of x and the 49 + 1 sums in registers while the
 //                             wave walks a strip of one row; the four waves of a block are added through LDS -> per-block partials
-//   dwln_reduce_kernel        partials -> dw [49][C], db, dgamma, dbeta: rows in ascending order, double accumulation (dwln_reduce.h, shared
+//   dwln_reduce_kernel        partials -> dw [49][C], db, dgamma, dbeta: rows in ascending order, double accumulation (train_ops.h, shared
 //                             with lncf_train.hip)
 //
 // The three conv modes share one mapping: a lane owns 4 consecutive channels (16-byte loads, coalesced over C) of a strip of PXT pixels of one
@@ -15,7 +15,7 @@
 // image only, so nothing of a neighbouring image enters a halo.  Every output element has one writer, no atomics: bitwise reproducible.
 // Element offsets are 64-bit; pixel and strip indices are int (B H W < 2^31 is required).
 #include "kernels.h"
-#include "dwln_reduce.h"
+#include "train_ops.h"
 
 template <typename T>
 using dv4 = T __attribute__((ext_vector_type(4)));
@@ -29,8 +29,6 @@ __device__ __forceinline__ T dv4_sum(dv4<T> v) {
     return (v[0] + v[1]) + (v[2] + v[3]);
 }
 
-constexpr int DWLN_MAX_C = 2048;
-constexpr int DWLN_A_BLOCKS = 1024;            // pass A: at most this many blocks (= rows of dgamma / dbeta partials)
 constexpr int DWLN_DW_STRIP = 128;             // pass B (weights): longest strip a wave walks
 template <typename T>
 struct DwlnPx { static constexpr int value = sizeof(T) == 4 ? 8 : 2; };      // pixels of a strip per lane
@@ -274,9 +272,8 @@ struct DwlnPlan {
     size_t off_pa, off_pb, elems;               // workspace (elements): du at 0, partials of pass A, of pass B
 };
 static bool dwln_plan(int B, int H, int W, int C, int pxt, DwlnPlan& q) {
-    if (B < 1 || H < 1 || W < 1 || C < 4 || C % 4 || C > DWLN_MAX_C) return false;
+    if (!train_shape_ok(B, H, W, C)) return false;
     const long long M = (long long)B * H * W;
-    if (M >= (1ll << 31)) return false;
     q.CG = C / 4;
     q.CGp = (q.CG + 63) / 64 * 64;
     q.NS = 512 / q.CGp;
@@ -284,7 +281,7 @@ static bool dwln_plan(int B, int H, int W, int C, int pxt, DwlnPlan& q) {
     q.segs = cdiv(W, pxt);
     q.nstrips = B * H * q.segs;
     q.nsb = cdiv(q.nstrips, q.NS);
-    q.RA = q.nsb < DWLN_A_BLOCKS ? q.nsb : DWLN_A_BLOCKS;
+    q.RA = train_rows(q.nsb);                   // pass A: blocks = rows of dgamma / dbeta partials
     q.segs_w = cdiv(W, DWLN_DW_STRIP);
     q.slen = cdiv(W, q.segs_w);
     q.segs_w = cdiv(W, q.slen);
@@ -306,27 +303,23 @@ size_t dwln_train_workspace_bytes(int B, int H, int W, int C) {
 }
 
 template <typename T>
-static const char* dwln_tname() { return sizeof(T) == 4 ? "f32" : "f64"; }
-static bool dwln_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <typename T>
 static int dwln_check(const char* what, const DwlnArgs<T>& a, DwlnPlan& q) {
-    UNI_REQUIRE(dwln_plan(a.B, a.H, a.W, a.C, DwlnPx<T>::value, q),
-                "%s: shape B=%d H=%d W=%d C=%d is outside B, H, W >= 1, C %% 4 == 0, 4 <= C <= %d, B H W < 2^31", what, a.B, a.H, a.W, a.C, DWLN_MAX_C);
-    UNI_REQUIRE(dwln_aligned(a.x) && dwln_aligned(a.w) && dwln_aligned(a.bias) && dwln_aligned(a.gamma), "%s: a pointer is not 16-byte aligned", what);
+    if (!dwln_plan(a.B, a.H, a.W, a.C, DwlnPx<T>::value, q)) return train_shape_refused(what, a.B, a.H, a.W, a.C);
+    UNI_REQUIRE(aligned16(a.x) && aligned16(a.w) && aligned16(a.bias) && aligned16(a.gamma), "%s: a pointer is not 16-byte aligned", what);
     return 0;
 }
 
 template <typename T>
 int launch_dwln_train_fwd(const DwlnArgs<T>& a, T* y, T* stats, hipStream_t s) {
     constexpr int PXT = DwlnPx<T>::value;
+    const char* tn = train_ename(0, sizeof(T) == 8);
     DwlnPlan q;
     if (int rc = dwln_check("dwln_train_fwd", a, q)) return rc;
-    UNI_REQUIRE(dwln_aligned(a.beta) && dwln_aligned(y) && dwln_aligned(stats), "dwln_train_fwd: a pointer is not 16-byte aligned");
+    UNI_REQUIRE(aligned16(a.beta) && aligned16(y) && aligned16(stats), "dwln_train_fwd: a pointer is not 16-byte aligned");
     UNI_REQUIRE(a.eps > 0, "dwln_train_fwd: eps %g is not positive", a.eps);
     DwlnK<T> k{a.x, a.w, a.bias, a.gamma, a.beta, nullptr, nullptr, y, stats, nullptr, (T)a.eps,
                a.H, a.W, a.C, q.CG, q.CGp, q.NS, q.segs, q.nstrips, 0, 0};
-    uni_variant_note("dwln_train fwd<%s,PXT=%d> wps=%d NS=%d", dwln_tname<T>(), PXT, q.CGp / 64, q.NS);
+    uni_variant_note("dwln_train fwd<%s,PXT=%d> wps=%d NS=%d", tn, PXT, q.CGp / 64, q.NS);
     hipLaunchKernelGGL((dwln_conv_kernel<T, PXT, 0>), dim3(q.nsb), dim3(q.threads), 0, s, k);
     UNI_CHECK_HIP(hipGetLastError());
     return 0;
@@ -336,13 +329,14 @@ template <typename T>
 int launch_dwln_train_bwd(const DwlnArgs<T>& a, const T* stats, const T* gy, T* gx, T* gw, T* gb, T* ggamma, T* gbeta, void* ws, size_t ws_bytes,
                           hipStream_t s) {
     constexpr int PXT = DwlnPx<T>::value;
+    const char* tn = train_ename(0, sizeof(T) == 8);
     DwlnPlan q;
     if (int rc = dwln_check("dwln_train_bwd", a, q)) return rc;
     UNI_REQUIRE((gw != nullptr) == (gb != nullptr) && (ggamma != nullptr) == (gbeta != nullptr),
                 "dwln_train_bwd: grad_weight / grad_bias and grad_ln_weight / grad_ln_bias come in pairs");
     const size_t need = dwln_train_workspace_bytes(a.B, a.H, a.W, a.C) * (sizeof(T) / 4);
     UNI_REQUIRE(ws_bytes >= need, "dwln_train_bwd: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    UNI_REQUIRE(dwln_aligned(stats) && dwln_aligned(gy) && dwln_aligned(gx) && dwln_aligned(gw) && dwln_aligned(ws),
+    UNI_REQUIRE(aligned16(stats) && aligned16(gy) && aligned16(gx) && aligned16(gw) && aligned16(ws),
                 "dwln_train_bwd: a pointer is not 16-byte aligned");
     const bool need_du = gx || gw, need_gb = ggamma != nullptr;
     if (!need_du && !need_gb) return 0;
@@ -351,23 +345,23 @@ int launch_dwln_train_bwd(const DwlnArgs<T>& a, const T* stats, const T* gy, T* 
     T* part_b = du + q.off_pb;
     DwlnK<T> k{a.x, a.w, a.bias, a.gamma, nullptr, gy, stats, du, nullptr, part_a, T(0),
                a.H, a.W, a.C, q.CG, q.CGp, q.NS, q.segs, q.nstrips, (int)need_du, (int)need_gb};
-    uni_variant_note("dwln_train bwd_a<%s,PXT=%d> wps=%d NS=%d du=%d gb=%d", dwln_tname<T>(), PXT, q.CGp / 64, q.NS, (int)need_du, (int)need_gb);
+    uni_variant_note("dwln_train bwd_a<%s,PXT=%d> wps=%d NS=%d du=%d gb=%d", tn, PXT, q.CGp / 64, q.NS, (int)need_du, (int)need_gb);
     hipLaunchKernelGGL((dwln_conv_kernel<T, PXT, 1>), dim3(q.RA), dim3(q.threads), need_gb ? 2 * a.C * sizeof(T) : 0, s, k);
     if (gx) {
         DwlnK<T> kx{du, a.w, nullptr, nullptr, nullptr, nullptr, nullptr, gx, nullptr, nullptr, T(0),
                     a.H, a.W, a.C, q.CG, q.CGp, q.NS, q.segs, q.nstrips, 0, 0};
-        uni_variant_note("dwln_train bwd_dx<%s,PXT=%d> wps=%d NS=%d", dwln_tname<T>(), PXT, q.CGp / 64, q.NS);
+        uni_variant_note("dwln_train bwd_dx<%s,PXT=%d> wps=%d NS=%d", tn, PXT, q.CGp / 64, q.NS);
         hipLaunchKernelGGL((dwln_conv_kernel<T, PXT, 2>), dim3(q.nsb), dim3(q.threads), 0, s, kx);
     }
     if (gw) {
-        uni_variant_note("dwln_train bwd_dw<%s> slen=%d", dwln_tname<T>(), q.slen);
+        uni_variant_note("dwln_train bwd_dw<%s> slen=%d", tn, q.slen);
         hipLaunchKernelGGL((dwln_dw_kernel<T>), dim3(q.RB, q.NCT), dim3(256), 0, s, a.x, (const T*)du, part_b, a.H, a.W, a.C, q.slen, q.segs_w,
                            q.nstrips_w);
     }
     DwlnRJob jw{part_b, gw, gb, q.RB, 50 * a.C, 49 * a.C, gw ? cdiv(50 * a.C, 64) : 0};
     DwlnRJob jg{part_a, ggamma, gbeta, q.RA, 2 * a.C, a.C, need_gb ? cdiv(2 * a.C, 64) : 0};
     if (jw.blocks + jg.blocks) {
-        uni_variant_note("dwln_train reduce<%s> dw=%d gb=%d", dwln_tname<T>(), gw != nullptr, (int)need_gb);
+        uni_variant_note("dwln_train reduce<%s> dw=%d gb=%d", tn, gw != nullptr, (int)need_gb);
         hipLaunchKernelGGL((dwln_reduce_kernel<T>), dim3(jw.blocks + jg.blocks), dim3(256), 0, s, jw, jg);
     }
     UNI_CHECK_HIP(hipGetLastError());

@@ -16,16 +16,13 @@
 //                                  registers (C <= 256: x is read once, two-pass variance per slice).  Otherwise (wider C) the slice is walked in chunks
 //                                  of CH channels, two-pass inside a chunk, and x is read a second time for the output.  Chunks and slices are
 //                                  combined with the pairwise mean / M2 update (Chan et al.), the slices through LDS in ascending wave order.
-//   dwln_reduce_kernel             partials [R][2][C] -> grad_weight, grad_bias (dwln_reduce.h)
+//   dwln_reduce_kernel             partials [R][2][C] -> grad_weight, grad_bias (train_ops.h)
 //
 // mode 0 = forward, 1 = backward.  Every output element has one writer, no atomics, fixed summation orders: bitwise reproducible.  Element
 // offsets are 64-bit; pixel, group and tile indices fit 32 bits (B H W < 2^31 is required).
 #include "kernels.h"
-#include "dwln_reduce.h"
-#include <type_traits>
+#include "train_ops.h"
 
-constexpr int LNCF_MAX_C = 2048;
-constexpr int LNCF_ROWS = 1024;                 // at most this many blocks (= rows of partials)
 constexpr int LNCF_NW = 8;                      // NCHW path: waves of a block
 
 template <typename T>
@@ -39,31 +36,6 @@ struct LncfK {                                  // kernel arguments (by value)
     int HW, C;
     long long M;                                // B H W
 };
-
-// V consecutive elements in accesses of 16 bytes, converted to / from the math type
-template <typename E, int V, typename T>
-__device__ __forceinline__ void lncf_load(const E* p, T (&v)[V]) {
-    constexpr int N = 16 / sizeof(E) < V ? 16 / sizeof(E) : V;
-    using vec = E __attribute__((ext_vector_type(N)));
-#pragma unroll
-    for (int k = 0; k < V / N; ++k) {
-        const vec t = *reinterpret_cast<const vec*>(p + k * N);
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[k * N + i] = (T)t[i];
-    }
-}
-template <typename E, int V, typename T>
-__device__ __forceinline__ void lncf_store(E* p, const T (&v)[V]) {
-    constexpr int N = 16 / sizeof(E) < V ? 16 / sizeof(E) : V;
-    using vec = E __attribute__((ext_vector_type(N)));
-#pragma unroll
-    for (int k = 0; k < V / N; ++k) {
-        vec t;
-#pragma unroll
-        for (int i = 0; i < N; ++i) t[i] = (E)v[k * N + i];
-        *reinterpret_cast<vec*>(p + k * N) = t;
-    }
-}
 
 // sum over the G lanes of a pixel (G a power of two, the lanes are consecutive): xor butterfly, every lane gets the total
 template <typename T>
@@ -91,8 +63,8 @@ __global__ __launch_bounds__(256) void lncf_cl_kernel(LncfK<T> p, int G, int lgG
 #pragma unroll
         for (int j = 0; j < V; ++j) wv[k][j] = bv[k][j] = dg[k][j] = db[k][j] = T(0);
         if (vok[k]) {
-            lncf_load<T, V>(p.w + c[k], wv[k]);
-            if (MODE == 0) lncf_load<T, V>(p.bias + c[k], bv[k]);
+            vec_load<T, V>(p.w + c[k], wv[k]);
+            if (MODE == 0) vec_load<T, V>(p.bias + c[k], bv[k]);
         }
     }
     for (unsigned grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
@@ -104,7 +76,7 @@ __global__ __launch_bounds__(256) void lncf_cl_kernel(LncfK<T> p, int G, int lgG
         for (int k = 0; k < NV; ++k) {
 #pragma unroll
             for (int j = 0; j < V; ++j) xv[k][j] = T(0);
-            if (live && vok[k]) lncf_load<XT, V>(reinterpret_cast<const XT*>(p.x) + e + c[k], xv[k]);
+            if (live && vok[k]) vec_load<XT, V>(reinterpret_cast<const XT*>(p.x) + e + c[k], xv[k]);
         }
         if (MODE == 0) {
             T s = 0;
@@ -129,7 +101,7 @@ __global__ __launch_bounds__(256) void lncf_cl_kernel(LncfK<T> p, int G, int lgG
                     T r[V];
 #pragma unroll
                     for (int j = 0; j < V; ++j) r[j] = (xv[k][j] * rstd) * wv[k][j] + bv[k][j];
-                    lncf_store<T, V>(p.y + e + c[k], r);
+                    vec_store<T, V>(p.y + e + c[k], r);
                 }
                 if (g == 0) {
                     p.stats_out[(size_t)pix * 2] = mean;
@@ -147,7 +119,7 @@ __global__ __launch_bounds__(256) void lncf_cl_kernel(LncfK<T> p, int G, int lgG
             for (int k = 0; k < NV; ++k) {
 #pragma unroll
                 for (int j = 0; j < V; ++j) gv[k][j] = T(0);
-                if (live && vok[k]) lncf_load<T, V>(p.gy + e + c[k], gv[k]);
+                if (live && vok[k]) vec_load<T, V>(p.gy + e + c[k], gv[k]);
             }
             T s1 = 0, s2 = 0;
 #pragma unroll
@@ -174,7 +146,7 @@ __global__ __launch_bounds__(256) void lncf_cl_kernel(LncfK<T> p, int G, int lgG
                         T r[V];
 #pragma unroll
                         for (int j = 0; j < V; ++j) r[j] = rstd * (gv[k][j] - a - xv[k][j] * b);
-                        lncf_store<XT, V>(reinterpret_cast<XT*>(p.gx) + e + c[k], r);
+                        vec_store<XT, V>(reinterpret_cast<XT*>(p.gx) + e + c[k], r);
                     }
                 }
             }
@@ -385,13 +357,7 @@ __global__ __launch_bounds__(512) void lncf_nchw_kernel(LncfK<T> p, unsigned tpi
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-size_t lncf_train_workspace_bytes(int B, int H, int W, int C) {
-    if (B < 1 || H < 1 || W < 1 || C < 4 || C % 4 || C > LNCF_MAX_C || (long long)B * H * W >= (1ll << 31)) return 0;
-    return (size_t)4 * LNCF_ROWS * 2 * C;
-}
-
-static bool lncf_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static const char* lncf_xname(int x_dtype, bool f64) { return f64 ? "f64" : x_dtype == 1 ? "f16" : x_dtype == 2 ? "bf16" : "f32"; }
+size_t lncf_train_workspace_bytes(int B, int H, int W, int C) { return train_shape_ok(B, H, W, C) ? (size_t)4 * TRAIN_ROWS * 2 * C : 0; }
 
 // channels-last: NV vectors per lane and G = 2^lg lanes per pixel with G NV >= nvec and the fewest idle vector slots (the smaller NV on a tie)
 static void lncf_cl_plan(int nvec, int* nv, int* lg) {
@@ -412,12 +378,12 @@ static void lncf_cl_plan(int nvec, int* nv, int* lg) {
 template <typename T, typename XT, int MODE>
 static void lncf_launch(const LncfArgs<T>& a, const LncfK<T>& k, int* rows, hipStream_t s) {
     const char* what = MODE ? "bwd" : "fwd";
-    const char* xn = lncf_xname(a.x_dtype, sizeof(T) == 8);
+    const char* xn = train_ename(a.x_dtype, sizeof(T) == 8);
     const size_t lds = (MODE == 1 && k.part) ? (size_t)2 * a.C * sizeof(double) : 0;       // partial sums across lanes are formed in double
     const int gx = k.gx != nullptr, gwb = k.part != nullptr;
     if (a.nchw) {
         const unsigned tpi = (unsigned)cdiv(k.HW, 64), ntiles = (unsigned)a.B * tpi;              // <= B H W
-        *rows = ntiles < (unsigned)LNCF_ROWS ? (int)ntiles : LNCF_ROWS;
+        *rows = train_rows(ntiles);
         if (a.C <= 16 * LNCF_NW) {
             uni_variant_note("lncf_train %s_nchw<%s,regs=16> gx=%d gwb=%d", what, xn, gx, gwb);
             hipLaunchKernelGGL((lncf_nchw_kernel<T, XT, 16, true, MODE>), dim3(*rows), dim3(64 * LNCF_NW), 0, s, k, tpi, ntiles);
@@ -432,13 +398,13 @@ static void lncf_launch(const LncfArgs<T>& a, const LncfK<T>& k, int* rows, hipS
         }
         return;
     }
-    auto go = [&](auto vtag) {
+    train_with_vwidth<XT>(a.C, [&](auto vtag) {
         constexpr int V = decltype(vtag)::value;
         int nv = 1, lg = 0;
         lncf_cl_plan(a.C / V, &nv, &lg);
         const int ppb = 256 >> lg;
         const unsigned ngroups = (unsigned)((k.M + ppb - 1) / ppb);
-        *rows = ngroups < (unsigned)LNCF_ROWS ? (int)ngroups : LNCF_ROWS;
+        *rows = train_rows(ngroups);
         uni_variant_note("lncf_train %s_cl<%s,V=%d,NV=%d> G=%d gx=%d gwb=%d", what, xn, V, nv, 1 << lg, gx, gwb);
         auto run = [&](auto ntag) {
             constexpr int NV = decltype(ntag)::value;
@@ -455,39 +421,25 @@ static void lncf_launch(const LncfArgs<T>& a, const LncfK<T>& k, int* rows, hipS
                     else run(std::integral_constant<int, 8>());
                 }
         }
-    };
-    if constexpr (sizeof(XT) == 2) {
-        if (a.C % 8 == 0) return go(std::integral_constant<int, 8>());
-    }
-    go(std::integral_constant<int, 4>());
+    });
 }
 
 template <typename T, int MODE>
 static int lncf_dispatch(const char* what, const LncfArgs<T>& a, const LncfK<T>& k, int* rows, hipStream_t s) {
-    if constexpr (sizeof(T) == 8) {
-        UNI_REQUIRE(a.x_dtype == 0, "%s: x_dtype %d: the fp64 form takes fp64 x (0) only", what, a.x_dtype);
-        lncf_launch<T, double, MODE>(a, k, rows, s);
-    } else {
-        UNI_REQUIRE(a.x_dtype >= 0 && a.x_dtype <= 2, "%s: x_dtype %d is not 0 (fp32), 1 (fp16) or 2 (bf16)", what, a.x_dtype);
-        if (a.x_dtype == 0) lncf_launch<T, float, MODE>(a, k, rows, s);
-        else if (a.x_dtype == 1) lncf_launch<T, f16, MODE>(a, k, rows, s);
-        else lncf_launch<T, bf16, MODE>(a, k, rows, s);
-    }
-    return 0;
+    return train_with_etype<T>(what, "x_dtype", a.x_dtype, [&](auto e) { lncf_launch<T, typename decltype(e)::type, MODE>(a, k, rows, s); });
 }
 
 template <typename T>
 static int lncf_check(const char* what, const LncfArgs<T>& a) {
-    UNI_REQUIRE(lncf_train_workspace_bytes(a.B, a.H, a.W, a.C) != 0,
-                "%s: shape B=%d H=%d W=%d C=%d is outside B, H, W >= 1, C %% 4 == 0, 4 <= C <= %d, B H W < 2^31", what, a.B, a.H, a.W, a.C, LNCF_MAX_C);
-    UNI_REQUIRE(lncf_aligned(a.x) && lncf_aligned(a.w) && lncf_aligned(a.bias), "%s: a pointer is not 16-byte aligned", what);
+    if (!train_shape_ok(a.B, a.H, a.W, a.C)) return train_shape_refused(what, a.B, a.H, a.W, a.C);
+    UNI_REQUIRE(aligned16(a.x) && aligned16(a.w) && aligned16(a.bias), "%s: a pointer is not 16-byte aligned", what);
     return 0;
 }
 
 template <typename T>
 int launch_lncf_train_fwd(const LncfArgs<T>& a, T* y, T* stats, hipStream_t s) {
     if (int rc = lncf_check("lncf_train_fwd", a)) return rc;
-    UNI_REQUIRE(lncf_aligned(y) && lncf_aligned(stats), "lncf_train_fwd: a pointer is not 16-byte aligned");
+    UNI_REQUIRE(aligned16(y) && aligned16(stats), "lncf_train_fwd: a pointer is not 16-byte aligned");
     UNI_REQUIRE(a.eps > 0, "lncf_train_fwd: eps %g is not positive", a.eps);
     const LncfK<T> k{a.x, a.w, a.bias, nullptr, nullptr, y, stats, nullptr, nullptr, (T)a.eps, a.H * a.W, a.C, (long long)a.B * a.H * a.W};
     int rows;
@@ -500,21 +452,18 @@ template <typename T>
 int launch_lncf_train_bwd(const LncfArgs<T>& a, const T* stats, const T* gy, void* gx, T* gw, T* gb, void* ws, size_t ws_bytes, hipStream_t s) {
     if (int rc = lncf_check("lncf_train_bwd", a)) return rc;
     UNI_REQUIRE((gw != nullptr) == (gb != nullptr), "lncf_train_bwd: grad_weight and grad_bias come as a pair");
-    UNI_REQUIRE(lncf_aligned(stats) && lncf_aligned(gy) && lncf_aligned(gx) && lncf_aligned(gw) && lncf_aligned(gb) && lncf_aligned(ws),
+    UNI_REQUIRE(aligned16(stats) && aligned16(gy) && aligned16(gx) && aligned16(gw) && aligned16(gb) && aligned16(ws),
                 "lncf_train_bwd: a pointer is not 16-byte aligned");
     if (!gx && !gw) return 0;
-    if (gw) {
-        const size_t need = lncf_train_workspace_bytes(a.B, a.H, a.W, a.C) * (sizeof(T) / 4);
-        UNI_REQUIRE(ws && ws_bytes >= need, "lncf_train_bwd: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, need);
-    }
-    T* part = gw ? reinterpret_cast<T*>(ws) : nullptr;
+    T* part;
+    if (int rc = train_partials("lncf_train_bwd", gw != nullptr, ws, ws_bytes, lncf_train_workspace_bytes(a.B, a.H, a.W, a.C), &part)) return rc;
     const LncfK<T> k{a.x, a.w, nullptr, gy, stats, nullptr, nullptr, gx, part, T(0), a.H * a.W, a.C, (long long)a.B * a.H * a.W};
     int rows;
     if (int rc = lncf_dispatch<T, 1>("lncf_train_bwd", a, k, &rows, s)) return rc;
     if (gw) {
         const DwlnRJob none{nullptr, nullptr, nullptr, 0, 0, 0, 0};
         const DwlnRJob job{part, gw, gb, rows, 2 * a.C, a.C, cdiv(2 * a.C, 64)};
-        uni_variant_note("lncf_train reduce<%s>", sizeof(T) == 8 ? "f64" : "f32");
+        uni_variant_note("lncf_train reduce<%s>", train_ename(0, sizeof(T) == 8));
         hipLaunchKernelGGL((dwln_reduce_kernel<T>), dim3(job.blocks), dim3(256), 0, s, none, job);
     }
     UNI_CHECK_HIP(hipGetLastError());

@@ -67,7 +67,7 @@ def _fusable(block):
     if not (conv.kernel_size == (7, 7) and conv.padding == (3, 3) and conv.stride == (1, 1) and conv.dilation == (1, 1)
             and conv.padding_mode == "zeros" and conv.groups == Cc == conv.out_channels and conv.bias is not None):
         return False
-    if Cc % 4 or not 4 <= Cc <= ops.DWLN_MAX_C:
+    if Cc % 4 or not 4 <= Cc <= ops.TRAIN_MAX_C:
         return False
     w, b = getattr(norm, "weight", None), getattr(norm, "bias", None)
     if not isinstance(w, torch.Tensor) or not isinstance(b, torch.Tensor) or not isinstance(getattr(norm, "eps", None), float):
@@ -146,7 +146,7 @@ def _tail_fusable(block):
     Cc = getattr(block.dwconv, "in_channels", None)
     if not isinstance(block.pwconv2, torch.nn.Linear) or not isinstance(Cc, int) or block.pwconv2.out_features != Cc:
         return False
-    if Cc % 4 or not 4 <= Cc <= ops.DWLN_MAX_C or not hasattr(block, "gamma"):
+    if Cc % 4 or not 4 <= Cc <= ops.TRAIN_MAX_C or not hasattr(block, "gamma"):
         return False
     g = block.gamma
     if g is not None and not (isinstance(g, torch.nn.Parameter) and tuple(g.shape) == (Cc,)):
@@ -207,7 +207,7 @@ def _lncf_fusable(m):
     Cc = w.shape[0]
     if tuple(b.shape) != (Cc,) or tuple(getattr(m, "normalized_shape", ())) != (Cc,):
         return False
-    return Cc % 4 == 0 and 4 <= Cc <= ops.DWLN_MAX_C
+    return Cc % 4 == 0 and 4 <= Cc <= ops.TRAIN_MAX_C
 
 
 def fuse_layernorm_cf(model):

@@ -882,15 +882,66 @@ def mot_corr_loss(embed_0, embed_1, targets, s=8, bidirect=True, grid_sample=Tru
     return MotCorrLossFunction.apply(embed_0, embed_1, targets.detach().float().contiguous(), float(s), flags)
 
 
-DWLN_MAX_C = 2048
+# ---- what the three ConvNeXt training operators (dwconv7_ln, block_tail, layernorm_cf) share: their argument checks, in the order each calls them
+TRAIN_MAX_C = 2048
+DWLN_MAX_C = TRAIN_MAX_C          # the earlier name
+_STORE_DTYPE = {torch.float32: 0, torch.float64: 0, torch.float16: 1, torch.bfloat16: 2}     # the y_dtype / x_dtype argument of the library
 
 
-def _dwln_ws(dev, dtype, N, H, W, Cc):
-    need = L.lib().uni_dwln_train_workspace_bytes(N, H, W, Cc)
+def _check_tensors(op, names, ts, optional=()):
+    """every argument is a tensor; those named in `optional` may be None"""
+    for n, t in zip(names, ts):
+        if not isinstance(t, torch.Tensor) and (t is not None or n not in optional):
+            raise L.UnicornHipError("%s: %s is not a tensor%s" % (op, n, " or None" if n in optional else ""))
+
+
+def _check_map_dims(op, name, t):
+    """-> N, C, H, W of the map `t`"""
+    if t.dim() != 4:
+        raise L.UnicornHipError("%s: %s of shape %s is not (N, C, H, W)" % (op, name, tuple(t.shape)))
+    return t.shape
+
+
+def _check_channel_vecs(op, names, ts, Cc):
+    for n, t in zip(names, ts):
+        if tuple(t.shape) != (Cc,):
+            raise L.UnicornHipError("%s: %s of shape %s is not (%d,)" % (op, n, tuple(t.shape), Cc))
+
+
+def _check_train_shape(op, N, Cc, H, W):
+    if Cc % 4 or not 4 <= Cc <= TRAIN_MAX_C:
+        raise L.UnicornHipError("%s: C = %d is outside C %% 4 == 0, 4 <= C <= %d" % (op, Cc, TRAIN_MAX_C))
+    if N and (H == 0 or W == 0 or N * H * W >= 1 << 31):
+        raise L.UnicornHipError("%s: shape N=%d H=%d W=%d is outside a non-empty map with N H W < 2^31" % (op, N, H, W))
+
+
+def _check_eps(op, eps):
+    if not float(eps) > 0:
+        raise L.UnicornHipError("%s: eps = %r is not positive" % (op, eps))
+
+
+def _check_one_device(op, ts):
+    _need_cuda(*ts)
+    if len({t.device for t in ts}) != 1:
+        raise L.UnicornHipError("%s: tensors on different devices" % op)
+
+
+def _train_ws(op, entry_name, dev, dtype, N, H, W, Cc):
+    """the backward workspace that the library function `entry_name` (uni_*_workspace_bytes) sizes: uninitialised bytes on `dev`"""
+    need = getattr(L.lib(), entry_name)(N, H, W, Cc)
     if need == 0:
-        raise L.UnicornHipError("dwconv7_ln: shape N=%d C=%d H=%d W=%d is outside the limits of uni_dwln_train_bwd (include/unicorn_hip.h)"
-                                % (N, Cc, H, W))
+        raise L.UnicornHipError("%s: shape N=%d C=%d H=%d W=%d is outside the limits of %s (include/unicorn_hip.h)"
+                                % (op, N, Cc, H, W, entry_name.replace("workspace_bytes", "bwd")))
     return torch.empty(need * _ws_factor(dtype), device=dev, dtype=torch.uint8)
+
+
+def _map_layout(t):
+    """-> (t or a channels-last copy of it, nchw flag): NCHW-contiguous and channels-last memory are read in place"""
+    if t.is_contiguous(memory_format=torch.channels_last):
+        return t, 0
+    if t.is_contiguous():
+        return t, 1
+    return t.contiguous(memory_format=torch.channels_last), 0
 
 
 class DwConv7LNFunction(torch.autograd.Function):
@@ -943,7 +994,7 @@ class DwConv7LNFunction(torch.autograd.Function):
             g = grad_y.contiguous()
             wt = weight.reshape(Cc, 49).t().contiguous()
             with torch.cuda.device(xc.device):
-                ws = _dwln_ws(xc.device, xc.dtype, N, H, W, Cc)
+                ws = _train_ws("dwconv7_ln", "uni_dwln_train_workspace_bytes", xc.device, xc.dtype, N, H, W, Cc)
                 L.check(fn(L.ptr(xc), L.ptr(wt), L.ptr(bias.contiguous()), L.ptr(ln_weight.contiguous()), L.ptr(stats), L.ptr(g), N, H, W, Cc,
                            L.ptr(gx), L.ptr(gwt), L.ptr(gb), L.ptr(gg), L.ptr(gbe), L.ptr(ws), ws.numel(), L.stream_ptr()), name)
         gw = gwt.t().reshape(Cc, 1, 7, 7).contiguous() if need[1] else None
@@ -960,24 +1011,14 @@ def dwconv7_ln(x, weight, bias, ln_weight, ln_bias, eps=1e-6):
     parameters and two numbers per pixel; neither y nor the convolution output.  N == 0 returns an empty tensor without a library call."""
     names = ("x", "weight", "bias", "ln_weight", "ln_bias")
     ts = (x, weight, bias, ln_weight, ln_bias)
-    for n, t in zip(names, ts):
-        if not isinstance(t, torch.Tensor):
-            raise L.UnicornHipError("dwconv7_ln: %s is not a tensor" % n)
-    if x.dim() != 4:
-        raise L.UnicornHipError("dwconv7_ln: x of shape %s is not (N, C, H, W)" % (tuple(x.shape),))
-    N, Cc, H, W = x.shape
+    _check_tensors("dwconv7_ln", names, ts)
+    N, Cc, H, W = _check_map_dims("dwconv7_ln", "x", x)
     if tuple(weight.shape) != (Cc, 1, 7, 7):
         raise L.UnicornHipError("dwconv7_ln: weight of shape %s is not the depthwise 7x7 weight (%d, 1, 7, 7) of x's %d channels"
                                 % (tuple(weight.shape), Cc, Cc))
-    for n, t in zip(names[2:], ts[2:]):
-        if tuple(t.shape) != (Cc,):
-            raise L.UnicornHipError("dwconv7_ln: %s of shape %s is not (%d,)" % (n, tuple(t.shape), Cc))
-    if Cc % 4 or not 4 <= Cc <= DWLN_MAX_C:
-        raise L.UnicornHipError("dwconv7_ln: C = %d is outside C %% 4 == 0, 4 <= C <= %d" % (Cc, DWLN_MAX_C))
-    if N and (H == 0 or W == 0 or N * H * W >= 1 << 31):
-        raise L.UnicornHipError("dwconv7_ln: shape N=%d H=%d W=%d is outside a non-empty map with N H W < 2^31" % (N, H, W))
-    if not float(eps) > 0:
-        raise L.UnicornHipError("dwconv7_ln: eps = %r is not positive" % (eps,))
+    _check_channel_vecs("dwconv7_ln", names[2:], ts[2:], Cc)
+    _check_train_shape("dwconv7_ln", N, Cc, H, W)
+    _check_eps("dwconv7_ln", eps)
     autocast = x.is_cuda and torch.is_autocast_enabled("cuda")
     if autocast:
         if not all(t.is_floating_point() for t in ts):
@@ -985,22 +1026,8 @@ def dwconv7_ln(x, weight, bias, ln_weight, ln_bias, eps=1e-6):
     elif x.dtype not in _F64_SFX or any(t.dtype != x.dtype for t in ts):
         raise L.UnicornHipError("dwconv7_ln: dtypes %s unsupported (all fp32 or all fp64; half inputs only under torch.autocast)"
                                 % ", ".join(str(t.dtype) for t in ts))
-    _need_cuda(*ts)
-    if len({t.device for t in ts}) != 1:
-        raise L.UnicornHipError("dwconv7_ln: tensors on different devices")
+    _check_one_device("dwconv7_ln", ts)
     return DwConv7LNFunction.apply(x, weight, bias, ln_weight, ln_bias, float(eps))
-
-
-_BT_Y_DTYPE = {torch.float32: 0, torch.float64: 0, torch.float16: 1, torch.bfloat16: 2}
-
-
-def _bt_layout(t):
-    """-> (t or a channels-last copy of it, nchw flag): NCHW-contiguous and channels-last memory are read in place"""
-    if t.is_contiguous(memory_format=torch.channels_last):
-        return t, 0
-    if t.is_contiguous():
-        return t, 1
-    return t.contiguous(memory_format=torch.channels_last), 0
 
 
 class BlockTailFunction(torch.autograd.Function):
@@ -1018,10 +1045,10 @@ class BlockTailFunction(torch.autograd.Function):
         out = torch.empty((N, Cc, H, W), device=residual.device, dtype=residual.dtype, memory_format=torch.channels_last)
         if N == 0:
             return out
-        res, nchw = _bt_layout(residual)
+        res, nchw = _map_layout(residual)
         fn, name = _entry("uni_block_tail_fwd", residual.dtype)
         with torch.cuda.device(residual.device):
-            L.check(fn(L.ptr(y), _BT_Y_DTYPE[y.dtype], L.ptr(res), nchw, L.ptr(gamma), L.ptr(scale), N, H, W, Cc, L.ptr(out), L.stream_ptr()), name)
+            L.check(fn(L.ptr(y), _STORE_DTYPE[y.dtype], L.ptr(res), nchw, L.ptr(gamma), L.ptr(scale), N, H, W, Cc, L.ptr(out), L.stream_ptr()), name)
         return out
 
     @staticmethod
@@ -1035,13 +1062,11 @@ class BlockTailFunction(torch.autograd.Function):
         if N == 0:
             return gy, grad_out if need_res else None, gg.zero_() if need_g else None, None
         if need_y or need_g:
-            g, nchw = _bt_layout(grad_out)
+            g, nchw = _map_layout(grad_out)
             fn, name = _entry("uni_block_tail_bwd", g.dtype)
             with torch.cuda.device(g.device):
-                ws = None
-                if need_g:
-                    ws = torch.empty(L.lib().uni_block_tail_workspace_bytes(N, H, W, Cc) * _ws_factor(g.dtype), device=g.device, dtype=torch.uint8)
-                L.check(fn(L.ptr(y), _BT_Y_DTYPE[y.dtype], L.ptr(g), nchw, L.ptr(gamma), L.ptr(scale), N, H, W, Cc, L.ptr(gy), L.ptr(gg),
+                ws = _train_ws("block_tail", "uni_block_tail_workspace_bytes", g.device, g.dtype, N, H, W, Cc) if need_g else None
+                L.check(fn(L.ptr(y), _STORE_DTYPE[y.dtype], L.ptr(g), nchw, L.ptr(gamma), L.ptr(scale), N, H, W, Cc, L.ptr(gy), L.ptr(gg),
                            L.ptr(ws), ws.numel() if need_g else 0, L.stream_ptr()), name)
         return gy, grad_out if need_res else None, gg, None
 
@@ -1059,39 +1084,27 @@ def block_tail(y, residual, gamma=None, scale=None):
     place in either of the two layouts.  Autograd keeps y, gamma and scale, never out.  C % 4 == 0, 4 <= C <= 2048.  The one deliberate
     difference to the eager lines: a sample with scale 0 is not read, so its grad_y is 0 and it adds 0 to grad_gamma even where y holds Inf
     or NaN (eager gives NaN).  N == 0 returns an empty tensor without a library call."""
-    for n, t in (("y", y), ("residual", residual)):
-        if not isinstance(t, torch.Tensor):
-            raise L.UnicornHipError("block_tail: %s is not a tensor" % n)
-    for n, t in (("gamma", gamma), ("scale", scale)):
-        if t is not None and not isinstance(t, torch.Tensor):
-            raise L.UnicornHipError("block_tail: %s is not a tensor or None" % n)
-    if residual.dim() != 4:
-        raise L.UnicornHipError("block_tail: residual of shape %s is not (N, C, H, W)" % (tuple(residual.shape),))
-    N, Cc, H, W = residual.shape
+    _check_tensors("block_tail", ("y", "residual", "gamma", "scale"), (y, residual, gamma, scale), optional=("gamma", "scale"))
+    N, Cc, H, W = _check_map_dims("block_tail", "residual", residual)
     if tuple(y.shape) != (N, H, W, Cc):
         raise L.UnicornHipError("block_tail: y of shape %s is not (N, H, W, C) = (%d, %d, %d, %d) of residual" % (tuple(y.shape), N, H, W, Cc))
-    if gamma is not None and tuple(gamma.shape) != (Cc,):
-        raise L.UnicornHipError("block_tail: gamma of shape %s is not (%d,)" % (tuple(gamma.shape), Cc))
+    if gamma is not None:
+        _check_channel_vecs("block_tail", ("gamma",), (gamma,), Cc)
     if scale is not None and tuple(scale.shape) not in ((N,), (N, 1, 1, 1)):
         raise L.UnicornHipError("block_tail: scale of shape %s is not (%d,) or (%d, 1, 1, 1)" % (tuple(scale.shape), N, N))
-    if Cc % 4 or not 4 <= Cc <= DWLN_MAX_C:
-        raise L.UnicornHipError("block_tail: C = %d is outside C %% 4 == 0, 4 <= C <= %d" % (Cc, DWLN_MAX_C))
-    if N and (H == 0 or W == 0 or N * H * W >= 1 << 31):
-        raise L.UnicornHipError("block_tail: shape N=%d H=%d W=%d is outside a non-empty map with N H W < 2^31" % (N, H, W))
+    _check_train_shape("block_tail", N, Cc, H, W)
     if scale is not None and scale.requires_grad:
         raise L.UnicornHipError("block_tail: scale requires a gradient; it is a constant of the step")
     ts = [t for t in (y, residual, gamma, scale) if t is not None]
     if y.dtype == torch.float64:
         ok = all(t.dtype == torch.float64 for t in ts)
     else:
-        ok = (y.dtype in _BT_Y_DTYPE and residual.dtype in (torch.float32, torch.float16, torch.bfloat16)
+        ok = (y.dtype in _STORE_DTYPE and residual.dtype in (torch.float32, torch.float16, torch.bfloat16)
               and all(t.dtype == torch.float32 for t in (gamma, scale) if t is not None))
     if not ok:
         raise L.UnicornHipError("block_tail: dtypes %s unsupported (y fp32 / fp16 / bf16 with residual fp32 or half and gamma, scale fp32; or "
                                 "all fp64)" % ", ".join(str(t.dtype) for t in ts))
-    _need_cuda(*ts)
-    if len({t.device for t in ts}) != 1:
-        raise L.UnicornHipError("block_tail: tensors on different devices")
+    _check_one_device("block_tail", ts)
     if residual.dtype in (torch.float16, torch.bfloat16):
         residual = residual.float()
     if scale is not None:
@@ -1116,7 +1129,7 @@ class LayerNormCFFunction(torch.autograd.Function):
         N, Cc, H, W = x.shape
         ctx.dims = (N, Cc, H, W)
         out_dtype = torch.promote_types(x.dtype, weight.dtype)
-        xc, nchw = _bt_layout(x)
+        xc, nchw = _map_layout(x)
         ctx.nchw = nchw
         y = _lncf_like(xc, nchw, out_dtype)
         if N == 0:
@@ -1125,7 +1138,7 @@ class LayerNormCFFunction(torch.autograd.Function):
         stats = torch.empty((N * H * W, 2), device=x.device, dtype=out_dtype)
         fn, name = _entry("uni_lncf_train_fwd", out_dtype)
         with torch.cuda.device(x.device):
-            L.check(fn(L.ptr(xc), _BT_Y_DTYPE[xc.dtype], nchw, L.ptr(weight), L.ptr(bias), float(eps), N, H, W, Cc, L.ptr(y), L.ptr(stats),
+            L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], nchw, L.ptr(weight), L.ptr(bias), float(eps), N, H, W, Cc, L.ptr(y), L.ptr(stats),
                        L.stream_ptr()), name)
         ctx.save_for_backward(xc, weight, stats)
         return y
@@ -1148,11 +1161,8 @@ class LayerNormCFFunction(torch.autograd.Function):
             g = grad_out.contiguous() if nchw else grad_out.contiguous(memory_format=torch.channels_last)       # no copy in the layout of x
             fn, name = _entry("uni_lncf_train_bwd", weight.dtype)
             with torch.cuda.device(xc.device):
-                ws = None
-                if need_p:
-                    ws = torch.empty(L.lib().uni_lncf_train_workspace_bytes(N, H, W, Cc) * _ws_factor(weight.dtype), device=xc.device,
-                                     dtype=torch.uint8)
-                L.check(fn(L.ptr(xc), _BT_Y_DTYPE[xc.dtype], nchw, L.ptr(weight), L.ptr(stats), L.ptr(g), N, H, W, Cc, L.ptr(gx), L.ptr(gw),
+                ws = _train_ws("layernorm_cf", "uni_lncf_train_workspace_bytes", xc.device, weight.dtype, N, H, W, Cc) if need_p else None
+                L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], nchw, L.ptr(weight), L.ptr(stats), L.ptr(g), N, H, W, Cc, L.ptr(gx), L.ptr(gw),
                            L.ptr(gb), L.ptr(ws), ws.numel() if need_p else 0, L.stream_ptr()), name)
         return gx, gw if ctx.needs_input_grad[1] else None, gb if ctx.needs_input_grad[2] else None, None
 
@@ -1172,31 +1182,19 @@ def layernorm_cf(x, weight, bias, eps=1e-6):
     C % 4 == 0, 4 <= C <= 2048.  N == 0 returns an empty tensor without a library call."""
     names = ("x", "weight", "bias")
     ts = (x, weight, bias)
-    for n, t in zip(names, ts):
-        if not isinstance(t, torch.Tensor):
-            raise L.UnicornHipError("layernorm_cf: %s is not a tensor" % n)
-    if x.dim() != 4:
-        raise L.UnicornHipError("layernorm_cf: x of shape %s is not (N, C, H, W)" % (tuple(x.shape),))
-    N, Cc, H, W = x.shape
-    for n, t in zip(names[1:], ts[1:]):
-        if tuple(t.shape) != (Cc,):
-            raise L.UnicornHipError("layernorm_cf: %s of shape %s is not (%d,)" % (n, tuple(t.shape), Cc))
-    if Cc % 4 or not 4 <= Cc <= DWLN_MAX_C:
-        raise L.UnicornHipError("layernorm_cf: C = %d is outside C %% 4 == 0, 4 <= C <= %d" % (Cc, DWLN_MAX_C))
-    if N and (H == 0 or W == 0 or N * H * W >= 1 << 31):
-        raise L.UnicornHipError("layernorm_cf: shape N=%d H=%d W=%d is outside a non-empty map with N H W < 2^31" % (N, H, W))
-    if not float(eps) > 0:
-        raise L.UnicornHipError("layernorm_cf: eps = %r is not positive" % (eps,))
+    _check_tensors("layernorm_cf", names, ts)
+    N, Cc, H, W = _check_map_dims("layernorm_cf", "x", x)
+    _check_channel_vecs("layernorm_cf", names[1:], ts[1:], Cc)
+    _check_train_shape("layernorm_cf", N, Cc, H, W)
+    _check_eps("layernorm_cf", eps)
     if x.dtype == torch.float64:
         ok = weight.dtype == bias.dtype == torch.float64
     else:
-        ok = x.dtype in _BT_Y_DTYPE and weight.dtype == bias.dtype == torch.float32
+        ok = x.dtype in _STORE_DTYPE and weight.dtype == bias.dtype == torch.float32
     if not ok:
         raise L.UnicornHipError("layernorm_cf: dtypes %s unsupported (x fp32 / fp16 / bf16 with weight, bias fp32; or all fp64)"
                                 % ", ".join(str(t.dtype) for t in ts))
-    _need_cuda(*ts)
-    if len({t.device for t in ts}) != 1:
-        raise L.UnicornHipError("layernorm_cf: tensors on different devices")
+    _check_one_device("layernorm_cf", ts)
     return LayerNormCFFunction.apply(x, weight.contiguous(), bias.contiguous(), float(eps))
 
 
