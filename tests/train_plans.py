@@ -1,0 +1,124 @@
+"""The launch plans of the three ConvNeXt training operators (ops.layernorm_cf / csrc/lncf_train.hip, ops.dwconv7_ln / csrc/dwln_train.hip,
+ops.block_tail / csrc/block_tail.hip), written down as explicit lists, and the maps their parity cases run on.
+
+A launcher's variant tag (uni_variant_trace, include/unicorn_hip.h) reads `<operator> <fwd|bwd...><plan> <need flags>`, for instance
+`lncf_train bwd_cl<f16,V=8,NV=3> G=4 gx=1 gwb=1`.  The PLAN CLASS of a tag is the part between the kernel name and the need flags:
+`cl<f16,V=8,NV=3> G=4`.  It names the template instantiation and the lane mapping, and the forward and the backward of one call carry the
+same one.  EXPECTED lists, per operator, every plan class the host code can pick for C = 4, 8, ..., 2048 (lncf_cl_plan / lncf_launch,
+dwln_plan).  tests/test_train_plans_gpu.py sweeps every C on the device and demands that the classes found are EXPECTED, in both
+directions -- a retuned plan function shows up as a diff of these lists, an instantiation nobody can reach as well -- and then runs the
+smallest and the largest C of every class against the operator's restatement.  block_tail's tag does not carry its plan (PP = 512 / (C / V)
+is a kernel argument, not a template argument), so it has an explicit list of widths instead.
+
+Data and small helpers only: no GPU work, importable without a device."""
+import re
+
+C_STEP, C_MAX = 4, 2048                     # train_shape_ok (csrc/train_ops.h): C % 4 == 0, 4 <= C <= TRAIN_MAX_C
+SWEEP_C = tuple(range(C_STEP, C_MAX + 1, C_STEP))
+
+# (N, H, W) of the parity cases.  21 pixels per image and 42 in all: neither is a multiple of any pixels-per-block value of the channels-last
+# kernels (4 .. 256) or of the 64-pixel tile of the NCHW kernels, and a tile ends with its image.  block_tail runs three samples of this map.
+MAP = (2, 3, 7)
+# dwln: W = 11 is two strips of 8 pixels per row in fp32, the last of 3; six strips of 2 in fp64, the last of 1
+MAP_DW = (2, 5, 11)
+
+# every stage width of the ConvNeXt variants (96 .. 1536, 128 .. 1024, 192 .. 1536, 256 .. 2048), the smallest V = 8 width and four ragged ones:
+#   C = 384: PP = 5; 768: PP = 2 on 384 threads; 2048: CG = 512, PP = 1; 1000: PP = 2, 12 threads of the block idle; 500: PP = 4, 12 idle;
+#   2044: PP = 1, one idle lane; in NCHW memory 1000 and 2044 end in a partial channel tile behind 15 and 31 whole ones
+WIDTHS_BT = (8, 96, 100, 128, 192, 256, 384, 500, 512, 768, 1000, 1024, 1536, 2044, 2048)
+SCALE_BT = (1 / 0.7, 0.0, 1 / 0.7)          # the middle sample dropped, as STRADDLE of tests/test_block_tail_gpu.py
+
+_G = (1, 2, 4, 8, 16, 32, 64)
+# channels-last lncf: (NV, G) with G NV >= C / V and the fewest idle vector slots.  NV = 1 and NV = 3 exist at every G; 2, 4, 6 and 8 only
+# at G = 64 (below it a smaller NV with a larger G has as few idle slots and wins the tie)
+_CL_V4 = [(1, g) for g in _G] + [(2, 64)] + [(3, g) for g in _G] + [(4, 64), (6, 64), (8, 64)]          # 18
+_CL_V8 = [(1, g) for g in _G] + [(2, 64)] + [(3, g) for g in _G] + [(4, 64)]                            # 16: C / 8 <= 256 = 4 x 64
+# half x with C % 8 == 4 stays at V = 4: C / 4 is odd there, so NV = 1 with G = 2 or 4 (C = 8, 16) cannot occur; the other sixteen can
+_CL_V4_HALF = [p for p in _CL_V4 if p not in ((1, 2), (1, 4))]                                          # 16
+
+
+def _cl(dt, V, pairs):
+    return ["cl<%s,V=%d,NV=%d> G=%d" % (dt, V, nv, g) for nv, g in pairs]
+
+
+EXPECTED = {
+    "lncf": (_cl("f32", 4, _CL_V4) + _cl("f64", 4, _CL_V4)
+             + _cl("f16", 8, _CL_V8) + _cl("bf16", 8, _CL_V8) + _cl("f16", 4, _CL_V4_HALF) + _cl("bf16", 4, _CL_V4_HALF)
+             # NCHW: 16 channels per lane in registers (C <= 128), 32 (fp32 arithmetic only, C <= 256), else streamed in chunks of 8
+             + ["nchw<%s,%s>" % (dt, plan) for dt in ("f32", "f16", "bf16") for plan in ("regs=16", "regs=32", "stream=8")]
+             + ["nchw<f64,regs=16>", "nchw<f64,stream=8>"]),
+    # wps = ceil(C / 4 / 64) waves per strip, NS = 512 / (64 wps) strips per block; 8 pixels per lane in fp32, 2 in fp64
+    "dwln": ["<%s,PXT=%d> wps=%d NS=%d" % (dt, pxt, wps, 512 // (64 * wps)) for dt, pxt in (("f32", 8), ("f64", 2)) for wps in range(1, 9)],
+}
+
+# the classes no test had launched before this table existed, for the record and for the census file
+FIRST_RUN = {
+    "lncf": [c for c in EXPECTED["lncf"] if re.search(r"NV=[248]>|V=8,NV=[124]>|^cl<(f16|bf16),V=4,NV=[68]>|regs=32", c)],
+    "dwln": [c for c in EXPECTED["dwln"] if re.search(r"wps=[4578] ", c)],
+}
+
+
+def predicted(op, layout, dt, C):
+    """The plan class the lists above were written from, by the arithmetic of lncf_cl_plan / lncf_launch / dwln_plan restated: it picks the
+    widths of the CPU checks and says where a class begins and ends.  The sweep on the device is the authority, not this."""
+    if op == "dwln":
+        wps = (C // 4 + 63) // 64
+        return "<%s,PXT=%d> wps=%d NS=%d" % (dt, 2 if dt == "f64" else 8, wps, 512 // (64 * wps))
+    if layout == "nchw":
+        return "nchw<%s,%s>" % (dt, "regs=16" if C <= 128 else "regs=32" if C <= 256 and dt != "f64" else "stream=8")
+    V = 8 if dt in ("f16", "bf16") and C % 8 == 0 else 4
+    best = None
+    for nv in (1, 2, 3, 4, 6, 8):
+        lg = 0
+        while (nv << lg) < C // V:
+            lg += 1
+        if lg <= 6 and (best is None or (nv << lg) < best[0]):
+            best = (nv << lg, nv, 1 << lg)
+    return "cl<%s,V=%d,NV=%d> G=%d" % (dt, V, best[1], best[2])
+
+
+_FLAGS = re.compile(r"(?: (?:gx|gwb|du|gb|gy|gg)=\d+)+$")
+_KERNEL = re.compile(r"^(lncf_train|dwln_train|block_tail) (fwd|bwd)(_a|_dx)?_?")
+
+
+def strip_flags(tag):
+    """a variant tag without its trailing need flags (gx= gwb=, du= gb=, gy= gg=)"""
+    return _FLAGS.sub("", tag)
+
+
+def plan_class(tag):
+    """the plan class of a map kernel's tag: 'lncf_train bwd_cl<f32,V=4,NV=3> G=8 gx=1 gwb=0' -> 'cl<f32,V=4,NV=3> G=8',
+    'dwln_train bwd_a<f32,PXT=8> wps=1 NS=8 du=1 gb=1' -> '<f32,PXT=8> wps=1 NS=8'.  None for a tag that is not one of a map kernel
+    (the reduce launches, the weight pass of dwln)"""
+    m = _KERNEL.match(tag)
+    if not m or " reduce" in tag or "bwd_dw" in tag:
+        return None
+    return strip_flags(tag[m.end():])
+
+
+def group(by_c):
+    """{C: tag} -> {tag: [C, ...]}, every list ascending"""
+    out = {}
+    for C in sorted(by_c):
+        out.setdefault(by_c[C], []).append(C)
+    return out
+
+
+def ends(cs):
+    """the smallest and the largest C of a class (one value where they coincide): the smallest has the most idle vector slots or lanes, the
+    largest is the full one"""
+    return sorted({min(cs), max(cs)})
+
+
+def bt_class(layout, dt, C):
+    """the plan part of the block_tail tag at width C: V = 8 for half y where C allows it"""
+    if layout == "nchw":
+        return "nchw<%s>" % dt
+    return "cl<%s,V=%d>" % (dt, 8 if dt in ("f16", "bf16") and C % 8 == 0 else 4)
+
+
+def zero_one_vector(x, C):
+    """x (N, C, H, W) with the last 4-channel vector of pixel (0, 0, 0) zeroed: what a lane whose `vok`, G or slot index is wrong reads"""
+    x = x.clone()
+    x[0, C - 4:C, 0, 0] = 0.0
+    return x
