@@ -521,6 +521,38 @@ int uni_lncf_train_bwd_f64(const void* x, int x_dtype, int nchw, const double* w
                            int W, int C, void* grad_x, double* grad_weight, double* grad_bias, void* workspace, size_t workspace_bytes,
                            uni_stream_t stream);
 
+/* The point-wise middle of the ConvNeXt block's MLP for TRAINING (unicorn/models/backbone/convnext.py:46-48: x = pwconv1(x); x = act(x);
+ * x = pwconv2(x) with act = nn.GELU(), the exact erf form): the GELU forward, and a backward that REBUILDS a = gelu(h) from h, so that the
+ * caller keeps h (or only the input of pwconv1) instead of h and a.  The two GEMMs are the caller's (the vendor library).  One launch forward,
+ * at most three backward, no host synchronisation, no read-back, no allocation, no atomics.  Operator only.
+ *   h, a, grad_a, grad_h   dense [M][Hd]: rows = the M = N H W pixels, row pitch Hd;  grad_y dense [M][Co].  h_dtype: 0 = the type of the form
+ *                          (fp32, fp64 in the _f64 form), 1 = fp16, 2 = bf16 (fp32 form only) is the element type of all five.  Conversion
+ *                          in registers, all arithmetic fp32 (fp64).
+ *   grad_b1 [Hd], grad_b2 [Co]   in the type of the form
+ *   uni_pw_mlp_act_fwd   a = gelu(h) = h (1 + erf(h / sqrt 2)) / 2, written COMPLETELY.  a == h (in place) is allowed: every element is read and
+ *                        then written by the same lane.
+ *   uni_pw_mlp_act_bwd   one map kernel reads h and grad_a and writes what is asked for: a = gelu(h) (a == h allowed), grad_h = grad_a *
+ *                        gelu'(h) with gelu'(v) = Phi(v) + v phi(v) (grad_h == grad_a allowed), and per-block partial column sums of the
+ *                        UNROUNDED grad_h that an ordered reduce turns into grad_b1.  With grad_b2, a column-sum kernel over grad_y runs and
+ *                        its partials go through the SAME reduce launch.  a, grad_h, grad_b1 and grad_b2 may each be NULL: that part is
+ *                        skipped, what is computed has the same bits as in the full call.  h may be NULL when only grad_b2 is asked for,
+ *                        grad_a when neither grad_h nor grad_b1 is, grad_y without grad_b2; the workspace without grad_b1 and grad_b2 (it is
+ *                        then not touched).  Nothing asked for: no launch, no error.
+ * One writer per element, fixed summation orders (a lane's own rows in the math type; the lanes of a block and the rows of partials in
+ * ascending order in double): two calls give the same bits.
+ * Limits: 1 <= M < 2^31 (element offsets are 64-bit), Hd % 4 == 0, 4 <= Hd <= 8192, Co % 4 == 0, 4 <= Co <= 8192 (Co is checked even where
+ * grad_b2 is NULL), pointers 16-byte aligned; other shapes are refused with an error string and uni_pw_mlp_workspace_bytes returns 0 for them.
+ * workspace (backward with grad_b1 or grad_b2 only): 16-byte aligned device scratch of >= uni_pw_mlp_workspace_bytes(M, Hd, Co) bytes (fp32;
+ * the _f64 form needs twice that) = 4 * 256 * (Hd + Co): at most 256 blocks along the rows write one row of Hd (Co) partial sums each.  Nothing
+ * is kept in it between calls. */
+size_t uni_pw_mlp_workspace_bytes(int M, int Hd, int Co);
+int uni_pw_mlp_act_fwd(const void* h, int h_dtype, int M, int Hd, void* a, uni_stream_t stream);
+int uni_pw_mlp_act_bwd(const void* h, int h_dtype, const void* grad_a, int M, int Hd, void* a, void* grad_h, float* grad_b1, const void* grad_y,
+                       int Co, float* grad_b2, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+int uni_pw_mlp_act_fwd_f64(const void* h, int h_dtype, int M, int Hd, void* a, uni_stream_t stream);
+int uni_pw_mlp_act_bwd_f64(const void* h, int h_dtype, const void* grad_a, int M, int Hd, void* a, void* grad_h, double* grad_b1,
+                           const void* grad_y, int Co, double* grad_b2, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+
 /* What stands around the label propagation in the SOT / VOS TRAINING losses (unicorn/models/unicorn.py:315-337 compute_loss_sot, :339-390
  * compute_loss_vos) for a whole BATCH, without a host synchronisation, a read-back or an allocation; the number of launches does not
  * depend on the data.  The propagation itself is uni_corr_softmax_pv_lse / _bwd on the label rows these entries produce.

@@ -548,6 +548,18 @@ size_t uni_lncf_train_workspace_bytes(int B, int H, int W, int C) { return lncf_
         API(launch_lncf_train_bwd<T>(a, stats, grad_y, grad_x, grad_weight, grad_bias, workspace, workspace_bytes, S(stream)));                    \
     }
 UNI_PAIR(DEF_LNCF_TRAIN)
+size_t uni_pw_mlp_workspace_bytes(int M, int Hd, int Co) { return pw_mlp_workspace_bytes(M, Hd, Co); }
+#define DEF_PW_MLP(SFX, T)                                                                                                                         \
+    int uni_pw_mlp_act_fwd##SFX(const void* h, int h_dtype, int M, int Hd, void* a, uni_stream_t stream) {                                         \
+        UNI_REQUIRE(h && a, "pw_mlp_act_fwd" #SFX ": NULL argument");                                                                              \
+        API(launch_pw_mlp_act_fwd<T>(h, h_dtype, M, Hd, a, S(stream)));                                                                            \
+    }                                                                                                                                              \
+    int uni_pw_mlp_act_bwd##SFX(const void* h, int h_dtype, const void* grad_a, int M, int Hd, void* a, void* grad_h, T* grad_b1,                  \
+                                const void* grad_y, int Co, T* grad_b2, void* workspace, size_t workspace_bytes, uni_stream_t stream) {            \
+        const PwBwdArgs<T> args{h, grad_a, h_dtype, M, Hd, a, grad_h, grad_b1, grad_y, Co, grad_b2};                                               \
+        API(launch_pw_mlp_act_bwd<T>(args, workspace, workspace_bytes, S(stream)));                                                                \
+    }
+UNI_PAIR(DEF_PW_MLP)
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

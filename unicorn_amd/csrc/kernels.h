@@ -386,6 +386,28 @@ template <typename T>
 int launch_lncf_train_fwd(const LncfArgs<T>& a, T* y, T* stats, hipStream_t s);
 template <typename T>
 int launch_lncf_train_bwd(const LncfArgs<T>& a, const T* stats, const T* gy, void* gx, T* gw, T* gb, void* ws, size_t ws_bytes, hipStream_t s);
+// pw_mlp.hip: the point-wise middle of the ConvNeXt block's MLP for TRAINING (convnext.py:46-48; the GEMMs stay with the vendor library): the
+// exact GELU forward a = gelu(h) and a backward that rebuilds a from h: a and / or grad_h = grad_a * gelu'(h) and / or gb1[Hd] = the column sums of
+// the unrounded grad_h, plus gb2[Co] = the column sums of grad_y, fp32 (maps fp32, fp16 or bf16) and fp64, one launch forward and at most three
+// backward, no host read-back, no atomics.  h, a, ga, gh dense [M][Hd], gy dense [M][Co], all of the element type h_dtype names; a may be h and
+// gh may be ga.  Every output may be NULL (not computed).  Hd % 4 == 0, 4 <= Hd <= 8192, the same for Co, 1 <= M < 2^31.  Workspace (with gb1 or
+// gb2 only): pw_mlp_workspace_bytes for fp32, twice that for fp64.
+size_t pw_mlp_workspace_bytes(int M, int Hd, int Co);
+template <typename T>
+struct PwBwdArgs {
+    const void *h, *ga;
+    int h_dtype;                                // 0: the type T, 1 fp16, 2 bf16 (fp32 form only)
+    int M, Hd;
+    void *a, *gh;
+    T* gb1;
+    const void* gy;
+    int Co;
+    T* gb2;
+};
+template <typename T>
+int launch_pw_mlp_act_fwd(const void* h, int h_dtype, int M, int Hd, void* a, hipStream_t s);
+template <typename T>
+int launch_pw_mlp_act_bwd(const PwBwdArgs<T>& a, void* ws, size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

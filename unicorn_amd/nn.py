@@ -22,7 +22,16 @@ drop-path mask is drawn as timm's DropPath draws it, so a seeded run drops the s
 
 fuse_layernorm_cf(model) routes the channels-first LayerNorm between the stages (convnext.py:160-184; after the stem, before each downsample
 convolution, on the stage outputs) through unicorn_amd.ops.layernorm_cf, which reads channels-last memory (the output of block_tail) and
-NCHW memory (the output of the stem convolution) in place and answers in the same layout.  fuse_backbone applies all three."""
+NCHW memory (the output of the stem convolution) in place and answers in the same layout.  fuse_backbone applies all three.
+
+fuse_pw_mlp(model, keep) routes the point-wise middle of the block (convnext.py:46-48)
+
+    x = self.pwconv1(x); x = self.act(x); x = self.pwconv2(x)
+
+through unicorn_amd.ops.pw_mlp, which keeps one hidden map (keep="hidden") or none (keep="input") for the backward where the eager lines keep
+two.  The technique is that of fuse_dwconv_ln: pwconv1 and act get instance-level `forward`s that hand their input on unchanged, pwconv2 one
+that runs the operator with both Linears' parameters, so the block's own forward and fuse_block_tail's work unmodified.  fuse_backbone_mlp
+applies all four."""
 import torch
 
 from . import ops
@@ -239,3 +248,72 @@ def unfuse_layernorm_cf(model):
 def fuse_backbone(model):
     """fuse_convnext + fuse_layernorm_cf -> (blocks whose opening is fused, blocks whose close is fused, channels-first norms fused)"""
     return fuse_convnext(model) + (fuse_layernorm_cf(model),)
+
+
+class _FusedPw:
+    """instance-level `forward` of one of a block's pwconv1, act, pwconv2 (`role` 0, 1, 2): the first two hand their input on unchanged, the
+    third runs ops.pw_mlp with both Linears' parameters"""
+    __slots__ = ("pw1", "act", "pw2", "role", "keep")
+
+    def __init__(self, pw1, act, pw2, role, keep):
+        self.pw1, self.act, self.pw2, self.role, self.keep = pw1, act, pw2, role, keep
+
+    def __call__(self, x):
+        if not (self.pw1.training and self.pw2.training and isinstance(x, torch.Tensor) and x.is_cuda):
+            m = (self.pw1, self.act, self.pw2)[self.role]
+            return type(m).forward(m, x)
+        if self.role < 2:
+            return x
+        return ops.pw_mlp(x, self.pw1.weight, self.pw1.bias, self.pw2.weight, self.pw2.bias, self.keep)
+
+
+def _pw_fusable(block):
+    p1, act, p2 = (getattr(block, n, None) for n in ("pwconv1", "act", "pwconv2"))
+    if not isinstance(p1, torch.nn.Linear) or not isinstance(p2, torch.nn.Linear) or not isinstance(act, torch.nn.GELU):
+        return False
+    if p1.bias is None or p2.bias is None or p1.out_features != p2.in_features or getattr(act, "approximate", "none") != "none":
+        return False
+    if any(v % 4 or not 4 <= v <= ops.PW_MLP_MAX_H for v in (p1.out_features, p2.out_features)):
+        return False
+    return all(isinstance(m.__dict__.get("forward"), (_FusedPw, type(None))) for m in (p1, act, p2))
+
+
+def fuse_pw_mlp(model, keep="hidden"):
+    """Route the point-wise middle `pwconv2(act(pwconv1(x)))` (convnext.py:46-48) of every block of `model` through unicorn_amd.ops.pw_mlp,
+    which keeps one hidden map (keep="hidden") or none (keep="input": the backward repeats pwconv1's GEMM) between forward and backward
+    where the eager lines keep two.  A block is fused when pwconv1 and pwconv2 are nn.Linear with bias, pwconv1.out_features ==
+    pwconv2.in_features, both output widths are multiples of 4 in [4, 8192], act is nn.GELU with approximate == "none", and none of the three
+    modules carries an instance-level forward of somebody else's.  The three modules get instance-level `forward`s: in training mode on a
+    device tensor pwconv1 and act hand their input on UNCHANGED and pwconv2 runs the operator on both Linears' parameters; otherwise each
+    calls its module's own forward.  So a forward hook on pwconv1 or act of a fused block sees the un-transformed tensor (the LayerNorm
+    output), and the block is expected to run pwconv1 -> act -> pwconv2 back to back.  Module tree, parameter names and state_dict() stay as
+    they were; copy.deepcopy(model) gives a copy that uses the copy's parameters.  Returns the number of blocks that are fused (blocks fused
+    earlier are counted; they take the `keep` given now)."""
+    if keep not in ops.PW_MLP_KEEP:
+        raise ops.L.UnicornHipError("fuse_pw_mlp: keep = %r is not one of %s" % (keep, ", ".join(repr(k) for k in ops.PW_MLP_KEEP)))
+    n = 0
+    for block in model.modules():
+        if not _pw_fusable(block):
+            continue
+        mods = (block.pwconv1, block.act, block.pwconv2)
+        for role, m in enumerate(mods):
+            m.forward = _FusedPw(*mods, role, keep)
+        n += 1
+    return n
+
+
+def unfuse_pw_mlp(model):
+    """Remove what fuse_pw_mlp set; returns the number of blocks restored."""
+    n = 0
+    for m in model.modules():
+        f = m.__dict__.get("forward")
+        if isinstance(f, _FusedPw):
+            del m.__dict__["forward"]
+            n += f.role == 2
+    return n
+
+
+def fuse_backbone_mlp(model, keep="hidden"):
+    """fuse_backbone + fuse_pw_mlp -> (blocks whose opening is fused, blocks whose close is fused, channels-first norms fused, blocks whose
+    point-wise middle is fused): a fused block then runs no eager point-wise line"""
+    return fuse_backbone(model) + (fuse_pw_mlp(model, keep),)

@@ -1198,6 +1198,155 @@ def layernorm_cf(x, weight, bias, eps=1e-6):
     return LayerNormCFFunction.apply(x, weight.contiguous(), bias.contiguous(), float(eps))
 
 
+PW_MLP_MAX_H = 4 * TRAIN_MAX_C
+PW_MLP_KEEP = ("hidden", "input")
+
+
+def _pw_sum_dtype(cd):
+    """the dtype of the bias sums, which names the library form: fp64 for fp64 maps, fp32 for fp32 and half maps"""
+    return torch.float64 if cd == torch.float64 else torch.float32
+
+
+def _pw_act_bwd(dev, cd, M, Hd, Co, h, grad_a, a, grad_h, grad_b1, grad_y, grad_b2):
+    """uni_pw_mlp_act_bwd on (M, Hd) / (M, Co) maps of the dtype `cd` on the current device `dev`; every tensor may be None"""
+    fn, name = _entry("uni_pw_mlp_act_bwd", _pw_sum_dtype(cd))
+    ws, nws = None, 0
+    if grad_b1 is not None or grad_b2 is not None:
+        nws = L.lib().uni_pw_mlp_workspace_bytes(M, Hd, Co) * _ws_factor(_pw_sum_dtype(cd))
+        if nws == 0:
+            raise L.UnicornHipError("pw_mlp: shape M=%d Hd=%d Co=%d is outside the limits of uni_pw_mlp_act_bwd (include/unicorn_hip.h)" % (M, Hd, Co))
+        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+    L.check(fn(L.ptr(h), _STORE_DTYPE[cd], L.ptr(grad_a), M, Hd, L.ptr(a), L.ptr(grad_h), L.ptr(grad_b1), L.ptr(grad_y), Co, L.ptr(grad_b2),
+               L.ptr(ws), nws, L.stream_ptr()), name)
+
+
+class PwMlpFunction(torch.autograd.Function):
+    """`pwconv2(act(pwconv1(t)))` of a ConvNeXt block (convnext.py:46-48) with the GELU in HIP and the hidden maps rebuilt in the backward:
+    apply(t (..., C), w1 (Hd, C), b1 (Hd,), w2 (Co, Hd), b2 (Co,), keep) -> y (..., Co); ops.pw_mlp checks the arguments.  The two GEMMs of the
+    forward are the addmm calls F.linear makes.  The compute dtype is fp64 for fp64 tensors, else fp32, and under torch.autocast("cuda") the
+    autocast dtype: t and the parameters are cast to it here and autocast is switched off for the Function's own lines, so forward and
+    backward use the same dtypes.
+      keep == "hidden"  saves t (the cast copy under autocast), w1, w2 and h = pwconv1(t); a = gelu(h) is a temporary of the forward and is
+                        rebuilt by the backward into a temporary.  h is never written.
+      keep == "input"   a is written over h, nothing of M x Hd elements survives the forward; saves t, w1, b1 and w2.  The backward repeats the
+                        first addmm and works in place on its own buffers.
+    Only what autograd asks for is computed.  No host synchronisation, one writer per element: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, t, w1, b1, w2, b2, keep):
+        Hd, Cc = w1.shape
+        Co = w2.shape[0]
+        if torch.is_autocast_enabled("cuda"):
+            cd = torch.get_autocast_dtype("cuda")
+        else:
+            cd = torch.float64 if t.dtype == torch.float64 else torch.float32
+        M = t.numel() // Cc
+        ctx.keep, ctx.cd, ctx.t_shape, ctx.t_dtype, ctx.empty = keep, cd, t.shape, t.dtype, M == 0
+        if M == 0:
+            ctx.save_for_backward(w1, b1, w2, b2)
+            return torch.empty(t.shape[:-1] + (Co,), device=t.device, dtype=cd)
+        with torch.autocast("cuda", enabled=False), torch.cuda.device(t.device):
+            t2 = t.detach().reshape(M, Cc).to(cd).contiguous()
+            h = torch.addmm(b1.detach().to(cd), t2, w1.detach().to(cd).t())
+            a = h if keep == "input" else torch.empty_like(h)
+            fn, name = _entry("uni_pw_mlp_act_fwd", _pw_sum_dtype(cd))
+            L.check(fn(L.ptr(h), _STORE_DTYPE[cd], M, Hd, L.ptr(a), L.stream_ptr()), name)
+            y = torch.addmm(b2.detach().to(cd), a, w2.detach().to(cd).t())
+        if keep == "input":
+            ctx.save_for_backward(t2, w1, b1, w2)
+        else:
+            ctx.save_for_backward(t2, w1, w2, h)
+        ctx.b_dtypes = (b1.dtype, b2.dtype)
+        return y.reshape(t.shape[:-1] + (Co,))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        need = ctx.needs_input_grad
+        cd = ctx.cd
+        if ctx.empty:
+            w1, b1, w2, b2 = ctx.saved_tensors
+            z = torch.zeros_like
+            return (torch.zeros(ctx.t_shape, device=w1.device, dtype=ctx.t_dtype) if need[0] else None, z(w1) if need[1] else None,
+                    z(b1) if need[2] else None, z(w2) if need[3] else None, z(b2) if need[4] else None, None)
+        if ctx.keep == "input":
+            t2, w1, b1, w2 = ctx.saved_tensors
+            h = None
+        else:
+            t2, w1, w2, h = ctx.saved_tensors
+        M, Hd, Co, dev = t2.shape[0], w1.shape[0], w2.shape[0], t2.device
+        need_ga, need_gh = need[0] or need[1] or need[2], need[0] or need[1]
+        g_t = g_w1 = g_b1 = g_w2 = g_b2 = a = ga = None
+        with torch.autocast("cuda", enabled=False), torch.cuda.device(dev):
+            gy = grad_y.reshape(M, Co).to(cd).contiguous()
+            if need_ga or need[3]:
+                if h is None:                                                # keep == "input": h again, and a over it
+                    h = torch.addmm(b1.detach().to(cd), t2, w1.detach().to(cd).t())
+                    a = h if need[3] else None
+                elif need[3]:
+                    a = torch.empty_like(h)                                  # keep == "hidden": h is a saved tensor and is not written
+            else:
+                h = None
+            if need_ga:
+                ga = torch.mm(gy, w2.detach().to(cd))
+            gh = ga if need_gh else None                                     # grad_h over grad_a, a buffer of this call
+            if need[2]:
+                g_b1 = torch.empty(Hd, device=dev, dtype=_pw_sum_dtype(cd))
+            if need[4]:
+                g_b2 = torch.empty(Co, device=dev, dtype=_pw_sum_dtype(cd))
+            _pw_act_bwd(dev, cd, M, Hd, Co, h, ga, a, gh, g_b1, gy if need[4] else None, g_b2)
+            if need[3]:
+                g_w2 = torch.mm(gy.t(), a).to(w2.dtype)
+            if need[1]:
+                g_w1 = torch.mm(gh.t(), t2).to(w1.dtype)
+            if need[0]:
+                g_t = torch.mm(gh, w1.detach().to(cd)).reshape(ctx.t_shape).to(ctx.t_dtype)
+            if need[2]:
+                g_b1 = g_b1.to(ctx.b_dtypes[0])
+            if need[4]:
+                g_b2 = g_b2.to(ctx.b_dtypes[1])
+        return g_t, g_w1, g_b1, g_w2, g_b2, None
+
+
+def pw_mlp(t, w1, b1, w2, b2, keep="hidden"):
+    """`pwconv2(act(pwconv1(t)))` of a ConvNeXt block (convnext.py:46-48) as one operator, equal in value and in all five gradients to
+    F.linear(F.gelu(F.linear(t, w1, b1)), w2, b2) (the exact erf GELU, nn.GELU()'s default):
+      t        (..., C)
+      w1, b1   (Hd, C), (Hd,): pwconv1;  w2, b2  (Co, Hd), (Co,): pwconv2.  Hd % 4 == 0, 4 <= Hd <= 8192, the same for Co
+    All five fp32, or all fp64 for checks; under torch.autocast("cuda") any floating-point dtypes: t and the parameters are cast to the
+    autocast dtype as F.linear casts them, and y is half as it is in eager.  Returns y (..., Co) in the compute dtype.  Gradients come back in
+    the dtypes of their tensors.  The GEMMs are the vendor library's (the very addmm calls of F.linear, so h has eager's bits); the GELU, its
+    derivative and both bias sums are HIP (uni_pw_mlp_act_fwd / _bwd).
+      keep="hidden"  autograd keeps t (the half copy under autocast), w1, w2 and h: one (M, Hd) map instead of eager's two (h and gelu(h)).
+                     The backward rebuilds gelu(h) in one point-wise pass.
+      keep="input"   autograd keeps t, w1, b1 and w2: NO (M, Hd) map.  The backward repeats the first GEMM.
+    An empty t returns an empty result (zero parameter gradients) without a library call.  No host synchronisation."""
+    names = ("t", "w1", "b1", "w2", "b2")
+    ts = (t, w1, b1, w2, b2)
+    _check_tensors("pw_mlp", names, ts)
+    if keep not in PW_MLP_KEEP:
+        raise L.UnicornHipError("pw_mlp: keep = %r is not one of %s" % (keep, ", ".join(repr(k) for k in PW_MLP_KEEP)))
+    if t.dim() < 1 or w1.dim() != 2 or w2.dim() != 2 or w1.shape[1] != t.shape[-1] or w2.shape[1] != w1.shape[0]:
+        raise L.UnicornHipError("pw_mlp: shapes %s, %s, %s do not fit t (..., C), w1 (Hd, C), w2 (Co, Hd)"
+                                % (tuple(t.shape), tuple(w1.shape), tuple(w2.shape)))
+    Hd, Co = w1.shape[0], w2.shape[0]
+    _check_channel_vecs("pw_mlp", ("b1",), (b1,), Hd)
+    _check_channel_vecs("pw_mlp", ("b2",), (b2,), Co)
+    for n, v in (("Hd", Hd), ("Co", Co)):
+        if v % 4 or not 4 <= v <= PW_MLP_MAX_H:
+            raise L.UnicornHipError("pw_mlp: %s = %d is outside %s %% 4 == 0, 4 <= %s <= %d" % (n, v, n, n, PW_MLP_MAX_H))
+    if t.shape[-1] == 0 or t.numel() // max(t.shape[-1], 1) >= 1 << 31:
+        raise L.UnicornHipError("pw_mlp: t of shape %s is outside C >= 1 with fewer than 2^31 rows" % (tuple(t.shape),))
+    if t.is_cuda and torch.is_autocast_enabled("cuda"):
+        if not all(x.is_floating_point() for x in ts):
+            raise L.UnicornHipError("pw_mlp: dtypes %s: floating-point tensors are needed" % ", ".join(str(x.dtype) for x in ts))
+    elif t.dtype not in _F64_SFX or any(x.dtype != t.dtype for x in ts):
+        raise L.UnicornHipError("pw_mlp: dtypes %s unsupported (all fp32 or all fp64; half tensors only under torch.autocast)"
+                                % ", ".join(str(x.dtype) for x in ts))
+    _check_one_device("pw_mlp", ts)
+    return PwMlpFunction.apply(t, w1, b1, w2, b2, keep)
+
+
 def _prop_ws(dev, B, Kc, Q):
     need = L.lib().uni_prop_workspace_bytes(B, Kc, Q)
     if need == 0:
