@@ -1,10 +1,12 @@
-"""The plan lists of the three ConvNeXt training operators (tests/train_plans.py) without a GPU: the lists are well formed and every class
-is a string the launchers' own tag formats can print; the restated plan arithmetic gives exactly the lists; the fp32 yardstick of the
-restatements is positive at the widths tests/test_train_plans_gpu.py runs, so its 4 x bound never collapses to "<= 0"; and a lane that reads
-the wrong vector would miss that bound by more than 100 x."""
+"""The plan lists of the ConvNeXt training operators (tests/train_plans.py) without a GPU: the host check of the launch plans
+(tools/train_plan_check.cpp over csrc/train_plan.h) holds over its whole domain; the lists are well formed and every class is a string the
+header's own formatters print; the plans of the host code give exactly the lists; the fp32 yardstick of the restatements is positive at the
+widths tests/test_train_plans_gpu.py runs, so its 4 x bound never collapses to "<= 0"; and a lane that reads the wrong vector would miss that
+bound by more than 100 x."""
 import functools
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -15,18 +17,32 @@ import lncf_ref as RL
 import train_plans as P
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "unicorn_amd", "csrc")
-ENAMES = ("f32", "f16", "bf16", "f64")           # train_ename (csrc/train_ops.h)
+ENAMES = ("f32", "f16", "bf16", "f64")           # train_ename (csrc/train_plan.h)
 
 
-def _note_patterns(source, operator):
-    """the uni_variant_note format strings of `operator` in a launcher's source, each as a regular expression over whole tags"""
-    text = open(os.path.join(CSRC, source)).read()
-    pats = []
-    for fmt in re.findall(r'uni_variant_note\("(%s [^"]*)"' % operator, text):
-        rx = re.escape(fmt).replace("%s", "(?:%s)" % "|".join(ENAMES + ("fwd", "bwd"))).replace("%d", r"\d+")
-        pats.append(re.compile("^" + rx + "$"))
-    assert pats, (source, operator)
-    return pats
+def test_the_plans_hold_over_the_whole_admitted_domain():
+    """block size, grid, counters, lane mappings, partials inside the workspace, LDS and the size functions, at every point of the domain;
+    and each condition refuses a deliberately wrong plan"""
+    P.plan_list()                               # fails by name where the program was not built
+    r = subprocess.run([P.PLAN_CHECK], capture_output=True, text=True, timeout=120)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "train_plan_check: OK" in r.stdout and "FAIL" not in r.stdout
+    assert re.search(r"each condition bites: [1-9]\d* deliberately wrong plans refused", r.stdout)
+
+
+def test_the_limits_of_ops_are_the_limits_of_the_header():
+    from unicorn_amd import ops
+    limits = P.plan_list()[1]
+    assert ops.TRAIN_MAX_C == limits["TRAIN_MAX_C"] == P.C_MAX and ops.PW_MLP_MAX_H == limits["PW_MAX_H"]
+    assert limits["TRAIN_ROWS"] == 1024 and limits["PW_ROWS"] == 256
+
+
+def _printable(op):
+    """every plan class the formatter of `op` in csrc/train_plan.h writes over the whole domain (train_plan_check --list)"""
+    out = {cls for (o, _, _, _), (cls, _) in P.plan_list()[0].items() if o == op}
+    assert out, op
+    return out
 
 
 def test_expected_is_well_formed():
@@ -43,29 +59,44 @@ def test_expected_is_well_formed():
 
 
 def test_every_class_is_a_tag_the_launchers_can_print():
-    """a class, put back between the kernel name and the need flags, matches a uni_variant_note format string of its launcher, with a dtype
-    of train_ename and a layout the launcher has"""
-    lncf, dwln, bt = _note_patterns("lncf_train.hip", "lncf_train"), _note_patterns("dwln_train.hip", "dwln_train"), _note_patterns("block_tail.hip", "block_tail")
+    """a class is one the header's formatter prints (the launchers put it between the kernel name and the need flags), with a dtype of
+    train_ename and a layout the launcher has; and plan_class finds it again in the whole tag"""
+    lncf, dwln, bt = _printable("lncf"), _printable("dwln"), _printable("block_tail")
     for cls in P.EXPECTED["lncf"]:
         for kind, flags in (("fwd", "gx=0 gwb=0"), ("bwd", "gx=1 gwb=1")):
             tag = "lncf_train %s_%s %s" % (kind, cls, flags)
-            assert any(p.match(tag) for p in lncf), tag
+            assert cls in lncf, tag
             assert P.plan_class(tag) == cls and P.strip_flags(tag) == "lncf_train %s_%s" % (kind, cls)
         assert re.match(r"^(cl|nchw)<(%s)," % "|".join(ENAMES), cls), cls
     for cls in P.EXPECTED["dwln"]:
         for tag in ("dwln_train fwd%s" % cls, "dwln_train bwd_a%s du=1 gb=1" % cls, "dwln_train bwd_dx%s" % cls):
-            assert any(p.match(tag) for p in dwln), tag
+            assert cls in dwln, tag
             assert P.plan_class(tag) == cls
         assert re.match(r"^<(f32|f64),", cls), cls
     for layout in ("cl", "nchw"):
         for dt in ENAMES:
             for C in P.WIDTHS_BT:
                 tag = "block_tail bwd_%s gy=1 gg=1" % P.bt_class(layout, dt, C)
-                assert any(p.match(tag) for p in bt), tag
+                assert P.bt_class(layout, dt, C) in bt and re.match(r"^block_tail bwd_(cl<(%s),V=[48]>|nchw<(%s)>) " % (("|".join(ENAMES),) * 2), tag), tag
                 assert P.plan_class(tag) == P.bt_class(layout, dt, C)
     for tag in ("lncf_train reduce<f32>", "block_tail reduce<f64>", "dwln_train reduce<f32> dw=1 gb=1", "dwln_train bwd_dw<f32> slen=65"):
         assert P.plan_class(tag) is None, tag
     assert P.group({8: "a", 4: "a", 12: "b"}) == {"a": [4, 8], "b": [12]} and P.ends([4, 8, 12]) == [4, 12] and P.ends([4]) == [4]
+    # the launchers format no plan class of their own: the tag text is stated once, in the header
+    for unit in ("lncf_train.hip", "dwln_train.hip", "block_tail.hip", "pw_mlp.hip"):
+        text = open(os.path.join(CSRC, unit)).read()
+        assert "_plan_class(" in text and not re.search(r'uni_variant_note\("[^"]*(V=|PXT=|NV=|regs=|stream=)', text), unit
+
+
+def test_the_block_tail_widths_are_what_their_comment_says():
+    """the PP and idle-thread facts next to train_plans.WIDTHS_BT, for fp32 y in channels-last memory (4 channels per lane)"""
+    facts = {384: (5, 512, 32), 768: (2, 384, 0), 2048: (1, 512, 0), 1000: (2, 512, 12), 500: (4, 512, 12), 2044: (1, 512, 1)}      # PP, block, idle
+    for C, (pp, block, idle) in facts.items():
+        assert C in P.WIDTHS_BT
+        got = P.plan_extra("block_tail", "cl", "f32", C)
+        assert (got["PP"], got["block"], got["block"] - got["PP"] * (C // 4)) == (pp, block, idle), (C, got)
+    assert 2048 // 4 == 512                                                                  # CG = 512 at the widest C
+    assert -(-1000 // 64) == 15 + 1 and 1000 % 64 and -(-2044 // 64) == 31 + 1 and 2044 % 64      # NCHW: a partial channel tile behind 15 and 31 whole ones
 
 
 def _predicted_classes(op, combos):

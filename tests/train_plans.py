@@ -1,19 +1,25 @@
-"""The launch plans of the three ConvNeXt training operators (ops.layernorm_cf / csrc/lncf_train.hip, ops.dwconv7_ln / csrc/dwln_train.hip,
-ops.block_tail / csrc/block_tail.hip), written down as explicit lists, and the maps their parity cases run on.
+"""The launch plans of the ConvNeXt training operators (ops.layernorm_cf / csrc/lncf_train.hip, ops.dwconv7_ln / csrc/dwln_train.hip,
+ops.block_tail / csrc/block_tail.hip, ops.pw_mlp / csrc/pw_mlp.hip), written down as explicit lists, and the maps their parity cases run on.
 
 A launcher's variant tag (uni_variant_trace, include/unicorn_hip.h) reads `<operator> <fwd|bwd...><plan> <need flags>`, for instance
 `lncf_train bwd_cl<f16,V=8,NV=3> G=4 gx=1 gwb=1`.  The PLAN CLASS of a tag is the part between the kernel name and the need flags:
 `cl<f16,V=8,NV=3> G=4`.  It names the template instantiation and the lane mapping, and the forward and the backward of one call carry the
-same one.  EXPECTED lists, per operator, every plan class the host code can pick for C = 4, 8, ..., 2048 (lncf_cl_plan / lncf_launch,
-dwln_plan).  tests/test_train_plans_gpu.py sweeps every C on the device and demands that the classes found are EXPECTED, in both
+same one.  EXPECTED lists, per operator, every plan class the host code can pick for C = 4, 8, ..., 2048 (lncf_plan, dwln_plan in
+csrc/train_plan.h).  tests/test_train_plans_gpu.py sweeps every C on the device and demands that the classes found are EXPECTED, in both
 directions -- a retuned plan function shows up as a diff of these lists, an instantiation nobody can reach as well -- and then runs the
 smallest and the largest C of every class against the operator's restatement.  block_tail's tag does not carry its plan (PP = 512 / (C / V)
 is a kernel argument, not a template argument), so it has an explicit list of widths instead.
 
-Data and small helpers only: no GPU work, importable without a device."""
-import re
+predicted() and bt_class() do not restate the plans: they answer from what the host code itself prints, `tools/build/train_plan_check --list`
+(tools/train_plan_check.cpp over csrc/train_plan.h, the header the launchers read).
 
-C_STEP, C_MAX = 4, 2048                     # train_shape_ok (csrc/train_ops.h): C % 4 == 0, 4 <= C <= TRAIN_MAX_C
+Data and small helpers only: no GPU work, importable without a device."""
+import functools
+import os
+import re
+import subprocess
+
+C_STEP, C_MAX = 4, 2048                     # train_shape_ok (csrc/train_plan.h): C % 4 == 0, 4 <= C <= TRAIN_MAX_C
 SWEEP_C = tuple(range(C_STEP, C_MAX + 1, C_STEP))
 
 # (N, H, W) of the parity cases.  21 pixels per image and 42 in all: neither is a multiple of any pixels-per-block value of the channels-last
@@ -58,23 +64,34 @@ FIRST_RUN = {
 }
 
 
+PLAN_CHECK = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "build", "train_plan_check")
+
+
+@functools.lru_cache(maxsize=None)
+def plan_list():
+    """`train_plan_check --list`, run once: ({(op, layout, dt, C): (plan class, {"PP" | "block" | "L": value})}, {limit: value}); op is lncf,
+    block_tail, dwln or pw_mlp, layout is "" for the two operators that have one layout only"""
+    if not os.path.exists(PLAN_CHECK):
+        raise AssertionError("tools/build/train_plan_check is missing: run __graft_entry__.build() (csrc/build.sh builds it)")
+    r = subprocess.run([PLAN_CHECK, "--list"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    plans, limits = {}, {}
+    for line in r.stdout.splitlines():
+        head, *rest = line.split(" | ")
+        if head == "limits":
+            limits = {k: int(v) for k, v in (kv.split("=") for kv in rest[0].split())}
+            continue
+        op, layout, dt, C = head.split()
+        extra = {k: int(v) for k, v in (kv.split("=") for kv in rest[1].split())} if len(rest) > 1 else {}
+        key = (op, "" if layout == "-" else layout, dt, int(C))
+        assert key not in plans, key
+        plans[key] = (rest[0], extra)
+    return plans, limits
+
+
 def predicted(op, layout, dt, C):
-    """The plan class the lists above were written from, by the arithmetic of lncf_cl_plan / lncf_launch / dwln_plan restated: it picks the
-    widths of the CPU checks and says where a class begins and ends.  The sweep on the device is the authority, not this."""
-    if op == "dwln":
-        wps = (C // 4 + 63) // 64
-        return "<%s,PXT=%d> wps=%d NS=%d" % (dt, 2 if dt == "f64" else 8, wps, 512 // (64 * wps))
-    if layout == "nchw":
-        return "nchw<%s,%s>" % (dt, "regs=16" if C <= 128 else "regs=32" if C <= 256 and dt != "f64" else "stream=8")
-    V = 8 if dt in ("f16", "bf16") and C % 8 == 0 else 4
-    best = None
-    for nv in (1, 2, 3, 4, 6, 8):
-        lg = 0
-        while (nv << lg) < C // V:
-            lg += 1
-        if lg <= 6 and (best is None or (nv << lg) < best[0]):
-            best = (nv << lg, nv, 1 << lg)
-    return "cl<%s,V=%d,NV=%d> G=%d" % (dt, V, best[1], best[2])
+    """The plan class the host code (csrc/train_plan.h) picks: it picks the widths of the CPU checks and says where a class begins and ends"""
+    return plan_list()[0][(op, layout, dt, C)][0]
 
 
 _FLAGS = re.compile(r"(?: (?:gx|gwb|du|gb|gy|gg)=\d+)+$")
@@ -112,9 +129,12 @@ def ends(cs):
 
 def bt_class(layout, dt, C):
     """the plan part of the block_tail tag at width C: V = 8 for half y where C allows it"""
-    if layout == "nchw":
-        return "nchw<%s>" % dt
-    return "cl<%s,V=%d>" % (dt, 8 if dt in ("f16", "bf16") and C % 8 == 0 else 4)
+    return plan_list()[0][("block_tail", layout, dt, C)][0]
+
+
+def plan_extra(op, layout, dt, C):
+    """what the list says next to the class: PP and block for block_tail, L for pw_mlp"""
+    return plan_list()[0][(op, layout, dt, C)][1]
 
 
 def zero_one_vector(x, C):

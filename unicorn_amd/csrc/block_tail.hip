@@ -22,10 +22,6 @@
 #include "kernels.h"
 #include "train_ops.h"
 
-constexpr int BT_TILE = 64;                     // NCHW path: pixels and channels of a tile
-template <int V>
-struct BtU { static constexpr int value = V == 8 ? 2 : 4; };      // channels-last path: steps of PP pixels whose loads are in flight together
-
 template <typename T>
 struct BtK {                                    // kernel arguments (by value)
     const void* y;
@@ -217,29 +213,23 @@ __global__ __launch_bounds__(1024) void bt_reduce_kernel(const T* __restrict__ p
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-size_t block_tail_workspace_bytes(int B, int H, int W, int C) { return train_shape_ok(B, H, W, C) ? (size_t)4 * TRAIN_ROWS * C : 0; }
+size_t block_tail_workspace_bytes(int B, int H, int W, int C) { return bt_plan_workspace_bytes(B, H, W, C); }
 
-// launches mode MODE with the element type YT of y; *rows = the rows of partials it writes
+// launches mode MODE with the element type YT of y as bt_plan (train_plan.h) says; *rows = the rows of partials it writes
 template <typename T, typename YT, int MODE>
 static void bt_launch(const BtArgs<T>& a, const BtK<T>& k, int* rows, hipStream_t s) {
-    const char* what = MODE ? "bwd" : "fwd";
-    const char* yn = train_ename(a.y_dtype, sizeof(T) == 8);
-    if (a.nchw) {
-        const unsigned tpi = (unsigned)cdiv(k.HW, BT_TILE), ntiles = (unsigned)a.B * tpi;          // <= B H W
-        *rows = train_rows(ntiles);
-        uni_variant_note("block_tail %s_nchw<%s> gy=%d gg=%d", what, yn, k.gy != nullptr, k.part != nullptr);
-        hipLaunchKernelGGL((bt_nchw_kernel<T, YT, MODE>), dim3(*rows, cdiv(a.C, BT_TILE)), dim3(256), 0, s, k, tpi, ntiles);
+    const BtPlan q = bt_plan(a.B, a.H, a.W, a.C, sizeof(YT), a.nchw != 0);
+    *rows = q.rows;
+    char cls[32] = "";
+    if (train_tracing()) bt_plan_class(q, train_ename(a.y_dtype, sizeof(T) == 8), cls, sizeof(cls));
+    uni_variant_note("block_tail %s_%s gy=%d gg=%d", MODE ? "bwd" : "fwd", cls, k.gy != nullptr, k.part != nullptr);
+    if (q.nchw) {
+        hipLaunchKernelGGL((bt_nchw_kernel<T, YT, MODE>), dim3(q.grid_x, q.grid_y), dim3(q.block), 0, s, k, q.per_image, q.units);
         return;
     }
-    train_with_vwidth<YT>(a.C, [&](auto vtag) {
+    train_with_vwidth<YT>(q.V, [&](auto vtag) {
         constexpr int V = decltype(vtag)::value;
-        const int CG = a.C / V, PP = 512 / CG;                      // CG <= 512
-        const int chunk = BtU<V>::value * PP;                       // pixels of a chunk
-        const unsigned cpi = (unsigned)(((long long)k.HW + chunk - 1) / chunk);
-        const unsigned nchunks = (unsigned)a.B * cpi;               // <= B H W
-        *rows = train_rows(nchunks);
-        uni_variant_note("block_tail %s_cl<%s,V=%d> gy=%d gg=%d", what, yn, V, k.gy != nullptr, k.part != nullptr);
-        hipLaunchKernelGGL((bt_cl_kernel<T, YT, V, MODE>), dim3(*rows), dim3((PP * CG + 63) / 64 * 64), 0, s, k, CG, PP, cpi, nchunks);
+        hipLaunchKernelGGL((bt_cl_kernel<T, YT, V, MODE>), dim3(q.grid_x), dim3(q.block), 0, s, k, q.CG, q.PP, q.per_image, q.units);
     });
 }
 

@@ -45,6 +45,12 @@ if [ ! -f ../../tools/build/tile_index_check ] || [ ../../tools/tile_index_check
   g++ -O2 -std=c++17 -Wall -Wextra ../../tools/tile_index_check.cpp -o ../../tools/build/tile_index_check
   echo "built tools/build/tile_index_check"
 fi
+# host check of the training operators' launch plans in train_plan.h (tools/train_plan_check.cpp; tests/test_train_plans_cpu.py runs it and
+# tests/train_plans.py reads its --list): plain C++ and fatal, like the one above
+if [ ! -f ../../tools/build/train_plan_check ] || [ ../../tools/train_plan_check.cpp -nt ../../tools/build/train_plan_check ] || [ train_plan.h -nt ../../tools/build/train_plan_check ]; then
+  g++ -O2 -std=c++17 -Wall -Wextra ../../tools/train_plan_check.cpp -o ../../tools/build/train_plan_check
+  echo "built tools/build/train_plan_check"
+fi
 # standalone measurement program (tools/feed_probe.hip: which path feeds a CU; profiles/r05_feed_probe.txt) -- not part of the library:
 # built last and non-fatally (a probe that does not compile on another ROCm must not leave the libraries unbuilt)
 mkdir -p ../../tools/build

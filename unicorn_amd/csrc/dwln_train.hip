@@ -29,10 +29,6 @@ __device__ __forceinline__ T dv4_sum(dv4<T> v) {
     return (v[0] + v[1]) + (v[2] + v[3]);
 }
 
-constexpr int DWLN_DW_STRIP = 128;             // pass B (weights): longest strip a wave walks
-template <typename T>
-struct DwlnPx { static constexpr int value = sizeof(T) == 4 ? 8 : 2; };      // pixels of a strip per lane
-
 template <typename T>
 struct DwlnK {                                  // kernel arguments (by value)
     const T* in;                                // x (modes 0, 1) or du (mode 2)
@@ -265,46 +261,11 @@ __global__ __launch_bounds__(256) void dwln_dw_kernel(const T* __restrict__ x, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-struct DwlnPlan {
-    int CG, CGp, NS, threads;                   // conv kernels: lanes of a strip, padded to whole waves; strips per block
-    int segs, nstrips, nsb, RA;                 // strips of PXT pixels per row, in all, blocks of NS strips, blocks of pass A
-    int slen, segs_w, nstrips_w, RB, NCT;       // pass B (weights): strip length, strips per row, in all, blocks per channel tile, channel tiles
-    size_t off_pa, off_pb, elems;               // workspace (elements): du at 0, partials of pass A, of pass B
-};
-static bool dwln_plan(int B, int H, int W, int C, int pxt, DwlnPlan& q) {
-    if (!train_shape_ok(B, H, W, C)) return false;
-    const long long M = (long long)B * H * W;
-    q.CG = C / 4;
-    q.CGp = (q.CG + 63) / 64 * 64;
-    q.NS = 512 / q.CGp;
-    q.threads = q.NS * q.CGp;
-    q.segs = cdiv(W, pxt);
-    q.nstrips = B * H * q.segs;
-    q.nsb = cdiv(q.nstrips, q.NS);
-    q.RA = train_rows(q.nsb);                   // pass A: blocks = rows of dgamma / dbeta partials
-    q.segs_w = cdiv(W, DWLN_DW_STRIP);
-    q.slen = cdiv(W, q.segs_w);
-    q.segs_w = cdiv(W, q.slen);
-    q.nstrips_w = B * H * q.segs_w;
-    q.RB = cdiv(q.nstrips_w, 4);
-    q.NCT = cdiv(C, 64);
-    auto up = [](size_t n) { return (n + 63) / 64 * 64; };
-    q.off_pa = up((size_t)M * C);
-    q.off_pb = q.off_pa + up((size_t)q.RA * 2 * C);
-    q.elems = q.off_pb + up((size_t)q.RB * 50 * C);
-    return true;
-}
-// counted in fp32 elements (the fp64 launchers need twice the bytes) from the plan of the fp64 form: it has the fewer pixels per strip, so
-// the more blocks in pass A, and one formula serves both
-size_t dwln_train_workspace_bytes(int B, int H, int W, int C) {
-    DwlnPlan q;
-    static_assert(DwlnPx<double>::value <= DwlnPx<float>::value, "the workspace is sized by the fp64 plan");
-    return dwln_plan(B, H, W, C, DwlnPx<double>::value, q) ? 4 * q.elems : 0;
-}
+size_t dwln_train_workspace_bytes(int B, int H, int W, int C) { return dwln_plan_workspace_bytes(B, H, W, C); }
 
 template <typename T>
 static int dwln_check(const char* what, const DwlnArgs<T>& a, DwlnPlan& q) {
-    if (!dwln_plan(a.B, a.H, a.W, a.C, DwlnPx<T>::value, q)) return train_shape_refused(what, a.B, a.H, a.W, a.C);
+    if (!dwln_plan(a.B, a.H, a.W, a.C, sizeof(T) == 8, q)) return train_shape_refused(what, a.B, a.H, a.W, a.C);
     UNI_REQUIRE(aligned16(a.x) && aligned16(a.w) && aligned16(a.bias) && aligned16(a.gamma), "%s: a pointer is not 16-byte aligned", what);
     return 0;
 }
@@ -319,7 +280,9 @@ int launch_dwln_train_fwd(const DwlnArgs<T>& a, T* y, T* stats, hipStream_t s) {
     UNI_REQUIRE(a.eps > 0, "dwln_train_fwd: eps %g is not positive", a.eps);
     DwlnK<T> k{a.x, a.w, a.bias, a.gamma, a.beta, nullptr, nullptr, y, stats, nullptr, (T)a.eps,
                a.H, a.W, a.C, q.CG, q.CGp, q.NS, q.segs, q.nstrips, 0, 0};
-    uni_variant_note("dwln_train fwd<%s,PXT=%d> wps=%d NS=%d", tn, PXT, q.CGp / 64, q.NS);
+    char cls[48] = "";
+    if (train_tracing()) dwln_plan_class(q, tn, cls, sizeof(cls));
+    uni_variant_note("dwln_train fwd%s", cls);
     hipLaunchKernelGGL((dwln_conv_kernel<T, PXT, 0>), dim3(q.nsb), dim3(q.threads), 0, s, k);
     UNI_CHECK_HIP(hipGetLastError());
     return 0;
@@ -345,12 +308,14 @@ int launch_dwln_train_bwd(const DwlnArgs<T>& a, const T* stats, const T* gy, T* 
     T* part_b = du + q.off_pb;
     DwlnK<T> k{a.x, a.w, a.bias, a.gamma, nullptr, gy, stats, du, nullptr, part_a, T(0),
                a.H, a.W, a.C, q.CG, q.CGp, q.NS, q.segs, q.nstrips, (int)need_du, (int)need_gb};
-    uni_variant_note("dwln_train bwd_a<%s,PXT=%d> wps=%d NS=%d du=%d gb=%d", tn, PXT, q.CGp / 64, q.NS, (int)need_du, (int)need_gb);
-    hipLaunchKernelGGL((dwln_conv_kernel<T, PXT, 1>), dim3(q.RA), dim3(q.threads), need_gb ? 2 * a.C * sizeof(T) : 0, s, k);
+    char cls[48] = "";
+    if (train_tracing()) dwln_plan_class(q, tn, cls, sizeof(cls));
+    uni_variant_note("dwln_train bwd_a%s du=%d gb=%d", cls, (int)need_du, (int)need_gb);
+    hipLaunchKernelGGL((dwln_conv_kernel<T, PXT, 1>), dim3(q.RA), dim3(q.threads), need_gb ? q.lds_a : 0, s, k);
     if (gx) {
         DwlnK<T> kx{du, a.w, nullptr, nullptr, nullptr, nullptr, nullptr, gx, nullptr, nullptr, T(0),
                     a.H, a.W, a.C, q.CG, q.CGp, q.NS, q.segs, q.nstrips, 0, 0};
-        uni_variant_note("dwln_train bwd_dx<%s,PXT=%d> wps=%d NS=%d", tn, PXT, q.CGp / 64, q.NS);
+        uni_variant_note("dwln_train bwd_dx%s", cls);
         hipLaunchKernelGGL((dwln_conv_kernel<T, PXT, 2>), dim3(q.nsb), dim3(q.threads), 0, s, kx);
     }
     if (gw) {

@@ -23,8 +23,6 @@
 #include "kernels.h"
 #include "train_ops.h"
 
-constexpr int LNCF_NW = 8;                      // NCHW path: waves of a block
-
 template <typename T>
 struct LncfK {                                  // kernel arguments (by value)
     const void* x;
@@ -357,67 +355,41 @@ __global__ __launch_bounds__(512) void lncf_nchw_kernel(LncfK<T> p, unsigned tpi
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-size_t lncf_train_workspace_bytes(int B, int H, int W, int C) { return train_shape_ok(B, H, W, C) ? (size_t)4 * TRAIN_ROWS * 2 * C : 0; }
+size_t lncf_train_workspace_bytes(int B, int H, int W, int C) { return lncf_plan_workspace_bytes(B, H, W, C); }
 
-// channels-last: NV vectors per lane and G = 2^lg lanes per pixel with G NV >= nvec and the fewest idle vector slots (the smaller NV on a tie)
-static void lncf_cl_plan(int nvec, int* nv, int* lg) {
-    static const int nvs[] = {1, 2, 3, 4, 6, 8};
-    int best = 1 << 30;
-    for (int k : nvs) {
-        int l = 0;
-        while ((k << l) < nvec) ++l;
-        if (l <= 6 && (k << l) < best) {
-            best = k << l;
-            *nv = k;
-            *lg = l;
-        }
-    }
-}
-
-// launches mode MODE with the element type XT of x; *rows = the rows of partials it writes
+// launches mode MODE with the element type XT of x as lncf_plan (train_plan.h) says; *rows = the rows of partials it writes
 template <typename T, typename XT, int MODE>
 static void lncf_launch(const LncfArgs<T>& a, const LncfK<T>& k, int* rows, hipStream_t s) {
-    const char* what = MODE ? "bwd" : "fwd";
-    const char* xn = train_ename(a.x_dtype, sizeof(T) == 8);
-    const size_t lds = (MODE == 1 && k.part) ? (size_t)2 * a.C * sizeof(double) : 0;       // partial sums across lanes are formed in double
-    const int gx = k.gx != nullptr, gwb = k.part != nullptr;
-    if (a.nchw) {
-        const unsigned tpi = (unsigned)cdiv(k.HW, 64), ntiles = (unsigned)a.B * tpi;              // <= B H W
-        *rows = train_rows(ntiles);
-        if (a.C <= 16 * LNCF_NW) {
-            uni_variant_note("lncf_train %s_nchw<%s,regs=16> gx=%d gwb=%d", what, xn, gx, gwb);
-            hipLaunchKernelGGL((lncf_nchw_kernel<T, XT, 16, true, MODE>), dim3(*rows), dim3(64 * LNCF_NW), 0, s, k, tpi, ntiles);
-        } else if (sizeof(T) == 4 && a.C <= 32 * LNCF_NW) {      // fp64 (checks only): 32 x, grad_y and two sums per lane do not fit in registers
-            if constexpr (sizeof(T) == 4) {
-                uni_variant_note("lncf_train %s_nchw<%s,regs=32> gx=%d gwb=%d", what, xn, gx, gwb);
-                hipLaunchKernelGGL((lncf_nchw_kernel<T, XT, 32, true, MODE>), dim3(*rows), dim3(64 * LNCF_NW), 0, s, k, tpi, ntiles);
-            }
-        } else {
-            uni_variant_note("lncf_train %s_nchw<%s,stream=8> gx=%d gwb=%d", what, xn, gx, gwb);
-            hipLaunchKernelGGL((lncf_nchw_kernel<T, XT, 8, false, MODE>), dim3(*rows), dim3(64 * LNCF_NW), lds, s, k, tpi, ntiles);
-        }
-        return;
+    const LncfPlan q = lncf_plan(a.B, a.H, a.W, a.C, sizeof(XT), sizeof(T) == 8, a.nchw != 0, MODE == 1 && k.part);
+    *rows = q.rows;
+    char cls[48] = "";
+    if (train_tracing()) lncf_plan_class(q, train_ename(a.x_dtype, sizeof(T) == 8), cls, sizeof(cls));
+    uni_variant_note("lncf_train %s_%s gx=%d gwb=%d", MODE ? "bwd" : "fwd", cls, k.gx != nullptr, k.part != nullptr);
+    auto nchw = [&](auto ch, auto keep) {
+        hipLaunchKernelGGL((lncf_nchw_kernel<T, XT, decltype(ch)::value, decltype(keep)::value, MODE>), dim3(q.grid), dim3(q.block), q.lds, s, k,
+                           q.per_image, q.units);
+    };
+    switch (q.family) {
+        case LNCF_NCHW_REGS16: return nchw(std::integral_constant<int, 16>(), std::true_type());
+        case LNCF_NCHW_REGS32:                  // never the plan of the fp64 form
+            if constexpr (sizeof(T) == 4) nchw(std::integral_constant<int, 32>(), std::true_type());
+            return;
+        case LNCF_NCHW_STREAM8: return nchw(std::integral_constant<int, 8>(), std::false_type());
     }
-    train_with_vwidth<XT>(a.C, [&](auto vtag) {
+    train_with_vwidth<XT>(q.V, [&](auto vtag) {
         constexpr int V = decltype(vtag)::value;
-        int nv = 1, lg = 0;
-        lncf_cl_plan(a.C / V, &nv, &lg);
-        const int ppb = 256 >> lg;
-        const unsigned ngroups = (unsigned)((k.M + ppb - 1) / ppb);
-        *rows = train_rows(ngroups);
-        uni_variant_note("lncf_train %s_cl<%s,V=%d,NV=%d> G=%d gx=%d gwb=%d", what, xn, V, nv, 1 << lg, gx, gwb);
         auto run = [&](auto ntag) {
             constexpr int NV = decltype(ntag)::value;
-            hipLaunchKernelGGL((lncf_cl_kernel<T, XT, V, NV, MODE>), dim3(*rows), dim3(256), lds, s, k, 1 << lg, lg, ngroups);
+            hipLaunchKernelGGL((lncf_cl_kernel<T, XT, V, NV, MODE>), dim3(q.grid), dim3(q.block), q.lds, s, k, 1 << q.lg, q.lg, q.units);
         };
-        switch (nv) {
+        switch (q.NV) {
             case 1: run(std::integral_constant<int, 1>()); break;
             case 2: run(std::integral_constant<int, 2>()); break;
             case 3: run(std::integral_constant<int, 3>()); break;
             case 4: run(std::integral_constant<int, 4>()); break;
             default:                            // 6 or 8: more than 256 vectors, so V = 4
                 if constexpr (V == 4) {
-                    if (nv == 6) run(std::integral_constant<int, 6>());
+                    if (q.NV == 6) run(std::integral_constant<int, 6>());
                     else run(std::integral_constant<int, 8>());
                 }
         }

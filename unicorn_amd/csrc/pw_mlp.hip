@@ -106,49 +106,28 @@ __global__ __launch_bounds__(256) void pw_map_kernel(PwK<T> p, int L, int lgL, u
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-constexpr int PW_MAX_H = 4 * TRAIN_MAX_C;
-constexpr int PW_ROWS = 256;                    // at most this many rows of partials per sum
-
-static inline bool pw_width_ok(int N) { return N >= 4 && N % 4 == 0 && N <= PW_MAX_H; }
-static inline bool pw_shape_ok(int M, int Hd, int Co) { return M >= 1 && pw_width_ok(Hd) && pw_width_ok(Co); }
 static int pw_shape_refused(const char* what, int M, int Hd, int Co) {
     uni_set_error("%s: shape M=%d Hd=%d Co=%d is outside 1 <= M < 2^31, Hd %% 4 == 0, 4 <= Hd <= %d, Co %% 4 == 0, 4 <= Co <= %d", what, M, Hd, Co,
                   PW_MAX_H, PW_MAX_H);
     return -1;
 }
-size_t pw_mlp_workspace_bytes(int M, int Hd, int Co) { return pw_shape_ok(M, Hd, Co) ? (size_t)4 * PW_ROWS * ((size_t)Hd + Co) : 0; }
+size_t pw_mlp_workspace_bytes(int M, int Hd, int Co) { return pw_plan_workspace_bytes(M, Hd, Co); }
 
-// lanes per row of a block: the power of two L in [min(8, nvec rounded up), 256] with the fewest idle vector slots ceil(nvec / L) L - nvec,
-// the larger L on a tie
-static int pw_plan(int nvec) {
-    int lo = 0;
-    while ((1 << lo) < nvec && lo < 3) ++lo;
-    int best = 1 << 30, lg = lo;
-    for (int l = lo; l <= 8; ++l) {
-        const int padded = cdiv(nvec, 1 << l) << l;
-        if (padded <= best) {
-            best = padded;
-            lg = l;
-        }
-    }
-    return lg;
-}
-
-// launches MODE over the M x N map(s) of k with the element type E; *rows = the rows of partials it writes
+// launches MODE over the M x N map(s) of k with the element type E as pw_plan (train_plan.h) says; *rows = the rows of partials it writes
 template <typename T, typename E, int MODE>
 static void pw_launch(const char* note, PwK<T> k, int M, int N, int dtype, int* rows, hipStream_t s) {
-    train_with_vwidth<E>(N, [&](auto vtag) {
+    const PwPlan q = pw_plan(M, N, sizeof(E));
+    *rows = q.rows;
+    k.M = M;
+    k.N = N;
+    char cls[32] = "";
+    if (train_tracing()) pw_plan_class(q, train_ename(dtype, sizeof(T) == 8), cls, sizeof(cls));
+    if (MODE == 0) uni_variant_note("pw_mlp act_fwd%s", cls);
+    else if (MODE == 1) uni_variant_note("pw_mlp act_bwd%s %s", cls, note);
+    else uni_variant_note("pw_mlp colsum%s", cls);
+    train_with_vwidth<E>(q.V, [&](auto vtag) {
         constexpr int V = decltype(vtag)::value;
-        const int nvec = N / V, lg = pw_plan(nvec), rpb = 256 >> lg;
-        const unsigned ngroups = (unsigned)(((long long)M + rpb - 1) / rpb);
-        *rows = ngroups < (unsigned)PW_ROWS ? (int)ngroups : PW_ROWS;
-        k.M = M;
-        k.N = N;
-        const char* en = train_ename(dtype, sizeof(T) == 8);
-        if (MODE == 0) uni_variant_note("pw_mlp act_fwd<%s,V=%d>", en, V);
-        else if (MODE == 1) uni_variant_note("pw_mlp act_bwd<%s,V=%d> %s", en, V, note);
-        else uni_variant_note("pw_mlp colsum<%s,V=%d>", en, V);
-        hipLaunchKernelGGL((pw_map_kernel<T, E, V, MODE>), dim3(cdiv(nvec, 1 << lg), *rows), dim3(256), 0, s, k, 1 << lg, lg, ngroups);
+        hipLaunchKernelGGL((pw_map_kernel<T, E, V, MODE>), dim3(q.grid_x, q.grid_y), dim3(q.block), 0, s, k, 1 << q.lg, q.lg, q.ngroups);
     });
 }
 

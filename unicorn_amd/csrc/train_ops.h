@@ -1,22 +1,18 @@
-// What the three ConvNeXt training operators (dwln_train.hip, block_tail.hip, lncf_train.hip) share: the shape limits and their refusal, the
-// host helpers of their launchers, the converting 16-byte vector access and the ordered reduce of per-block partial sums.  Plain functions.
+// What the four ConvNeXt training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, pw_mlp.hip) share and that needs HIP: the refusal
+// of a shape, the host helpers of their launchers, the converting 16-byte vector access and the ordered reduce of per-block partial sums.  Plain
+// functions.  The shape limits and the launch plans are in train_plan.h, which compiles for the host alone.
 #pragma once
 #include "common.h"
+#include "train_plan.h"
 #include <type_traits>
 
-constexpr int TRAIN_MAX_C = 2048;
-constexpr int TRAIN_ROWS = 1024;                // at most this many blocks write partial sums (= rows of partials)
-
-static inline bool train_shape_ok(int B, int H, int W, int C) {
-    return B >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0 && C <= TRAIN_MAX_C && (long long)B * H * W < (1ll << 31);
-}
 static inline int train_shape_refused(const char* what, int B, int H, int W, int C) {
     uni_set_error("%s: shape B=%d H=%d W=%d C=%d is outside B, H, W >= 1, C %% 4 == 0, 4 <= C <= %d, B H W < 2^31", what, B, H, W, C, TRAIN_MAX_C);
     return -1;
 }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline const char* train_ename(int dtype, bool f64) { return f64 ? "f64" : dtype == 1 ? "f16" : dtype == 2 ? "bf16" : "f32"; }
-static inline int train_rows(unsigned n) { return n < (unsigned)TRAIN_ROWS ? (int)n : TRAIN_ROWS; }      // blocks that take n units of work
+// the plan class of a tag (the *_plan_class formatters of train_plan.h) is formatted only while the variant trace is on
+static inline bool train_tracing() { return g_uni_variant_trace.load(std::memory_order_relaxed) != 0; }
 
 // The element type E of a tensor that comes as (void*, dtype) next to the math type T: f(tag) with decltype(tag)::type = E.  `arg` names the
 // dtype argument ("y_dtype": the tensor is its first letter).
@@ -35,11 +31,11 @@ static int train_with_etype(const char* what, const char* arg, int dtype, F&& f)
     }
     return 0;
 }
-// channels per lane of a channels-last kernel: 16 bytes of E, so 8 for a half type where C allows it, else 4: f(integral_constant<int, V>)
+// a plan's channels per lane V (train_vwidth: 8 for a half type E only) as a template argument: f(integral_constant<int, V>)
 template <typename E, typename F>
-static void train_with_vwidth(int C, F&& f) {
+static void train_with_vwidth(int V, F&& f) {
     if constexpr (sizeof(E) == 2) {
-        if (C % 8 == 0) return f(std::integral_constant<int, 8>());
+        if (V == 8) return f(std::integral_constant<int, 8>());
     }
     f(std::integral_constant<int, 4>());
 }
