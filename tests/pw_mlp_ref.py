@@ -48,6 +48,23 @@ def draw(tag, seed, shape=None):
     return t, w1, b1, w2, b2, grad_out
 
 
+def draw_maps(M, Hd, Co):
+    """the kernels' own inputs without the GEMMs -> h, grad_a (M, Hd), grad_y (M, Co): plain fp32 normal draws, seeded by the shape"""
+    g = torch.Generator().manual_seed(1000003 * M + 4099 * Hd + Co)
+    return torch.randn(M, Hd, generator=g), torch.randn(M, Hd, generator=g), torch.randn(M, Co, generator=g)
+
+
+def exact_maps(M, Hd, Co, dtype, device="cpu"):
+    """-> h = 30 everywhere, grad_a[r, c] = 1 + (r + c) % 3, grad_y[r, c] = 1 + (2 r + c) % 3, and the integer column sums of the two in fp64.
+    gelu(30) == 30 and gelu'(30) == 1 in fp64, fp32, fp16 and bf16 arithmetic (Phi(30) rounds to 1, 30 phi(30) = 1e-195 vanishes next to it),
+    1, 2, 3 and 30 are numbers of every type and every sum stays below 2^24: a == h, grad_h == grad_a and the sums hold to the last bit, so a
+    row or a vector that is dropped, doubled or read from the wrong place changes an integer"""
+    r, c = torch.arange(M, device=device)[:, None], torch.arange(max(Hd, Co), device=device)[None, :]
+    ga, gy = 1 + (r + c[:, :Hd]) % 3, 1 + (2 * r + c[:, :Co]) % 3
+    assert 3 * M < 2 ** 24
+    return torch.full((M, Hd), 30.0, device=device, dtype=dtype), ga.to(dtype), gy.to(dtype), ga.double().sum(0), gy.double().sum(0)
+
+
 def gelu(h, tanh=False):
     """h Phi(h), the exact form; tanh: the approximation, for the test that tells the two apart"""
     if tanh:

@@ -3,7 +3,10 @@ buffer is a tests/guard.py allocation [front guard | payload | back guard].  h, 
 so a read outside a map reaches an output; a, grad_h, grad_b1 and grad_b2 are filled with 0xA5 and must come back completely written; the
 workspace is exactly what uni_pw_mlp_workspace_bytes returns (twice that for fp64) = 4 * 256 * (Hd + Co).  Guards must come back untouched and
 every output BIT-EQUAL to the plain call on exact-size tensors.  Shapes: the fixtures `c24` (42 rows, a multiple of no rows-per-block value),
-`h100` (Hd no multiple of 8: 25 vectors on 32 lanes) and `c48`, and a single row of 768 hidden units.  Each partial call (a alone, grad_h
+`h100` (Hd no multiple of 8: 25 vectors on 32 lanes) and `c48`, a single row of 768 hidden units, and three shapes whose last column tile has
+idle vector slots that sit on the LAST row, where a lane that ignores `vok` leaves the buffer: 37 x 68 with Co = 164 and 37 x 136 with Co = 328
+(three tiles of L = 8, seven slots idle, with four and with eight columns per lane; the column sums the same at L = 16) and 262 x 2020 with
+Co = 68 (two tiles of L = 256, seven idle, one row per group and 262 groups on 256 rows of partials: the blocks loop).  Each partial call (a alone, grad_h
 alone, the sums alone) leaves the others' buffers and a given workspace untouched."""
 import ctypes as C
 import time
@@ -19,6 +22,7 @@ import pw_mlp_ref as R  # noqa: E402
 DEV = "cuda"
 H_DTYPE = {torch.float32: 0, torch.float64: 0, torch.float16: 1, torch.bfloat16: 2}
 ROWS = 256
+RAGGED = {"m37n68": (37, 68, 164), "m37n136": (37, 136, 328), "m262n2020": (262, 2020, 68)}      # M, Hd, Co
 
 
 @pytest.fixture(scope="module")
@@ -41,6 +45,8 @@ def maps(tag):
     if tag == "row":
         g = torch.Generator().manual_seed(9)
         return torch.randn(1, 768, generator=g).double(), torch.randn(1, 768, generator=g).double(), torch.randn(1, 192, generator=g).double()
+    if tag in RAGGED:
+        return tuple(t.double() for t in R.draw_maps(*RAGGED[tag]))
     ins = [torch.from_numpy(R.load_case(tag)[n]) for n in R.INPUTS]
     full = R.value_and_grads(*ins, dtype=torch.float64)
     Hd, Co = full["h"].shape[-1], ins[5].shape[-1]
@@ -48,7 +54,7 @@ def maps(tag):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.float16, torch.bfloat16], ids=["fp32", "fp64", "fp16", "bf16"])
-@pytest.mark.parametrize("tag", ["c24", "h100", "c48", "row"])
+@pytest.mark.parametrize("tag", ["c24", "h100", "c48", "row"] + sorted(RAGGED))
 def test_pw_mlp_stays_inside_its_buffers(L, tag, dtype):
     h, ga, gy = (t.to(DEV, dtype) for t in maps(tag))
     (M, Hd), Co = h.shape, gy.shape[1]

@@ -1,10 +1,9 @@
 """The recomputing pwconv1-GELU-pwconv2 operator on the GPU (ops.pw_mlp, csrc/pw_mlp.hip, unicorn_amd.nn.fuse_pw_mlp / fuse_backbone_mlp): the
 fixtures written from the reference's own Block in fp64 (1e-12) and fp32 (4 x the larger of the reference's own fp32 deviation and that of the
 eager lines on the same device), fp16 / bf16 autocast against the eager autocast lines, the kernels alone through the C-ABI, the widest and the
-longest shapes, finite extremes of the GELU, the need flags with the variant trace, what autograd keeps and how many bytes that is, an empty
+longest shapes, a width whose last column tile has idle vector slots, finite extremes of the GELU, the need flags with the variant trace, what autograd keeps and how many bytes that is, an empty
 batch, and a stand-in mini-backbone fused with fuse_backbone_mlp against the unfused one.  No bound comes from the code under test."""
 import copy
-import ctypes as C
 import functools
 
 import pytest
@@ -15,12 +14,12 @@ pytestmark = pytest.mark.gpu
 
 import block_tail_ref as RB  # noqa: E402
 import pw_mlp_ref as R  # noqa: E402
-import variant_cases as vc  # noqa: E402
+import train_plans as TP  # noqa: E402
+from pw_mlp_calls import act_calls, traced as _traced  # noqa: E402
 
 DEV = "cuda"
 KEEPS = ["hidden", "input"]
 GRADS = ("g_t", "g_w1", "g_b1", "g_w2", "g_b2")
-H_DTYPE = {torch.float32: 0, torch.float64: 0, torch.float16: 1, torch.bfloat16: 2}
 ULP = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
 
 
@@ -30,10 +29,6 @@ def L():
     _lib.lib()
     assert torch.cuda.is_available(), "gpu tests need a HIP device"
     return _lib
-
-
-def P(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _leaves(ins, dtype, need):
@@ -125,34 +120,6 @@ def test_half_autocast_against_the_eager_autocast_lines(L, tag, half, keep):
 
 
 # ------------------------------------------------------------------------------------------------ the kernels alone, through the C-ABI
-def act_calls(L, h, ga, gy=None, want=("a", "gh", "gb1"), inplace=False, ws=True):
-    """uni_pw_mlp_act_fwd and _bwd on (M, Hd) device maps of one dtype -> {a_fwd, a, grad_h, g_b1, g_b2}"""
-    lib = L.lib()
-    f64 = h.dtype == torch.float64
-    sfx = "_f64" if f64 else ""
-    M, Hd = h.shape
-    Co = gy.shape[1] if gy is not None else 4
-    hd = H_DTYPE[h.dtype]
-    sdt = torch.float64 if f64 else torch.float32
-    s = L.stream_ptr()
-    out = {}
-    hf = h.clone()
-    out["a_fwd"] = hf if inplace else torch.empty_like(h)
-    L.check(getattr(lib, "uni_pw_mlp_act_fwd" + sfx)(P(hf), hd, M, Hd, P(out["a_fwd"]), s), "uni_pw_mlp_act_fwd" + sfx)
-    hb, gb = h.clone(), ga.clone()
-    out["a"] = (hb if inplace else torch.empty_like(h)) if "a" in want else None
-    out["grad_h"] = (gb if inplace else torch.empty_like(h)) if "gh" in want else None
-    out["g_b1"] = torch.empty(Hd, device=DEV, dtype=sdt) if "gb1" in want else None
-    out["g_b2"] = torch.empty(Co, device=DEV, dtype=sdt) if gy is not None else None
-    need = lib.uni_pw_mlp_workspace_bytes(M, Hd, Co) * (2 if f64 else 1)
-    assert need == 4 * 256 * (Hd + Co) * (2 if f64 else 1)
-    wsb = torch.empty(need, dtype=torch.uint8, device=DEV) if ws else None
-    L.check(getattr(lib, "uni_pw_mlp_act_bwd" + sfx)(P(hb), hd, P(gb), M, Hd, P(out["a"]), P(out["grad_h"]), P(out["g_b1"]), P(gy), Co, P(out["g_b2"]),
-                                                     P(wsb), need if ws else 0, s), "uni_pw_mlp_act_bwd" + sfx)
-    torch.cuda.synchronize()
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def hidden_case(tag):
     """h and grad_a of the case in fp64 on the CPU (the restatement on the fixture's inputs); computed once, shared, never modified"""
@@ -218,7 +185,7 @@ def test_finite_extremes(L, dtype):
 # ------------------------------------------------------------------------------------------------ wide and long shapes
 WIDE = {"hd8192": ((3,), 2048, 8192, 2048),          # the limit
         "hd6144": ((6,), 1536, 6144, 1536),          # the widest stage
-        "long": ((1, 300, 300), 4, 16, 4)}           # 90000 rows: 32 rows per block step, 2813 steps on 256 rows of partials -> blocks loop
+        "long": ((1, 300, 300), 4, 16, 4)}           # 90000 rows: L = 4, 64 rows per group, 1407 groups on 256 rows of partials -> blocks loop
 
 
 @functools.lru_cache(maxsize=None)
@@ -259,17 +226,48 @@ def test_long_column_sums_alone(L):
     assert e1 <= b1 and e2 <= b2
 
 
+# ------------------------------------------------------------------------------------------------ idle vector slots behind the first column tile
+RAGGED = ((2, 3, 7), 20, 136, 68)          # Hd = 136: 17 vectors of 8 on three tiles of L = 8 in a half type; Co = 68: the same with vectors of 4
+PRECISIONS = {"fp32": (torch.float32, None), "fp64": (torch.float64, None), "fp16": (torch.float32, torch.float16), "bf16": (torch.float32, torch.bfloat16)}
+
+
+@functools.lru_cache(maxsize=None)
+def ragged_case():
+    """inputs and the eager lines in fp64 on the device (computed once, shared, never modified)"""
+    ins = R.draw("ragged", 78, RAGGED)
+    return ins, run_eager(ins, torch.float64)
+
+
+def test_the_ragged_widths_have_idle_slots_behind_the_first_tile():
+    (_, _, Hd, Co) = RAGGED
+    for dt, N in (("f16", Hd), ("bf16", Hd), ("f32", Co), ("f64", Co), ("f16", Co)):
+        e = TP.plan_extra("pw_mlp", "", dt, N)
+        assert e["gx"] > 1 and e["idle"] > 0, (dt, N, e)
+
+
+@pytest.mark.parametrize("keep", KEEPS)
+@pytest.mark.parametrize("prec", sorted(PRECISIONS))
+def test_ragged_widths_against_the_eager_lines(L, prec, keep):
+    """ops.pw_mlp where the last column tile has idle vector slots, against the eager lines in fp64 on the same device: 1e-12 for fp64, else
+    4 x the deviation of the eager lines in the same precision (fp32, or fp32 tensors under fp16 / bf16 autocast), per result"""
+    dtype, autocast = PRECISIONS[prec]
+    ins, ref = ragged_case()
+    got, tags = _traced(L, lambda: run_op(ins, dtype, keep, autocast=autocast))
+    dt = {"fp32": "f32", "fp64": "f64", "fp16": "f16", "bf16": "bf16"}[prec]
+    assert tags.get("pw_mlp act_fwd" + _cls(dt, RAGGED[2])) == 1 and tags.get("pw_mlp colsum" + _cls(dt, RAGGED[3])) == 1, tags
+    eager = None if prec == "fp64" else run_eager(ins, dtype, autocast=autocast)
+    bad = {}
+    for n in R.RESULTS:
+        err = R.rel_err(got[n], ref[n])
+        bound = 1e-12 if eager is None else 4 * R.rel_err(eager[n], ref[n])
+        print("ragged %s %s %-5s err %.3e  bound %.3e" % (prec, keep, n, err, bound))
+        assert eager is None or got[n].dtype == eager[n].dtype, n
+        if not (got[n].shape == ref[n].shape and err <= bound):
+            bad[n] = (err, bound)
+    assert not bad, bad
+
+
 # ------------------------------------------------------------------------------------------------ need flags, saved tensors, memory, M = 0
-def _traced(L, fn):
-    lib = L.lib()
-    lib.uni_variant_trace(1)
-    try:
-        res = fn()
-    finally:
-        lib.uni_variant_trace(0)
-    return res, {t: v for t, v in vc.read_trace(lib).items() if t.startswith("pw_mlp ")}
-
-
 NEEDS = {"all": ((True,) * 5, 3), "t": ((True, False, False, False, False), 1), "w2": ((False, False, False, True, False), 1),
          "b2": ((False, False, False, False, True), 2), "b1": ((False, False, True, False, False), 2),
          "w1+b1": ((False, True, True, False, False), 2), "none": ((False,) * 5, 0)}
@@ -291,27 +289,40 @@ def test_need_flags(L, which, keep):
             assert torch.equal(got[n], full[n]), n
         else:
             assert got[n] is None, n
-    count = lambda key: sum(v for t, v in tags.items() if t.startswith("pw_mlp " + key))          # noqa: E731
-    assert count("act_fwd<f32,V=4>") == 1 and sum(tags.values()) == 1 + launches, tags
+    count = lambda key: sum(v for t, v in tags.items() if t == "pw_mlp " + key)          # noqa: E731
+    (_, Cc, Hd, Co) = R.CASES["c24"]
+    hid, out = _cls("f32", Hd), _cls("f32", Co)                      # '<f32,V=4> L=8' at both widths of c24
+    assert count("act_fwd" + hid) == 1 and sum(tags.values()) == 1 + launches, tags
     nt, nw1, nb1, nw2, nb2 = need
     if nt or nw1 or nb1 or nw2:
         flags = "a=%d gh=%d gb=%d" % (nw2, nt or nw1, nb1)
-        assert count("act_bwd<f32,V=4> " + flags) == 1, tags
+        assert count("act_bwd%s %s" % (hid, flags)) == 1, tags
     else:
-        assert count("act_bwd") == 0, tags
-    assert count("colsum<f32,V=4>") == int(nb2) and count("reduce<f32>") == int(nb1 or nb2), tags
+        assert not [t for t in tags if t.startswith("pw_mlp act_bwd")], tags
+    assert count("colsum" + out) == int(nb2) and count("reduce<f32>") == int(nb1 or nb2), tags
+
+
+def _cls(dt, N):
+    """the plan class `<dt,V=..> L=..` of width N with the L the host code lists (train_plan_check --list), not a retyped one"""
+    V = 8 if dt in ("f16", "bf16") and N % 8 == 0 else 4
+    return "<%s,V=%d> L=%d" % (dt, V, TP.plan_extra("pw_mlp", "", dt, N)["L"])
 
 
 def test_the_variant_tags_name_dtype_and_width(L):
-    want = {("c24", torch.float16): "<f16,V=8>", ("h100", torch.float16): "<f16,V=4>", ("c48", torch.bfloat16): "<bf16,V=8>"}
-    for (tag, half), text in want.items():
+    """the map kernels over the hidden units carry the class of Hd, the column sum of grad_y that of Co"""
+    want = {("c24", torch.float16): ("f16", 8, 8), ("h100", torch.float16): ("f16", 4, 4), ("c48", torch.bfloat16): ("bf16", 8, 8)}
+    for (tag, half), (dt, v_hid, v_out) in want.items():
+        (_, Cc, Hd, Co) = R.CASES[tag]
+        hid, out = _cls(dt, Hd), _cls(dt, Co)
+        assert hid.startswith("<%s,V=%d> L=" % (dt, v_hid)) and out.startswith("<%s,V=%d> L=" % (dt, v_out))
         ins = fixture_inputs(R.load_case(tag))
         _, tags = _traced(L, lambda: run_op(ins, torch.float32, autocast=half))
-        for kind in ("act_fwd", "act_bwd", "colsum"):
-            assert sum(v for t, v in tags.items() if t.startswith("pw_mlp " + kind + text)) == 1, (tag, kind, tags)
-        assert tags.get("pw_mlp reduce<f32>") == 1 and sum(tags.values()) == 4, tags
+        assert tags == {"pw_mlp act_fwd" + hid: 1, "pw_mlp act_bwd%s a=1 gh=1 gb=1" % hid: 1, "pw_mlp colsum" + out: 1, "pw_mlp reduce<f32>": 1}, (tag, tags)
+    (_, Cc, Hd, Co) = R.CASES["small"]
     _, tags = _traced(L, lambda: run_op(fixture_inputs(R.load_case("small")), torch.float64))
-    assert sorted(tags) == ["pw_mlp act_bwd<f64,V=4> a=1 gh=1 gb=1", "pw_mlp act_fwd<f64,V=4>", "pw_mlp colsum<f64,V=4>", "pw_mlp reduce<f64>"], tags
+    assert tags == {"pw_mlp act_bwd%s a=1 gh=1 gb=1" % _cls("f64", Hd): 1, "pw_mlp act_fwd" + _cls("f64", Hd): 1, "pw_mlp colsum" + _cls("f64", Co): 1,
+                    "pw_mlp reduce<f64>": 1}, tags
+    assert _cls("f64", Hd) == "<f64,V=4> L=4" and _cls("f64", Co) == "<f64,V=4> L=1" and _cls("f16", 96) == "<f16,V=8> L=16"       # the format, once
 
 
 @pytest.mark.parametrize("autocast", [None, torch.float16], ids=["fp32", "fp16-autocast"])

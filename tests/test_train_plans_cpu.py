@@ -14,6 +14,7 @@ import torch
 import block_tail_ref as RB
 import dwln_train_ref as RD
 import lncf_ref as RL
+import pw_mlp_ref as RP
 import train_plans as P
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "unicorn_amd", "csrc")
@@ -161,4 +162,111 @@ def test_a_lane_that_reads_the_wrong_vector_would_show(C):
     for n in ("y", "g_x", "g_weight"):
         moved, bound = RL.rel_err(wrong[n], ref[n]), 4 * dev[n]
         print("C=%d %-8s moved %.3e  bound %.3e  ratio %.3g" % (C, n, moved, bound, moved / bound))
+        assert moved > 100 * bound, (n, moved, bound)
+
+
+# ================================================================================================================ pw_mlp (csrc/pw_mlp.hip)
+def test_the_pw_mlp_list_is_exactly_what_the_host_code_prints():
+    """train_plans.EXPECTED_PW against pw_plan over N = 4, 8, ..., 8192 and the four element types, in both directions; every class is a tag the
+    launcher can print and pw_tag finds it again"""
+    assert len(P.EXPECTED_PW) == len(set(P.EXPECTED_PW)) == 2 * 9 + 2 * 9 + 2 * 8
+    assert P.SWEEP_N[0] == 4 and P.SWEEP_N[-1] == P.N_MAX == P.plan_list()[1]["PW_MAX_H"] and len(P.SWEEP_N) == 2048
+    listed = {k: v for k, v in P.plan_list()[0].items() if k[0] == "pw_mlp"}
+    assert sorted(listed) == sorted(("pw_mlp", "", dt, N) for dt in P.PW_DTYPES for N in P.SWEEP_N)
+    printed = _printable("pw_mlp")
+    assert printed == set(P.EXPECTED_PW), "printed but not listed: %s; listed but never printed: %s" % (
+        sorted(printed - set(P.EXPECTED_PW)), sorted(set(P.EXPECTED_PW) - printed))
+    per = {dt: P.pw_classes(dt) for dt in P.PW_DTYPES}
+    assert {dt: len(c) for dt, c in per.items()} == {"f32": 9, "f64": 9, "f16": 17, "bf16": 17}
+    for dt, classes in per.items():
+        for cls, ns in classes.items():
+            assert cls.startswith("<%s,V=" % dt) and re.match(r"^<(%s),V=[48]> L=(1|2|4|8|16|32|64|128|256)$" % "|".join(ENAMES), cls), cls
+            assert {P.plan_extra("pw_mlp", "", dt, N)["L"] for N in ns} == {P.pw_lanes(cls)}, cls       # the L of the tag is the L of the plan
+            for tag, kind in (("pw_mlp act_fwd%s" % cls, "act_fwd"), ("pw_mlp act_bwd%s a=1 gh=0 gb=1" % cls, "act_bwd"), ("pw_mlp colsum%s" % cls, "colsum")):
+                assert P.pw_tag(tag) == (kind, cls), tag
+    assert P.pw_tag("pw_mlp reduce<f32>") is None and P.pw_tag("lncf_train fwd_cl<f32,V=4,NV=1> G=1 gx=0 gwb=0") is None
+    first = P.pw_first_run()
+    assert first and set(first) < set(P.EXPECTED_PW) and len(first) == 28, first
+    assert "<f32,V=4> L=64" in first and "<f64,V=4> L=256" in first and "<f16,V=8> L=256" in first and "<f32,V=4> L=256" not in first
+
+
+def test_pw_mlp_spot_facts_of_the_plan():
+    f32, f16 = P.pw_classes("f32"), P.pw_classes("f16")
+    assert (f32["<f32,V=4> L=8"][0], f32["<f32,V=4> L=8"][-1]) == (20, 8160)
+    assert (f32["<f32,V=4> L=256"][0], f32["<f32,V=4> L=256"][-1]) == (996, 8192)
+    lanes = (8, 16, 32, 64, 128, 256)
+    assert [P.pw_widths("f32", "<f32,V=4> L=%d" % L)[2] for L in lanes] == [68, 164, 356, 740, 1508, 2020]
+    assert [P.pw_widths("f16", "<f16,V=8> L=%d" % L)[2] for L in lanes] == [136, 328, 712, 1480, 3016, 4040]
+    assert "<f16,V=4> L=2" not in f16 and f16["<f16,V=8> L=1"] == [8] and f16["<f16,V=8> L=2"] == [16]
+    for dt in P.PW_DTYPES:
+        for N in P.SWEEP_N:
+            e = P.plan_extra("pw_mlp", "", dt, N)
+            V = 8 if dt in ("f16", "bf16") and N % 8 == 0 else 4
+            assert 0 <= e["idle"] <= 7 and e["gx"] * e["L"] - e["idle"] == N // V and (e["gx"] - 1) * e["L"] < N // V, (dt, N, e)
+        for cls in P.pw_classes(dt):
+            lo, hi, ragged = P.pw_widths(dt, cls)
+            assert lo <= ragged <= hi and (ragged == lo) == (P.pw_lanes(cls) < 8 or lo == hi), (cls, lo, hi, ragged)
+
+
+def test_pw_mlp_rows_make_two_groups_and_a_block_that_loops():
+    """Where a group has more than five rows (L <= 32) -- M_short: two groups, five rows in the second; M_loop: 258 groups on 256 rows of
+    partials, so blockIdx.y 0 and 1 take two groups each, and the last group has five rows.  With 4, 2 and 1 rows per group the same row counts
+    make 3, 4 and 6 groups and 259, 260 and 262: still more than one group, still more groups than rows of partials, and the last group partial
+    wherever a group has more than one row.  The largest maps stay small: 1.1 M elements where a lane has four columns, twice that where it
+    has eight"""
+    rows = P.plan_list()[1]["PW_ROWS"]
+    for L in (1, 2, 4, 8, 16, 32, 64, 128, 256):
+        rpb = 256 // L
+        short, loop = P.pw_rows(L)
+        assert (short, loop) == (rpb + 5, 256 * rpb + rpb + 5)
+        if rpb > 5:
+            assert -(-short // rpb) == 2 and short - rpb == 5
+            assert -(-loop // rpb) == rows + 2 and loop - (rows + 1) * rpb == 5
+        else:
+            assert (-(-short // rpb), -(-loop // rpb)) == {4: (3, 259), 2: (4, 260), 1: (6, 262)}[rpb]
+            assert rpb == 1 or (short % rpb and loop % rpb)
+        assert 1 < -(-short // rpb) <= rows < -(-loop // rpb) <= 2 * rows
+    assert P.pw_rows(1) == (261, 65797) and P.pw_rows(256) == (6, 262)
+    for dt in P.PW_DTYPES:
+        shapes = P.pw_shapes(dt)
+        assert len(shapes) == 3 * len(P.pw_classes(dt))
+        for cls, M, N in shapes:
+            assert P.predicted("pw_mlp", "", dt, N) == cls and M * N < (2.2e6 if "V=8" in cls else 1.1e6), (cls, M, N)
+    assert max(M for _, M, N in P.pw_shapes("f32")) == 65797 and ("<f32,V=4> L=256", 262, 2020) in P.pw_shapes("f32")
+
+
+@functools.lru_cache(maxsize=None)
+def pw_yardstick(M, N):
+    """h, grad_a, grad_y drawn for the shape; a, grad_h, g_b1 and the column sums of grad_y in fp64 and the fp32 restatement's deviation"""
+    h, ga, gy = RP.draw_maps(M, N, N)
+    ref, f32 = RP.act_maps(h.double(), ga.double()), RP.act_maps(h, ga)
+    return (h, ga, gy), ref, {n: RP.rel_err(f32[n], ref[n]) for n in ("a", "grad_h", "g_b1")}
+
+
+def test_pw_mlp_fp32_yardstick_is_positive_at_every_shape_the_gpu_file_runs():
+    shapes = sorted({(M, N) for _, M, N in P.pw_shapes("f32")})
+    # 27 less the two classes of one width (N = 4, N = 8), whose lo and hi coincide
+    assert len(shapes) == 27 - 2 and (8229, 68) in shapes and (65797, 4) in shapes and (262, 2020) in shapes and (37, 8160) in shapes
+    for M, N in shapes:
+        dev = pw_yardstick(M, N)[2]
+        print("M=%5d N=%4d " % (M, N) + "  ".join("%s %.2e" % kv for kv in dev.items()))
+        assert all(0 < v < 1e-5 for v in dev.values()), (M, N, dev)
+
+
+@pytest.mark.parametrize("L,which", [(1, "ragged"), (8, "ragged"), (256, "ragged"), (8, "hi")])
+def test_a_pw_mlp_lane_that_skips_a_vector_or_a_group_would_show(L, which):
+    """On the restatement: the last V columns of the last row of h zeroed -- what the last lane of the last column tile reads when its `vok`, its
+    column or its group stride is wrong -- moves a, grad_h and g_b1, and the last five rows left out of the column sum -- a last group that
+    is dropped -- moves g_b1, each by more than 100 x the fp32 bound of the GPU test (4 x the yardstick)."""
+    cls = "<f32,V=4> L=%d" % L
+    lo, hi, ragged = P.pw_widths("f32", cls)
+    M, N = (P.pw_rows(L)[1], ragged) if which == "ragged" else (P.pw_rows(L)[0], hi)
+    (h, ga, _), ref, dev = pw_yardstick(M, N)
+    wrong_h = h.double().clone()
+    wrong_h[-1, -4:] = 0.0
+    wrong = RP.act_maps(wrong_h, ga.double())
+    short = RP.act_maps(h.double()[:-5], ga.double()[:-5])
+    for n, moved in [(n, RP.rel_err(wrong[n], ref[n])) for n in ("a", "grad_h", "g_b1")] + [("g_b1", RP.rel_err(short["g_b1"], ref["g_b1"]))]:
+        bound = 4 * dev[n]
+        print("%s M=%d N=%d %-7s moved %.3e  bound %.3e  ratio %.3g" % (cls, M, N, n, moved, bound, moved / bound))
         assert moved > 100 * bound, (n, moved, bound)

@@ -64,12 +64,39 @@ FIRST_RUN = {
 }
 
 
+# ---------------------------------------------------------------------------------------------------------------- pw_mlp
+# pw_plan (csrc/train_plan.h) over N = 4, 8, ..., 8192: a plan class is (dtype, V, L) -- `<f16,V=8> L=16` -- with V = N's columns per lane and
+# L the lanes per row of a block.  tests/test_pw_mlp_plans_gpu.py sweeps every N and runs every class; train_plan_census.json and the two
+# dicts above stay those of the three operators swept first, so pw_mlp has lists of its own.
+N_STEP, N_MAX = 4, 8192                     # pw_width_ok: N % 4 == 0, 4 <= N <= PW_MAX_H
+SWEEP_N = tuple(range(N_STEP, N_MAX + 1, N_STEP))
+PW_DTYPES = ("f32", "f64", "f16", "bf16")
+_PW_L = (1, 2, 4, 8, 16, 32, 64, 128, 256)
+# half types at V = 4 are the widths with N % 8 == 4: N / 4 is odd, so L = 2 (N = 8 alone, which takes V = 8) cannot occur
+_PW_L_HALF4 = tuple(L for L in _PW_L if L != 2)
+
+
+def _pw(dt, V, ls):
+    return ["<%s,V=%d> L=%d" % (dt, V, L) for L in ls]
+
+
+EXPECTED_PW = (_pw("f32", 4, _PW_L) + _pw("f64", 4, _PW_L) + _pw("f16", 8, _PW_L) + _pw("bf16", 8, _PW_L)
+               + _pw("f16", 4, _PW_L_HALF4) + _pw("bf16", 4, _PW_L_HALF4))                                # 2 x 9 + 2 x 9 + 2 x 8 = 52
+
+# the widths (Hd and Co) at which a test compared pw_mlp with a reference before this list existed: the fixtures, the wide and long shapes
+# and the mini-backbone of tests/test_pw_mlp_gpu.py.  pw_first_run() is every class none of them reaches.
+PW_WIDTHS_BEFORE = {"f32": (4, 12, 16, 24, 32, 48, 64, 96, 100, 128, 192, 1536, 2048, 6144, 8192),
+                    "f64": (4, 12, 16, 24, 32, 48, 64, 96, 100, 128, 192),
+                    "f16": (12, 16, 24, 32, 48, 64, 96, 100, 128, 192),
+                    "bf16": (12, 16, 24, 48, 96, 100, 192)}
+
+
 PLAN_CHECK = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "build", "train_plan_check")
 
 
 @functools.lru_cache(maxsize=None)
 def plan_list():
-    """`train_plan_check --list`, run once: ({(op, layout, dt, C): (plan class, {"PP" | "block" | "L": value})}, {limit: value}); op is lncf,
+    """`train_plan_check --list`, run once: ({(op, layout, dt, C): (plan class, {"PP" | "block" | "L" | "gx" | "idle": value})}, {limit: value}); op is lncf,
     block_tail, dwln or pw_mlp, layout is "" for the two operators that have one layout only"""
     if not os.path.exists(PLAN_CHECK):
         raise AssertionError("tools/build/train_plan_check is missing: run __graft_entry__.build() (csrc/build.sh builds it)")
@@ -133,7 +160,8 @@ def bt_class(layout, dt, C):
 
 
 def plan_extra(op, layout, dt, C):
-    """what the list says next to the class: PP and block for block_tail, L for pw_mlp"""
+    """what the list says next to the class: PP and block for block_tail; for pw_mlp L, and at M = 1 gx (column tiles of L vectors) and idle
+    (vector slots of those tiles that no vector fills)"""
     return plan_list()[0][(op, layout, dt, C)][1]
 
 
@@ -142,3 +170,59 @@ def zero_one_vector(x, C):
     x = x.clone()
     x[0, C - 4:C, 0, 0] = 0.0
     return x
+
+
+# ---------------------------------------------------------------------------------------------------------------- pw_mlp: classes, widths, rows
+_PW_TAG = re.compile(r"^pw_mlp (act_fwd|act_bwd|colsum)(<[^>]+> L=\d+)")
+
+
+def pw_tag(tag):
+    """('act_fwd' | 'act_bwd' | 'colsum', plan class) of a map kernel's tag: 'pw_mlp act_bwd<f16,V=8> L=16 a=1 gh=1 gb=1' -> ('act_bwd',
+    '<f16,V=8> L=16'); None for the reduce launch"""
+    m = _PW_TAG.match(tag)
+    return (m.group(1), m.group(2)) if m else None
+
+
+@functools.lru_cache(maxsize=None)
+def pw_classes(dt):
+    """{plan class: [N, ...]} of the element type dt over SWEEP_N, as the host code says (train_plan_check --list)"""
+    return group({N: predicted("pw_mlp", "", dt, N) for N in SWEEP_N})
+
+
+def pw_lanes(cls):
+    """L of a plan class"""
+    return int(cls.rsplit("L=", 1)[1])
+
+
+def pw_first_run():
+    """the classes no test had compared with a reference before tests/test_pw_mlp_plans_gpu.py, in the order of EXPECTED_PW"""
+    before = {predicted("pw_mlp", "", dt, N) for dt, ws in PW_WIDTHS_BEFORE.items() for N in ws}
+    return [c for c in EXPECTED_PW if c not in before]
+
+
+def pw_widths(dt, cls):
+    """(lo, hi, ragged) of a class: its smallest and its largest N, and the smallest N with more than one column tile (gx > 1) AND idle vector
+    slots in the last one (idle > 0) -- `vok` false in a block with blockIdx.x > 0.  Classes with L < 8 have one tile only: ragged = lo"""
+    ns = pw_classes(dt)[cls]
+    ragged = [N for N in ns if plan_extra("pw_mlp", "", dt, N)["gx"] > 1 and plan_extra("pw_mlp", "", dt, N)["idle"] > 0]
+    assert bool(ragged) == (pw_lanes(cls) >= 8), (cls, ragged[:1])
+    return ns[0], ns[-1], ragged[0] if ragged else ns[0]
+
+
+def pw_rows(L):
+    """(M_short, M_loop) for a class of L lanes per row, rpb = 256 / L rows per group.  M_short = rpb + 5: two groups, the second with five
+    live slots.  M_loop = 256 rpb + rpb + 5: 258 groups on PW_ROWS = 256 rows of partials, so blockIdx.y 0 and 1 take two groups each and the
+    last group has five rows.  That is so for rpb > 5 (L <= 32); with 4, 2 and 1 rows per group the same counts make 3, 4, 6 and 259, 260, 262
+    groups (tests/test_train_plans_cpu.py states it)"""
+    rpb = 256 // L
+    return rpb + 5, 256 * rpb + rpb + 5
+
+
+def pw_shapes(dt):
+    """[(class, M, N)]: per class of dt, lo and hi at M_short and ragged at M_loop"""
+    out = []
+    for cls in pw_classes(dt):
+        lo, hi, ragged = pw_widths(dt, cls)
+        short, loop = pw_rows(pw_lanes(cls))
+        out += [(cls, short, lo), (cls, short, hi), (cls, loop, ragged)]
+    return out

@@ -316,7 +316,8 @@ static int list() {
         for (int N = 4; N <= PW_MAX_H; N += 4) {
             const PwPlan q = pw_plan(1, N, e.esize);
             pw_plan_class(q, e.name, cls, sizeof(cls));
-            std::printf("pw_mlp - %s %d | %s | L=%d\n", e.name, N, cls, 1 << q.lg);
+            // at M = 1: gx column tiles of L vectors; idle = the vector slots of those tiles that no vector fills
+            std::printf("pw_mlp - %s %d | %s | L=%d gx=%d idle=%d\n", e.name, N, cls, 1 << q.lg, q.grid_x, (q.grid_x << q.lg) - N / q.V);
         }
     std::printf("limits | TRAIN_MAX_C=%d TRAIN_ROWS=%d PW_MAX_H=%d PW_ROWS=%d\n", TRAIN_MAX_C, TRAIN_ROWS, PW_MAX_H, PW_ROWS);
     return 0;

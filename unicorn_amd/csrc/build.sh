@@ -51,6 +51,8 @@ if [ ! -f ../../tools/build/train_plan_check ] || [ ../../tools/train_plan_check
   g++ -O2 -std=c++17 -Wall -Wextra ../../tools/train_plan_check.cpp -o ../../tools/build/train_plan_check
   echo "built tools/build/train_plan_check"
 fi
+../../tools/build/train_plan_check > build/train_plan_check.log || { tail -3 build/train_plan_check.log; exit 1; }
+tail -2 build/train_plan_check.log
 # standalone measurement program (tools/feed_probe.hip: which path feeds a CU; profiles/r05_feed_probe.txt) -- not part of the library:
 # built last and non-fatally (a probe that does not compile on another ROCm must not leave the libraries unbuilt)
 mkdir -p ../../tools/build

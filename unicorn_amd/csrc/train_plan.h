@@ -194,7 +194,9 @@ static inline PwPlan pw_plan(int M, int N, int esize) {
     q.block = 256;
     return q;
 }
-// `<f16,V=8>`
-static inline void pw_plan_class(const PwPlan& q, const char* en, char* buf, size_t n) { std::snprintf(buf, n, "<%s,V=%d>", en, q.V); }
+// `<f16,V=8> L=16`: the instantiation and the lane mapping, as lncf's `cl<...> G=4`
+static inline void pw_plan_class(const PwPlan& q, const char* en, char* buf, size_t n) {
+    std::snprintf(buf, n, "<%s,V=%d> L=%d", en, q.V, 1 << q.lg);
+}
 // two sums: [PW_ROWS][Hd] at 0, [PW_ROWS][Co] behind it
 static inline size_t pw_plan_workspace_bytes(int M, int Hd, int Co) { return pw_shape_ok(M, Hd, Co) ? (size_t)4 * PW_ROWS * ((size_t)Hd + Co) : 0; }
