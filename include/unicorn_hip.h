@@ -553,6 +553,52 @@ int uni_pw_mlp_act_fwd_f64(const void* h, int h_dtype, int M, int Hd, void* a, u
 int uni_pw_mlp_act_bwd_f64(const void* h, int h_dtype, const void* grad_a, int M, int Hd, void* a, void* grad_h, double* grad_b1,
                            const void* grad_y, int Co, double* grad_b2, void* workspace, size_t workspace_bytes, uni_stream_t stream);
 
+/* GroupNorm + activation for TRAINING: what every BaseConv of the YOLOX-PAFPN and of the head runs after convert_bn_model_to_gn
+ * (unicorn/models/backbone/network_blocks.py:29-51: act(bn(conv(x))) with bn = GroupNorm(16, C, eps=1e-3), act = SiLU), the CondInst mask
+ * branch (GroupNorm(16, C) + ReLU) and unicorn.py:38 (GroupNorm(32, C) alone), forward and backward for a whole batch: at most three launches
+ * forward and three backward, no host synchronisation, no read-back, no allocation, no atomics.  The convolution is the caller's.  Operator
+ * only: the model-level engine stays inference only.
+ *   x, y, grad_y, grad_x  (B, C, H, W) maps, all four in ONE memory layout: nchw == 0: dense [B][H][W][C] (channels-last memory), nchw != 0:
+ *                         dense [B][C][H][W].  Both are read and written in place.  x_dtype: 0 = the type of the form (fp32, fp64 in the _f64
+ *                         form), 1 = fp16, 2 = bf16 (fp32 form only) is the type of x and grad_x; y and grad_y have the type of the form.
+ *                         Conversion in registers, all arithmetic fp32 (fp64).  y must not overlap x.
+ *   weight, bias, grad_weight, grad_bias  [C]
+ *   G                     groups of cpg = C / G consecutive channels; cpg need not be a multiple of 4
+ *   act                   0 none, 1 ReLU, 3 SiLU z * sigmoid(z) (the exact form)
+ *   stats                 [B G][2] = mean and 1 / sqrt(var + eps) of every (sample, group), written by the forward, read by the backward
+ *   uni_gn_act_train_fwd  mean and the biased variance over the m = cpg H W elements of a (sample, group); z = (x - mean) * rstd * weight[c] +
+ *                         bias[c]; y = act(z).  Launch 1: every block takes pixels of ONE image and writes, per channel, the mean over its pixels
+ *                         and the sum of squared deviations from THAT mean (a second pass over its pixels: no E[x^2] - E[x]^2); launch 2 combines
+ *                         these parts (count, mean, M2; Chan et al.) in a fixed order in double; launch 3 writes y.  Between launch 1
+ *                         and launch 3 the parts lie in y (they fit for every admitted shape), so there is no forward workspace.  Writes y and
+ *                         stats COMPLETELY.
+ *   uni_gn_act_train_bwd  xhat = (x - mean) * rstd, z as above, dz = grad_y * act'(z) with act' = 1, z > 0, s (1 + z (1 - s)) for s = sigmoid(z):
+ *                         grad_bias[c] = sum over n, h, w of dz, grad_weight[c] = sum of dz * xhat; with A = sum_{c in g} weight[c] sum_hw dz and
+ *                         Bq = sum_{c in g} weight[c] sum_hw dz * xhat: grad_x = rstd * (weight[c] * dz - (A + xhat * Bq) / m).  Launch 1 writes the
+ *                         per-(row of partials, channel) sums of dz * xhat and dz, launch 2 forms A / m, Bq / m per (sample, group) and
+ *                         grad_weight, grad_bias from them, launch 3 writes grad_x.  grad_x and the pair grad_weight / grad_bias may be NULL: that
+ *                         part of launch 2 is skipped, and launch 3 with grad_x; what is computed has the same bits as in the full call.  Both
+ *                         NULL: no launch, no error.  Each output is written COMPLETELY.
+ * One writer per element, fixed summation orders (a lane's own pixels in the math type, the first-pass sum of x in double; the lanes of a
+ * block and the rows of partials in ascending order or a fixed tree in double): two calls give the same bits.
+ * Limits: B, H, W >= 1, C % 4 == 0, 4 <= C <= 2048, B H W < 2^31 (element offsets are 64-bit), 1 <= G <= C, C % G == 0, pointers 16-byte
+ * aligned (H W need not be a multiple of anything: with nchw != 0 the rows of a channel plane are read element-wise); other shapes are
+ * refused with an error string before any launch and uni_gn_act_train_workspace_bytes returns 0 for them.
+ * workspace (every backward that computes something): 16-byte aligned device scratch of >= uni_gn_act_train_workspace_bytes(B, H, W, C, G)
+ * bytes (fp32; the _f64 form needs twice that) = 4 * (B rpi 2 C rounded up to 64, + 2 B G) with rpi = min(ceil(H W / u), max(1, 1024 / B)) rows
+ * of partials per image, u = the power of two >= B H W / 512 within [16, 256].  Nothing is kept in it between calls. */
+size_t uni_gn_act_train_workspace_bytes(int B, int H, int W, int C, int G);
+int uni_gn_act_train_fwd(const void* x, int x_dtype, int nchw, const float* weight, const float* bias, double eps, int act, int B, int H, int W,
+                         int C, int G, float* y, float* stats, uni_stream_t stream);
+int uni_gn_act_train_bwd(const void* x, int x_dtype, int nchw, const float* weight, const float* bias, const float* stats, const float* grad_y,
+                         int act, int B, int H, int W, int C, int G, void* grad_x, float* grad_weight, float* grad_bias, void* workspace,
+                         size_t workspace_bytes, uni_stream_t stream);
+int uni_gn_act_train_fwd_f64(const void* x, int x_dtype, int nchw, const double* weight, const double* bias, double eps, int act, int B, int H,
+                             int W, int C, int G, double* y, double* stats, uni_stream_t stream);
+int uni_gn_act_train_bwd_f64(const void* x, int x_dtype, int nchw, const double* weight, const double* bias, const double* stats,
+                             const double* grad_y, int act, int B, int H, int W, int C, int G, void* grad_x, double* grad_weight,
+                             double* grad_bias, void* workspace, size_t workspace_bytes, uni_stream_t stream);
+
 /* What stands around the label propagation in the SOT / VOS TRAINING losses (unicorn/models/unicorn.py:315-337 compute_loss_sot, :339-390
  * compute_loss_vos) for a whole BATCH, without a host synchronisation, a read-back or an allocation; the number of launches does not
  * depend on the data.  The propagation itself is uni_corr_softmax_pv_lse / _bwd on the label rows these entries produce.

@@ -1,4 +1,4 @@
-// Host check of unicorn_amd/csrc/train_plan.h: the launch plans of the four ConvNeXt training operators over their admitted domain.  Plain C++
+// Host check of unicorn_amd/csrc/train_plan.h: the launch plans of the four ConvNeXt training operators and of gn_act over their admitted domain.  Plain C++
 // (built by unicorn_amd/csrc/build.sh into tools/build/train_plan_check, run by tests/test_train_plans_cpu.py; tests/train_plans.py reads
 // --list).  Default: every condition below at every point of the domain, then each condition once on a deliberately wrong plan, which it must
 // refuse; prints `train_plan_check: OK` or the first violated condition with its arguments and exits non-zero.  --list: one line per
@@ -152,6 +152,65 @@ static void check_pw(const PwPlan& q, int M, int N, int esize, size_t off, size_
     check_region(q.rows, PW_ROWS, off, (size_t)N, ws_f32_bytes);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- gn_act
+static const int GN_GS[] = {1, 2, 4, 16, 32};    // next to G = C and G = C / 4 (cpg = 1 and 4) and G = C / 6, C / 12 where they divide (cpg = 6, 12)
+static void check_gn(const GnPlan& q, const Map& m, int C, int G, const Etype& e) {
+    const long long HW = (long long)m.H * m.W;
+    // gn_cl_kernel: sm[256 V] doubles and bc[256 V] of the math type where it sums, __launch_bounds__(256); gn_nchw_kernel: no LDS, __launch_bounds__(256)
+    check_launch(q.grid_x, q.grid_y, q.block, 256, q.nchw ? 0 : (size_t)256 * q.V * (8 + (e.f64 ? 8 : 4)), 0);
+    REQUIRE(q.block == 256, "block %d", q.block);
+    REQUIRE(q.unit >= (q.nchw ? 64 : GN_UNIT_CL_MIN) && q.unit <= GN_UNIT_NCHW && (q.unit & (q.unit - 1)) == 0 && (long long)q.upi * q.unit >= HW && (long long)(q.upi - 1) * q.unit < HW, "%u units of %d pixels, %lld pixels", q.upi, q.unit, HW);
+    REQUIRE(q.rpi >= 1 && (unsigned)q.rpi <= q.upi && q.rows == (long long)m.B * q.rpi && q.grid_x == q.rows, "%d rows per image, %d rows, grid %d", q.rpi,
+            q.rows, q.grid_x);
+    REQUIRE(q.rows <= (m.B > TRAIN_ROWS ? m.B : TRAIN_ROWS), "%d rows of partials", q.rows);
+    long long px = 0;                           // the rows of an image take every pixel once
+    for (int r = 0; r < q.rpi; ++r) {
+        const long long n = gn_row_pixels(HW, q.unit, q.upi, q.rpi, r);
+        REQUIRE(n >= 1, "row %d of %d takes %lld pixels", r, q.rpi, n);
+        px += n;
+    }
+    REQUIRE(px == HW, "the rows take %lld pixels of %lld", px, HW);
+    // the forward keeps [rows][planes][C] in y [B][H W][C]
+    REQUIRE((q.planes == 2 || (q.planes == 1 && HW == 1)) && (long long)q.rpi * q.planes <= HW, "%d planes x %d rows in a map of %lld pixels", q.planes, q.rpi, HW);
+    if (q.nchw) {
+        REQUIRE((long long)q.grid_y * GN_NCHW_CT >= C && (long long)(q.grid_y - 1) * GN_NCHW_CT < C, "%d channel tiles", q.grid_y);
+    } else {
+        const int nvec = C / q.V, L = 1 << q.lg;
+        REQUIRE(q.V == 4 || (q.V == 8 && e.esize == 2 && C % 8 == 0), "V = %d", q.V);
+        REQUIRE(q.lg >= 0 && q.lg <= 8 && (long long)q.grid_y * L >= nvec && (long long)(q.grid_y - 1) * L < nvec, "%d column tiles of %d vectors, %d vectors", q.grid_y,
+                L, nvec);
+    }
+    REQUIRE(q.comb_blocks >= 1 && q.comb_blocks <= (unsigned)GN_COMB_BLOCKS && (long long)q.comb_blocks <= (long long)m.B * G, "%u combine blocks",
+            q.comb_blocks);
+    // partials [rows][2][C], then the group sums [B G][2]: disjoint, inside the bytes the size function promises
+    const size_t ws = gn_plan_workspace_bytes(m.B, m.H, m.W, C, G);
+    REQUIRE((size_t)q.rows * 2 * C <= q.off_ab && q.off_ab % 4 == 0 && q.elems == q.off_ab + (size_t)m.B * G * 2 && q.elems * 4 <= ws,
+            "partials end at %zu, group sums at %zu .. %zu, the workspace holds %zu", (size_t)q.rows * 2 * C, q.off_ab, q.elems, ws / 4);
+}
+static void check_gn_at(const Map& m, int C, int G, const Etype& e, bool nchw) {
+    char b[160];
+    std::snprintf(b, sizeof(b), "gn_act B=%d H=%d W=%d C=%d G=%d %s %s", m.B, m.H, m.W, C, G, e.name, nchw ? "nchw" : "cl");
+    g_where = b;
+    REQUIRE(gn_shape_ok(m.B, m.H, m.W, C, G), "gn_shape_ok refuses an admitted shape");
+    check_gn(gn_plan(m.B, m.H, m.W, C, G, e.esize, nchw), m, C, G, e);
+}
+static long long sweep_gn() {
+    long long n = 0;
+    for (const Map& m : MAPS)
+        for (int C = 4; C <= TRAIN_MAX_C; C += 4)
+            for (const Etype& e : ETYPES)
+                for (int nchw = 0; nchw < 2; ++nchw) {
+                    int gs[16], ng = 0;
+                    for (int G : GN_GS)
+                        if (C % G == 0) gs[ng++] = G;
+                    gs[ng++] = C, gs[ng++] = C / 4;
+                    if (C % 6 == 0) gs[ng++] = C / 6;
+                    if (C % 12 == 0) gs[ng++] = C / 12;
+                    for (int i = 0; i < ng; ++i, ++n) check_gn_at(m, C, gs[i], e, nchw);
+                }
+    return n;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- the sweeps
 static void check_dwln(const Map& m, int C, const Etype& e) {
     DwlnPlan q, q64;
@@ -214,6 +273,13 @@ static void check_sizes() {
         for (int Hd : NS)
             for (int Co : NS)
                 REQUIRE((pw_plan_workspace_bytes(M, Hd, Co) != 0) == pw_shape_ok(M, Hd, Co), "M=%d Hd=%d Co=%d", M, Hd, Co);
+    for (const Map& m : EDGE)
+        for (int C : CS)
+            for (int G : {-1, 0, 1, 3, 4, 5, 16, 96, 2048, 4096}) {
+                const bool ok = train_shape_ok(m.B, m.H, m.W, C) && G >= 1 && G <= C && C % G == 0;
+                REQUIRE(gn_shape_ok(m.B, m.H, m.W, C, G) == ok && (gn_plan_workspace_bytes(m.B, m.H, m.W, C, G) != 0) == ok, "B=%d H=%d W=%d C=%d G=%d: admitted %d",
+                        m.B, m.H, m.W, C, G, (int)ok);
+            }
 }
 
 // each condition once on a deliberately wrong plan: `what` must fail
@@ -286,6 +352,24 @@ static int check_that_conditions_bite() {
     pw("pw_mlp: L halved", second, [](PwPlan& q) { --q.lg; });
     pw("pw_mlp: a column tile less", second, [](PwPlan& q) { --q.grid_x; });
     pw("pw_mlp: the second sum a row late", second + 768, [](PwPlan&) {});
+    auto gn = [&](const char* what, const Map& gm, bool nchw, int C, int G, auto&& spoil) {
+        GnPlan q = gn_plan(gm.B, gm.H, gm.W, C, G, 4, nchw);
+        spoil(q);
+        must_fail(what, [&] { check_gn(q, gm, C, G, f32); });
+        ++n;
+    };
+    const Map one{3, 1, 1};
+    gn("gn_act: a row more per image", m, false, 96, 16, [](GnPlan& q) { ++q.rpi; });
+    gn("gn_act: rows + 1", m, false, 96, 16, [](GnPlan& q) { q.grid_x = ++q.rows; });
+    gn("gn_act: a unit less per image", m, true, 96, 16, [](GnPlan& q) { --q.upi; });
+    gn("gn_act: units of 8 pixels", m, false, 96, 16, [](GnPlan& q) { q.unit = 8; q.upi = 11250; });
+    gn("gn_act: two planes in a map of one pixel", one, false, 96, 16, [](GnPlan& q) { q.planes = 2; });
+    gn("gn_act: a column tile less", m, false, 1000, 5, [](GnPlan& q) { --q.grid_y; });
+    gn("gn_act: a channel tile less", m, true, 1000, 5, [](GnPlan& q) { --q.grid_y; });
+    gn("gn_act: V = 8 for fp32", m, false, 96, 16, [](GnPlan& q) { q.V = 8; });
+    gn("gn_act: the group sums inside the partials", m, false, 96, 16, [](GnPlan& q) { q.off_ab -= 64; });
+    gn("gn_act: more combine blocks than pairs", one, false, 96, 1, [](GnPlan& q) { q.comb_blocks = 4; });
+    gn("gn_act: block of 512", m, true, 96, 16, [](GnPlan& q) { q.block = 512; });
     g_where = "";
     return n;
 }
@@ -320,6 +404,16 @@ static int list() {
             std::printf("pw_mlp - %s %d | %s | L=%d gx=%d idle=%d\n", e.name, N, cls, 1 << q.lg, q.grid_x, (q.grid_x << q.lg) - N / q.V);
         }
     std::printf("limits | TRAIN_MAX_C=%d TRAIN_ROWS=%d PW_MAX_H=%d PW_ROWS=%d\n", TRAIN_MAX_C, TRAIN_ROWS, PW_MAX_H, PW_ROWS);
+    // gn_act: the class depends on C, the layout and the element type alone; G = 4 divides every C.  ws = the workspace bytes of the parity map
+    // (2, 9, 7) at G = 4, gy = column (channel) tiles, unit = the most pixels of a unit (what a map of TRAIN_ROWS such units or more takes)
+    for (const Etype& e : ETYPES)
+        for (int nchw = 0; nchw < 2; ++nchw)
+            for (int C = 4; C <= TRAIN_MAX_C; C += 4) {
+                const GnPlan q = gn_plan(2, 9, 7, C, 4, e.esize, nchw);
+                gn_plan_class(q, e.name, cls, sizeof(cls));
+                std::printf("gn_act %s %s %d | %s | gy=%d unit=%d ws=%zu\n", nchw ? "nchw" : "cl", e.name, C, cls, q.grid_y, nchw ? GN_UNIT_NCHW : GN_UNIT_CL,
+                            gn_plan_workspace_bytes(2, 9, 7, C, 4));
+            }
     return 0;
 }
 
@@ -335,8 +429,10 @@ int main(int argc, char** argv) {
     const long long pw = sweep_pw();
     std::printf("pw_mlp: %lld plans over %zu row counts x N = 4, 8, ..., %d x both vector widths, as the first and as the second sum\n", pw,
                 sizeof(PW_M) / sizeof(PW_M[0]), PW_MAX_H);
+    const long long gn = sweep_gn();
+    std::printf("gn_act: %lld plans over the same maps, widths, element types and layouts x G = 1, 2, 4, 16, 32, C, C / 4, C / 6, C / 12 where they divide C\n", gn);
     check_sizes();
-    std::printf("workspace sizes: 0 exactly where train_shape_ok / pw_shape_ok refuses\n");
+    std::printf("workspace sizes: 0 exactly where train_shape_ok / pw_shape_ok / gn_shape_ok refuses\n");
     std::printf("each condition bites: %d deliberately wrong plans refused\n", check_that_conditions_bite());
     std::printf("train_plan_check: OK\n");
     return 0;

@@ -560,6 +560,22 @@ size_t uni_pw_mlp_workspace_bytes(int M, int Hd, int Co) { return pw_mlp_workspa
         API(launch_pw_mlp_act_bwd<T>(args, workspace, workspace_bytes, S(stream)));                                                                \
     }
 UNI_PAIR(DEF_PW_MLP)
+size_t uni_gn_act_train_workspace_bytes(int B, int H, int W, int C, int G) { return gn_act_train_workspace_bytes(B, H, W, C, G); }
+#define DEF_GN_ACT_TRAIN(SFX, T)                                                                                                                   \
+    int uni_gn_act_train_fwd##SFX(const void* x, int x_dtype, int nchw, const T* weight, const T* bias, double eps, int act, int B, int H, int W,  \
+                                  int C, int G, T* y, T* stats, uni_stream_t stream) {                                                             \
+        UNI_REQUIRE(x && weight && bias && y && stats, "gn_act_train_fwd" #SFX ": NULL argument");                                                 \
+        const GnArgs<T> a{x, x_dtype, nchw, weight, bias, eps, act, B, H, W, C, G};                                                                \
+        API(launch_gn_act_train_fwd<T>(a, y, stats, S(stream)));                                                                                   \
+    }                                                                                                                                              \
+    int uni_gn_act_train_bwd##SFX(const void* x, int x_dtype, int nchw, const T* weight, const T* bias, const T* stats, const T* grad_y, int act,  \
+                                  int B, int H, int W, int C, int G, void* grad_x, T* grad_weight, T* grad_bias, void* workspace,                  \
+                                  size_t workspace_bytes, uni_stream_t stream) {                                                                   \
+        UNI_REQUIRE(x && weight && bias && stats && grad_y, "gn_act_train_bwd" #SFX ": NULL argument");                                            \
+        const GnArgs<T> a{x, x_dtype, nchw, weight, bias, 0.0, act, B, H, W, C, G};                                                                \
+        API(launch_gn_act_train_bwd<T>(a, stats, grad_y, grad_x, grad_weight, grad_bias, workspace, workspace_bytes, S(stream)));                  \
+    }
+UNI_PAIR(DEF_GN_ACT_TRAIN)
 
 // F.interpolate(scale_factor = 1/r): output size floor(in * (1/r)), source scale (float)(1 / (1/r)) (ATen compute_scales_value)
 static void resize_geometry(int Hn, int Wn, double r, int* ho, int* wo, float* rscale) {

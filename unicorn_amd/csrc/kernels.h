@@ -408,6 +408,28 @@ template <typename T>
 int launch_pw_mlp_act_fwd(const void* h, int h_dtype, int M, int Hd, void* a, hipStream_t s);
 template <typename T>
 int launch_pw_mlp_act_bwd(const PwBwdArgs<T>& a, void* ws, size_t ws_bytes, hipStream_t s);
+// gn_act_train.hip: GroupNorm + activation for TRAINING (network_blocks.py:29-51 after convert_bn_model_to_gn: act(bn(conv(x))) with bn =
+// GroupNorm(16, C, eps=1e-3); the CondInst mask branch; unicorn.py:38): y = act((x - mean) * rstd * w[c] + bias[c]) with the statistics of every
+// (sample, group), forward + backward (xhat, z and act'(z) are recomputed), fp32 (x / grad_x fp32, fp16 or bf16) and fp64, at most three launches
+// forward and three backward, no host read-back, no atomics.  x, y, gy, gx are (B, C, H, W) maps in channels-last memory or, with nchw != 0,
+// NCHW-contiguous, all four in the same layout; y and gy have the type T, gx the type of x; stats [B G][2] (mean, rstd).  act: 0 none, 1 ReLU,
+// 3 SiLU.  The forward keeps its partial statistics in y until the last launch overwrites it.  gx and the pair gw / gb may be NULL (not computed).
+// train_shape_ok(B, H, W, C), 1 <= G <= C, C % G == 0.  Workspace (every backward): gn_act_train_workspace_bytes for fp32, twice that for fp64.
+size_t gn_act_train_workspace_bytes(int B, int H, int W, int C, int G);
+template <typename T>
+struct GnArgs {
+    const void* x;
+    int x_dtype;                                // 0: the type T, 1 fp16, 2 bf16 (fp32 form only)
+    int nchw;
+    const T *w, *bias;
+    double eps;                                 // forward only (the backward reads rstd)
+    int act;
+    int B, H, W, C, G;
+};
+template <typename T>
+int launch_gn_act_train_fwd(const GnArgs<T>& a, T* y, T* stats, hipStream_t s);
+template <typename T>
+int launch_gn_act_train_bwd(const GnArgs<T>& a, const T* stats, const T* gy, void* gx, T* gw, T* gb, void* ws, size_t ws_bytes, hipStream_t s);
 // post.hip: utils/boxes.py:33-77 on the device (corners in place, conf filter, (batched) NMS, sorted survivor rows)
 int launch_letterbox(const unsigned char* img, int h, int w, int swap_rb, int H, int W, float* out, double* r_out, hipStream_t s);
 size_t postprocess_workspace_bytes(int A);

@@ -1,4 +1,4 @@
-// What the four ConvNeXt training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, pw_mlp.hip) share and that needs HIP: the refusal
+// What the training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, pw_mlp.hip, gn_act_train.hip) share and that needs HIP: the refusal
 // of a shape, the host helpers of their launchers, the converting 16-byte vector access and the ordered reduce of per-block partial sums.  Plain
 // functions.  The shape limits and the launch plans are in train_plan.h, which compiles for the host alone.
 #pragma once

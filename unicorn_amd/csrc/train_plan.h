@@ -1,4 +1,4 @@
-// How a shape maps to a launch in the four ConvNeXt training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, pw_mlp.hip): the shape
+// How a shape maps to a launch in the training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, pw_mlp.hip, gn_act_train.hip): the shape
 // limits, the vector width, the lane mapping, grid, block, dynamic LDS, the rows of partial sums and the workspace that holds them -- stated
 // here and nowhere else.  Plain C++17, no HIP: the launchers read these plans, tools/train_plan_check.cpp checks them over the admitted
 // domain and prints them, tests/train_plans.py answers from that listing.  Retune a plan here; the check program says what it breaks.
@@ -200,3 +200,75 @@ static inline void pw_plan_class(const PwPlan& q, const char* en, char* buf, siz
 }
 // two sums: [PW_ROWS][Hd] at 0, [PW_ROWS][Co] behind it
 static inline size_t pw_plan_workspace_bytes(int M, int Hd, int Co) { return pw_shape_ok(M, Hd, Co) ? (size_t)4 * PW_ROWS * ((size_t)Hd + Co) : 0; }
+
+// ---------------------------------------------------------------------------------------------------------------- gn_act_train
+constexpr int GN_UNIT_CL = 256;                 // gn_act: most pixels of a unit (consecutive pixels of ONE image), channels-last memory
+constexpr int GN_UNIT_CL_MIN = 16;              // ... fewest: small maps take short units, so that about GN_ROWS_CL rows of blocks share the pixels
+constexpr int GN_ROWS_CL = 512;                 // gn_act, channels-last: the rows in all that the choice of the unit aims for
+constexpr int GN_RED_COLS = 16;                 // gn_act, combine launch: columns of [2 C] per block (and 256 / 16 slices of rows)
+constexpr int GN_UNIT_NCHW = 512;               // ... NCHW memory
+constexpr int GN_COMB_BLOCKS = 65536;           // gn_act, combine launches: at most this many blocks walk the (sample, group) pairs
+constexpr int GN_NCHW_CT = 16;                  // gn_act, NCHW path: channels of a block (four waves, a wave takes one channel at a time)
+static inline bool gn_shape_ok(int B, int H, int W, int C, int G) { return train_shape_ok(B, H, W, C) && G >= 1 && G <= C && C % G == 0; }
+// pixels of the units r, r + rpi, r + 2 rpi, ... < upi of an image of HW pixels (the last unit may be short); callable from a kernel.  The row
+// count holds what does not depend on r, so that a loop over rows divides nothing.
+struct GnRowCount {
+    long long full, cut;                        // pixels of upi / rpi whole units; what the last unit lacks
+    unsigned rem;                               // rows r < rem take one unit more
+    int last, unit;                             // the row of the last unit
+};
+constexpr GnRowCount gn_row_count(long long HW, int unit, unsigned upi, int rpi) {
+    return GnRowCount{(long long)(upi / (unsigned)rpi) * unit, (long long)upi * unit - HW, upi % (unsigned)rpi, (int)((upi - 1) % (unsigned)rpi), unit};
+}
+constexpr long long gn_row_pixels(const GnRowCount& c, int r) { return c.full + ((unsigned)r < c.rem ? c.unit : 0) - (r == c.last ? c.cut : 0); }
+constexpr long long gn_row_pixels(long long HW, int unit, unsigned upi, int rpi, int r) { return gn_row_pixels(gn_row_count(HW, unit, upi, rpi), r); }
+struct GnPlan {
+    bool nchw;
+    int V, lg;                                  // channels-last: channels per vector, L = 2^lg lanes (vectors) per pixel of a block, 256 / L pixels per step
+    int unit;                                   // pixels of a unit
+    unsigned upi;                               // units per image
+    int rpi, rows;                              // rows of partials per image (block r of an image takes the units r, r + rpi, ...), in all (= B rpi)
+    int planes;                                 // forward: planes [C] of a row of partials: mean and M2, or the mean alone where H W == 1 (M2 = 0)
+    int grid_x, grid_y, block;                  // rows; column tiles of L vectors (channels-last) or of GN_NCHW_CT channels (NCHW)
+    unsigned comb_blocks;                       // the two combine launches: blocks that walk the B G (sample, group) pairs, a block each
+    size_t off_ab, elems;                       // workspace (elements): partials [rows][2][C] at 0, the group sums [B G][2] at off_ab
+};
+// A block belongs to one image: rows = B rpi with rpi = min(units per image, max(1, TRAIN_ROWS / B)), so at most max(B, TRAIN_ROWS) rows.
+// Channels-last units are as short as that cap allows (a (2, C, 25, 40) map in units of 256 pixels is 8 rows of blocks on 256 compute units).
+// Channels-last: the lane mapping of pw_plan over the C / V vectors of a pixel.  NCHW: a wave reads 64 consecutive pixels of a channel plane.
+static inline GnPlan gn_plan(int B, int H, int W, int C, int G, int esize, bool nchw) {
+    GnPlan q{};
+    const long long HW = (long long)H * W;
+    q.nchw = nchw;
+    q.unit = nchw ? GN_UNIT_NCHW : GN_UNIT_CL_MIN;
+    while (!nchw && q.unit < GN_UNIT_CL && (long long)q.unit * GN_ROWS_CL < B * HW) q.unit <<= 1;      // the power of two >= B H W / GN_ROWS_CL in [16, 256]
+    q.upi = (unsigned)plan_cdiv(HW, q.unit);
+    const int cap = TRAIN_ROWS / B > 1 ? TRAIN_ROWS / B : 1;
+    q.rpi = train_rows(q.upi, cap);
+    q.rows = B * q.rpi;                         // <= max(B, TRAIN_ROWS) < 2^31
+    q.planes = HW == 1 ? 1 : 2;
+    q.grid_x = q.rows;
+    q.block = 256;
+    if (nchw) {
+        q.V = 1;
+        q.grid_y = (int)plan_cdiv(C, GN_NCHW_CT);
+    } else {
+        const PwPlan w = pw_plan(1, C, esize);
+        q.V = w.V, q.lg = w.lg, q.grid_y = w.grid_x;
+    }
+    const long long pairs = (long long)B * G;
+    q.comb_blocks = (unsigned)(pairs < GN_COMB_BLOCKS ? pairs : GN_COMB_BLOCKS);
+    q.off_ab = ((size_t)q.rows * 2 * C + 63) / 64 * 64;
+    q.elems = q.off_ab + (size_t)B * G * 2;
+    return q;
+}
+// `cl<f16,V=8> L=16`, `nchw<f32> CT=16`
+static inline void gn_plan_class(const GnPlan& q, const char* en, char* buf, size_t n) {
+    if (q.nchw) std::snprintf(buf, n, "nchw<%s> CT=%d", en, GN_NCHW_CT);
+    else std::snprintf(buf, n, "cl<%s,V=%d> L=%d", en, q.V, 1 << q.lg);
+}
+// counted in fp32 elements (the fp64 launchers need twice the bytes) from the channels-last plan: it has the shorter units, so the more rows
+static inline size_t gn_plan_workspace_bytes(int B, int H, int W, int C, int G) {
+    static_assert(GN_UNIT_CL <= GN_UNIT_NCHW, "the workspace is sized by the channels-last plan");
+    return gn_shape_ok(B, H, W, C, G) ? 4 * gn_plan(B, H, W, C, G, 4, false).elems : 0;
+}

@@ -31,7 +31,11 @@ fuse_pw_mlp(model, keep) routes the point-wise middle of the block (convnext.py:
 through unicorn_amd.ops.pw_mlp, which keeps one hidden map (keep="hidden") or none (keep="input") for the backward where the eager lines keep
 two.  The technique is that of fuse_dwconv_ln: pwconv1 and act get instance-level `forward`s that hand their input on unchanged, pwconv2 one
 that runs the operator with both Linears' parameters, so the block's own forward and fuse_block_tail's work unmodified.  fuse_backbone_mlp
-applies all four."""
+applies all four.
+
+fuse_groupnorm_act(model) routes the GroupNorm + SiLU / ReLU lines behind the backbone (BaseConv of the YOLOX-PAFPN and of the head after
+convert_bn_model_to_gn, network_blocks.py:29-51; the CondInst mask branch; unicorn.py:38) through unicorn_amd.ops.group_norm_act by the same
+technique: the norm runs the operator with the activation, the activation module hands its input on.  fuse_model applies all five."""
 import torch
 
 from . import ops
@@ -317,3 +321,97 @@ def fuse_backbone_mlp(model, keep="hidden"):
     """fuse_backbone + fuse_pw_mlp -> (blocks whose opening is fused, blocks whose close is fused, channels-first norms fused, blocks whose
     point-wise middle is fused): a fused block then runs no eager point-wise line"""
     return fuse_backbone(model) + (fuse_pw_mlp(model, keep),)
+
+
+class _FusedGroupNormAct:
+    """instance-level `forward` of a GroupNorm (`role` 0: runs ops.group_norm_act with the activation `act`, which may be None) or of the
+    activation module behind it (`role` 1: hands its input on unchanged)"""
+    __slots__ = ("norm", "act", "role")
+
+    def __init__(self, norm, act, role):
+        self.norm, self.act, self.role = norm, act, role
+
+    def __call__(self, x):
+        n, a = self.norm, self.act
+        m = a if self.role else n
+        if not (n.training and (a is None or a.training) and isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_cuda):
+            return type(m).forward(m, x)
+        if self.role:
+            return x
+        return ops.group_norm_act(x, n.num_groups, n.weight, n.bias, n.eps, _gn_act_name(a))
+
+
+def _gn_act_name(a):
+    return "none" if a is None else "silu" if isinstance(a, torch.nn.SiLU) else "relu"
+
+
+def _gn_fusable(m):
+    if not isinstance(m, torch.nn.GroupNorm) or not m.affine or m.weight is None or m.bias is None:
+        return False
+    Cc = m.num_channels
+    return Cc % 4 == 0 and 4 <= Cc <= ops.TRAIN_MAX_C and isinstance(m.__dict__.get("forward"), (_FusedGroupNormAct, type(None)))
+
+
+def _gn_pairs(model):
+    """[(norm, activation module or None)] of the three patterns of fuse_groupnorm_act, every norm once, in the order of model.modules()"""
+    seen = {}
+    for _, m in model.named_modules(remove_duplicate=False):
+        seen[id(m)] = seen.get(id(m), 0) + 1
+    pairs, done = [], set()
+
+    def add(norm, act):
+        if id(norm) in done or not _gn_fusable(norm):
+            return
+        done.add(id(norm))
+        ok = (isinstance(act, (torch.nn.SiLU, torch.nn.ReLU)) and seen[id(norm)] == 1 and seen[id(act)] == 1
+              and isinstance(act.__dict__.get("forward"), (_FusedGroupNormAct, type(None))))
+        pairs.append((norm, act if ok else None))
+
+    for m in model.modules():
+        if isinstance(m, torch.nn.Sequential):
+            kids = list(m)
+            for i, k in enumerate(kids):
+                if isinstance(k, torch.nn.GroupNorm):
+                    add(k, kids[i + 1] if i + 1 < len(kids) else None)
+        elif isinstance(getattr(m, "bn", None), torch.nn.GroupNorm) and isinstance(getattr(m, "act", None), torch.nn.Module):
+            add(m.bn, m.act)
+    return pairs
+
+
+def fuse_groupnorm_act(model):
+    """Route the GroupNorm + activation lines of `model` through unicorn_amd.ops.group_norm_act, which keeps x and two numbers per (sample,
+    group) for the backward where the eager lines keep two or three maps.  Three patterns are fused:
+      - a module with the children `bn` (nn.GroupNorm) and `act` (nn.SiLU or nn.ReLU, in place or not) that runs act(bn(conv(x))): BaseConv
+        (network_blocks.py:29-51) after convert_bn_model_to_gn;
+      - inside an nn.Sequential, a GroupNorm directly followed by nn.SiLU / nn.ReLU (the CondInst mask branch);
+      - a GroupNorm that ends an nn.Sequential or is followed there by anything else (unicorn.py:38): act="none".
+    A norm qualifies with affine parameters, C % 4 == 0 and 4 <= C <= 2048; other norms are left alone.  The norm gets an instance-level
+    `forward` that runs the operator WITH the activation, the activation module one that hands its input on unchanged; both call their module's
+    own forward outside training mode, for CPU tensors and for input that is not 4-D.  The activation module is made the identity only if
+    that module object (and the norm) occurs exactly once in model.named_modules(remove_duplicate=False) and it carries no instance-level
+    forward of somebody else's; otherwise, and for LeakyReLU and every other activation, the norm alone is fused (act="none") and the activation
+    stays eager.  So a forward hook on a fused activation sees the ACTIVATED tensor as its input.  Module tree, parameter names and
+    state_dict() stay as they were; copy.deepcopy(model) gives a copy that uses the copy's parameters.  Returns the number of norms fused
+    (norms fused earlier are counted)."""
+    pairs = _gn_pairs(model)
+    for norm, act in pairs:
+        norm.forward = _FusedGroupNormAct(norm, act, 0)
+        if act is not None:
+            act.forward = _FusedGroupNormAct(norm, act, 1)
+    return len(pairs)
+
+
+def unfuse_groupnorm_act(model):
+    """Remove what fuse_groupnorm_act set; returns the number of norms restored."""
+    n = 0
+    for m in model.modules():
+        f = m.__dict__.get("forward")
+        if isinstance(f, _FusedGroupNormAct):
+            del m.__dict__["forward"]
+            n += f.role == 0
+    return n
+
+
+def fuse_model(model, keep="hidden"):
+    """fuse_backbone_mlp + fuse_groupnorm_act -> the four counts of fuse_backbone_mlp and the number of GroupNorms fused"""
+    return fuse_backbone_mlp(model, keep) + (fuse_groupnorm_act(model),)

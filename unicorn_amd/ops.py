@@ -1198,6 +1198,99 @@ def layernorm_cf(x, weight, bias, eps=1e-6):
     return LayerNormCFFunction.apply(x, weight.contiguous(), bias.contiguous(), float(eps))
 
 
+GN_ACT = {"none": 0, "relu": 1, "silu": 3}       # the activation codes of the engine
+
+
+class GroupNormActFunction(torch.autograd.Function):
+    """GroupNorm followed by an activation (network_blocks.py:29-51 after convert_bn_model_to_gn): apply(x (N,C,H,W), weight (C,), bias (C,),
+    num_groups, eps, act code) -> y (N,C,H,W) in the memory layout of x; x fp32 / fp16 / bf16 with fp32 weight and bias -> y fp32, or all fp64
+    (ops.group_norm_act checks).  Channels-last and NCHW-contiguous memory of x are read in place, anything else is converted once to
+    channels-last; grad_out is read in place when it has the layout of x.  Saves x, weight, bias and the (N G, 2) statistics, never y or a
+    normalised map: the backward recomputes xhat, z and act'(z).  x.grad has the dtype and layout of x; only what autograd asks for is computed.
+    No host synchronisation, one writer per element: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, num_groups, eps, act):
+        N, Cc, H, W = x.shape
+        ctx.dims = (N, Cc, H, W, num_groups, act)
+        out_dtype = torch.promote_types(x.dtype, weight.dtype)
+        xc, nchw = _map_layout(x)
+        ctx.nchw = nchw
+        y = _lncf_like(xc, nchw, out_dtype)
+        if N == 0:
+            ctx.save_for_backward(xc, weight, bias)
+            return y
+        stats = torch.empty((N * num_groups, 2), device=x.device, dtype=out_dtype)
+        fn, name = _entry("uni_gn_act_train_fwd", out_dtype)
+        with torch.cuda.device(x.device):
+            L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], nchw, L.ptr(weight), L.ptr(bias), float(eps), act, N, H, W, Cc, num_groups, L.ptr(y),
+                       L.ptr(stats), L.stream_ptr()), name)
+        ctx.save_for_backward(xc, weight, bias, stats)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        N, Cc, H, W, G, act = ctx.dims
+        nchw = ctx.nchw
+        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        xc, weight, bias = ctx.saved_tensors[:3]
+        gx = _lncf_like(xc, nchw, xc.dtype) if need_x else None
+        gw = torch.empty_like(weight) if need_p else None
+        gb = torch.empty_like(weight) if need_p else None
+        if N == 0:
+            if need_p:
+                gw.zero_(), gb.zero_()
+        elif need_x or need_p:
+            stats = ctx.saved_tensors[3]
+            g = grad_out.contiguous() if nchw else grad_out.contiguous(memory_format=torch.channels_last)       # no copy in the layout of x
+            fn, name = _entry("uni_gn_act_train_bwd", weight.dtype)
+            with torch.cuda.device(xc.device):
+                need = L.lib().uni_gn_act_train_workspace_bytes(N, H, W, Cc, G)
+                if need == 0:
+                    raise L.UnicornHipError("group_norm_act: shape N=%d C=%d H=%d W=%d G=%d is outside the limits of uni_gn_act_train_bwd "
+                                            "(include/unicorn_hip.h)" % (N, Cc, H, W, G))
+                ws = torch.empty(need * _ws_factor(weight.dtype), device=xc.device, dtype=torch.uint8)
+                L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], nchw, L.ptr(weight), L.ptr(bias), L.ptr(stats), L.ptr(g), act, N, H, W, Cc, G, L.ptr(gx),
+                           L.ptr(gw), L.ptr(gb), L.ptr(ws), ws.numel(), L.stream_ptr()), name)
+        return gx, gw if ctx.needs_input_grad[1] else None, gb if ctx.needs_input_grad[2] else None, None, None, None
+
+
+def group_norm_act(x, num_groups, weight, bias, eps=1e-5, act="silu"):
+    """act(F.group_norm(x, num_groups, weight, bias, eps)) as one operator, equal in value and in all three gradients: mean and biased
+    variance over the (C / num_groups) H W elements of every (sample, group), z = (x - mean) / sqrt(var + eps) * weight[c] + bias[c], y = z
+    (act="none"), max(z, 0) ("relu") or z * sigmoid(z) ("silu").
+      x             (N, C, H, W) fp32, fp16 or bf16; read in the dtype it has (no cast under autocast).  Channels-last memory and
+                    NCHW-contiguous memory (what a convolution returns) are read in place, any other strides are converted once to channels-last
+      num_groups    1 <= num_groups <= C, C % num_groups == 0; C / num_groups need not be a multiple of 4
+      weight, bias  (C,) fp32
+    All three fp64 is accepted for checks.  Returns y of the shape of x in the MEMORY LAYOUT of x (of its channels-last copy for other
+    strides), dtype torch.promote_types(x.dtype, weight.dtype): fp32 (fp64), what the eager lines return with or without autocast.
+    Gradients: x.grad in the dtype and layout of x, weight.grad and bias.grad (C,); grad_out is read in place when it has the layout of x,
+    otherwise it is converted once.  Autograd keeps x, weight, bias and two numbers per (sample, group), neither y nor a normalised map.
+    C % 4 == 0, 4 <= C <= 2048.  N == 0 returns an empty tensor without a library call."""
+    names = ("x", "weight", "bias")
+    ts = (x, weight, bias)
+    _check_tensors("group_norm_act", names, ts)
+    N, Cc, H, W = _check_map_dims("group_norm_act", "x", x)
+    _check_channel_vecs("group_norm_act", names[1:], ts[1:], Cc)
+    _check_train_shape("group_norm_act", N, Cc, H, W)
+    if isinstance(num_groups, bool) or not isinstance(num_groups, int) or not 1 <= num_groups <= Cc or Cc % num_groups:
+        raise L.UnicornHipError("group_norm_act: num_groups = %r is not an integer in [1, C] that divides C = %d" % (num_groups, Cc))
+    _check_eps("group_norm_act", eps)
+    if act not in GN_ACT:
+        raise L.UnicornHipError("group_norm_act: act = %r is not one of %s" % (act, ", ".join(repr(k) for k in GN_ACT)))
+    if x.dtype == torch.float64:
+        ok = weight.dtype == bias.dtype == torch.float64
+    else:
+        ok = x.dtype in _STORE_DTYPE and weight.dtype == bias.dtype == torch.float32
+    if not ok:
+        raise L.UnicornHipError("group_norm_act: dtypes %s unsupported (x fp32 / fp16 / bf16 with weight, bias fp32; or all fp64)"
+                                % ", ".join(str(t.dtype) for t in ts))
+    _check_one_device("group_norm_act", ts)
+    return GroupNormActFunction.apply(x, weight.contiguous(), bias.contiguous(), num_groups, float(eps), GN_ACT[act])
+
+
 PW_MLP_MAX_H = 4 * TRAIN_MAX_C
 PW_MLP_KEEP = ("hidden", "input")
 
