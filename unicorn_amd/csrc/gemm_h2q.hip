@@ -32,6 +32,9 @@ constexpr int STAGE = 4 * HALF;                  // A0 A1 B0 B1 of one K step
 constexpr int OPER = 2 * STAGE;
 constexpr int STG = 4096;                        // per-wave epilogue staging block
 constexpr int LDS_BYTES = OPER + NW * STG;       // 163840 = all of the CU's LDS
+// epilogue: per-lane byte offset of a column past N.  Every descriptor of the epilogue holds < 2^30 bytes (gemm_h2q_supported) and the row
+// steps added to the offset stay below 2^30 as well, so the sum is beyond num_records and never overflows an int.
+constexpr int EPI_OUT_OF_RANGE = 0x40000000;
 
 struct Tile { int m0, n0, k0, split; };      // k0: first K step of the unit (split-K), split: index of its K range
 // A side of a tile: buffer descriptor + per-lane offsets [half][piece]; CONV: byte offset (< 2^26, launcher checks) | validity bits << 26.
@@ -41,6 +44,21 @@ struct ATile { __amdgpu_buffer_rsrc_t rs; int vo[2][2]; };
 __device__ __forceinline__ Tile tile_of(int u, int nbm, int nbn, int nku) {
     const SplitTilePos t = supertile_split_pos(u, nbm, nbn, BM, BN);
     return {t.bm, t.bn, t.split * nku, t.split};
+}
+// h2_split (common.h) of two values at once, for the epilogue: hi = the packed conversion of the clamped pair, and the difference
+// c - float(hi) taken by v_fma_mix_f32, which reads the f16 half directly (fma(float(hi), -1, c) is that difference exactly; written in
+// C++ it is folded back into a conversion and a subtraction, hence the instruction by name).  One instruction per value in place of a
+// conversion back to fp32 plus a (packed) subtraction.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void h2_split2(float x0, float x1, f16x2& hi, f16x2& lo) {
+    const f32x2 c = {__builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f)};
+    hi = __builtin_convertvector(c, f16x2);
+    const unsigned hp = __builtin_bit_cast(unsigned, hi);
+    f32x2 d;
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d[0]) : "v"(hp), "v"(c[0]));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d[1]) : "v"(hp), "v"(c[1]));
+    lo = __builtin_convertvector(d, f16x2);
 }
 }  // namespace
 
@@ -262,15 +280,11 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
         const int nw0 = done.n0 + wc * 64;
         const int rb0 = done.m0 + grp * 128;
         const int srow = p.splitk > 1 ? done.split * p.M : 0;     // split-K: outF is the slab [splitk][M][N], this unit's K range owns slab `split`
-        if (p.dbg & 16) {                             // ablation: no drain, accumulators kept live
-            float sacc = 0.f;
+        if (p.dbg & 16) {                             // ablation: no drain, accumulators kept live (an empty statement that reads them)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sacc += acc[i][j][r];
-            if (sacc == 1.2345e-30f && p.outF) p.outF[0] = sacc;
+                for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[i][j]));
             continue;
         }
         if (STATS) {
@@ -285,14 +299,49 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
                     for (int r = 0; r < 16; ++r) acc[i][j][r] *= p.wscale;
         }
         const float ws = STATS ? 1.f : p.wscale;
-        // bias of the wave's 64 columns through SCALAR loads (constant address space): SMEM does not sit on the vector-memory
-        // counter, so no wait of the epilogue drains the DMA stream or the stores behind it.  Lane (fr, fh) owns columns 8 g + 4 fh + e.
         const bool has_res = OUTF && !STATS && !CONV && p.res != nullptr, has_b = p.outB != nullptr;
+        // ---- output addressing.  Every output tensor (and the residual) gets ONE buffer descriptor per tile: base = the tile's first row,
+        // num_records = its valid rows x the row stride, so a row past M falls outside the descriptor and the hardware drops the store
+        // (a load returns zeros): no row compare, no 64-bit address per store.  A lane keeps one 32-bit byte offset per 32-column slab
+        // (its row within the wave group's first 8 / 16 rows + its column; EPI_OUT_OF_RANGE where the column is past N) and adds
+        // the scalar offset of the 8- / 16-row step.  A 256-row tile spans < 2^30 bytes (gemm_h2q_supported checks the strides).
+        // dbg & 4 (no epilogue stores): empty descriptors.
+        constexpr int OB = FMT == FMT_H2 ? 4 : 2;             // bytes per operand-format element
+        const int rows = (p.dbg & 4) ? 0 : min(BM, p.M - done.m0);
+        const int ldf4 = p.ldf * 4, ldr4 = p.ldr * 4, ldbB = p.ldb * OB;
+        const bool remap = (CONV || STATS) && p.out_hw != 0;   // outF row remap of the head outputs: plain problems never carry one (gemm_h2q_supported)
+        __amdgpu_buffer_rsrc_t rsF, rsB, rsR;
+        int voF[2], voB[2], voR[2];
+        rsB = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.outB) + (long)done.m0 * ldbB, 0, rows * ldbB, 0x00020000);
+        if (OUTF) {
+            rsF = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.outF) + (long)(done.m0 + srow) * ldf4, 0, rows * ldf4, 0x00020000);
+            rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.res)) + (long)done.m0 * ldr4, 0, has_res ? rows * ldr4 : 0, 0x00020000);
+            const int c = lane & 7, rl = grp * 128 + (lane >> 3);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int col = nw0 + j * 32 + 4 * c;
+                const bool cok = col < p.N;
+                voF[j] = cok ? rl * ldf4 + col * 4 : EPI_OUT_OF_RANGE;
+                voR[j] = cok ? rl * ldr4 + col * 4 : EPI_OUT_OF_RANGE;
+                // operand-format copy of 4 channels: f16x2 = the hi quad of the 32-byte group, its lo quad 16 bytes behind; bf16 = 8 bytes
+                voB[j] = cok ? rl * ldbB + (FMT == FMT_H2 ? (col >> 3) * 32 + (col & 7) * 2 : col * 2) : EPI_OUT_OF_RANGE;
+            }
+        } else {
+            const int c = lane & 3, rl = grp * 128 + (lane >> 2);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int col = nw0 + j * 32 + 8 * c;
+                voB[j] = col < p.N ? rl * ldbB + col * OB : EPI_OUT_OF_RANGE;
+            }
+        }
+        // bias of the wave's 64 columns through SCALAR loads (constant address space): SMEM does not sit on the vector-memory
+        // counter, so no wait of the epilogue drains the DMA stream or the stores behind it.  Lane (fr, fh) owns columns 8 g + 4 fh + e:
+        // the two quads of a group are loaded as two vectors, so the lane's choice is ONE select per value (a select between elements of
+        // one 8-float vector becomes a dynamic index, which hipcc expands into a chain of seven compares and selects per value).
 #pragma unroll
         for (int j = 0; j < 2; ++j) {                  // 32-column slab of the wave tile: its bias once, then the four 32-row blocks
             float bv[16];
             {
-                typedef float f32x8 __attribute__((ext_vector_type(8)));
                 const __attribute__((address_space(4))) float* bias = (const __attribute__((address_space(4))) float*)(p.bias);
                 if (!p.bias) {
 #pragma unroll
@@ -300,9 +349,13 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
                 } else if (nw0 + 64 <= p.N) {                   // uniform
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const f32x8 b8 = *reinterpret_cast<const __attribute__((address_space(4))) f32x8*>(bias + nw0 + j * 32 + 8 * g);
+                        const f32x4 lo = *reinterpret_cast<const __attribute__((address_space(4))) f32x4*>(bias + nw0 + j * 32 + 8 * g);
+                        const f32x4 hi = *reinterpret_cast<const __attribute__((address_space(4))) f32x4*>(bias + nw0 + j * 32 + 8 * g + 4);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) bv[4 * g + e] = fh ? b8[4 + e] : b8[e];
+                        for (int e = 0; e < 4; ++e) {
+                            bv[4 * g + e] = fh ? hi[e] : lo[e];
+                            asm("" : "+v"(bv[4 * g + e]));      // a plain register value: hipcc then pairs the activation's fp32 arithmetic (v_pk_*) as before
+                        }
                     }
                 } else {                                        // ragged last N tile: clamped element loads
 #pragma unroll
@@ -320,14 +373,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
                 // residual rows of this 32 x 32 block requested first: their latency hides under the activation + staging below
                 f32x4 rv[4];
                 if (has_res) {
-                    const int c = lane & 7, rr = lane >> 3;
-                    const int col = nw0 + j * 32 + 4 * c;
 #pragma unroll
-                    for (int tt = 0; tt < 4; ++tt) {
-                        const int row = rb0 + i * 32 + tt * 8 + rr;
-                        const bool ok = row < p.M && col < p.N;
-                        rv[tt] = *reinterpret_cast<const f32x4*>(p.res + (ok ? (size_t)row * p.ldr + col : 0));
-                    }
+                    for (int tt = 0; tt < 4; ++tt)
+                        rv[tt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, voR[j] + (i * 32 + tt * 8) * ldr4, 0, 0));
                 }
                 // fp32 [32 rows][32 cols] of block (i, j): 128-B rows, float4 chunks XOR-swizzled with row & 7
 #pragma unroll
@@ -340,43 +388,54 @@ __global__ __launch_bounds__(64 * NW) void gemm_h2q_kernel(GemmArgs p) {
                 wave_lds_fence();
                 if (OUTF) {        // fp32 (+ residual) output, optional operand-format copy: 4 channels per lane, 8 rows per instruction
                     const int c = lane & 7, rr = lane >> 3;
-                    const int col = nw0 + j * 32 + 4 * c;
 #pragma unroll
                     for (int tt = 0; tt < 4; ++tt) {
-                        const int r = tt * 8 + rr, row = rb0 + i * 32 + r;
+                        const int r = tt * 8 + rr, ro = i * 32 + tt * 8;      // ro: the step's first row within the wave group's 128
                         f32x4 v = *reinterpret_cast<const f32x4*>(st + r * 128 + ((c ^ (r & 7)) << 4));
                         if (has_res) v += rv[tt];
-                        if (row < p.M && col < p.N && !(p.dbg & 4)) {
-                            const int orow = (p.out_hw ? (row / p.out_hw) * p.out_stride + p.out_off + row % p.out_hw : row) + srow;
-                            *reinterpret_cast<f32x4*>(p.outF + (size_t)orow * p.ldf + col) = v;
-                            if (has_b) act_store4(p.outB, (size_t)row * p.ldb + col, v[0], v[1], v[2], v[3], FMT);
+                        if (remap) {           // remapped rows: one division per row, address and guards per lane
+                            const int row = rb0 + ro + rr, col = nw0 + j * 32 + 4 * c;
+                            if (row < p.M && col < p.N && !(p.dbg & 4)) {
+                                const int orow = (row / p.out_hw) * p.out_stride + p.out_off + row % p.out_hw + srow;
+                                *reinterpret_cast<f32x4*>(p.outF + (size_t)orow * p.ldf + col) = v;
+                            }
+                        } else {
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsF, voF[j] + ro * ldf4, 0, 0);
+                        }
+                        if (has_b) {           // the operand-format copy (act_store4's values at act_store4's addresses)
+                            if (FMT == FMT_H2) {
+                                f16x4 h, l;
+#pragma unroll
+                                for (int q = 0; q < 4; q += 2) { f16x2 hh, ll; h2_split2(v[q], v[q + 1], hh, ll); h[q] = hh[0]; h[q + 1] = hh[1]; l[q] = ll[0]; l[q + 1] = ll[1]; }
+                                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, h), rsB, voB[j] + ro * ldbB, 0, 0);
+                                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, l), rsB, voB[j] + ro * ldbB + 16, 0, 0);
+                            } else {
+                                const bf16x4 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+                                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rsB, voB[j] + ro * ldbB, 0, 0);
+                            }
                         }
                     }
                 } else {           // operand-format output only: 8 channels (one 32-byte [hi | lo] group) per lane, 16 rows per instruction
                     const int c = lane & 3, rr = lane >> 2;
-                    const int col = nw0 + j * 32 + 8 * c;
 #pragma unroll
                     for (int tt = 0; tt < 2; ++tt) {
-                        const int r = tt * 16 + rr, row = rb0 + i * 32 + r;
+                        const int r = tt * 16 + rr, ro = i * 32 + tt * 16;
                         const f32x4 lo = *reinterpret_cast<const f32x4*>(st + r * 128 + (((2 * c) ^ (r & 7)) << 4));
                         const f32x4 hi = *reinterpret_cast<const f32x4*>(st + r * 128 + (((2 * c + 1) ^ (r & 7)) << 4));
-                        if (row < p.M && col < p.N && !(p.dbg & 4)) {
-                            const float v8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                            // streaming (non-temporal) stores: the consumer is the next launch and the tensor (786 MB for a stage-2
-                            // pwconv1) is far larger than L2, keeping it there only evicts the operand panels of this GEMM
-                            if (FMT == FMT_H2) {
-                                f16x8 h, l;
+                        const float v8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                        // streaming (non-temporal, aux = 2) stores: the consumer is the next launch and the tensor (786 MB for a stage-2
+                        // pwconv1) is far larger than L2, keeping it there only evicts the operand panels of this GEMM
+                        if (FMT == FMT_H2) {
+                            f16x8 h, l;
 #pragma unroll
-                                for (int q = 0; q < 8; ++q) { f16 hh, ll; h2_split(v8[q], hh, ll); h[q] = hh; l[q] = ll; }
-                                char* op = reinterpret_cast<char*>(p.outB) + ((size_t)row * p.ldb + col) * 4;
-                                __builtin_nontemporal_store(__builtin_bit_cast(f32x4, h), reinterpret_cast<f32x4*>(op));
-                                __builtin_nontemporal_store(__builtin_bit_cast(f32x4, l), reinterpret_cast<f32x4*>(op + 16));
-                            } else {
-                                bf16x8 o;
+                            for (int q = 0; q < 8; q += 2) { f16x2 hh, ll; h2_split2(v8[q], v8[q + 1], hh, ll); h[q] = hh[0]; h[q + 1] = hh[1]; l[q] = ll[0]; l[q + 1] = ll[1]; }
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, h), rsB, voB[j] + ro * ldbB, 0, 2);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, l), rsB, voB[j] + ro * ldbB + 16, 0, 2);
+                        } else {
+                            bf16x8 o;
 #pragma unroll
-                                for (int q = 0; q < 8; ++q) o[q] = (bf16)v8[q];
-                                __builtin_nontemporal_store(__builtin_bit_cast(f32x4, o), reinterpret_cast<f32x4*>(p.outB + (size_t)row * p.ldb + col));
-                            }
+                            for (int q = 0; q < 8; ++q) o[q] = (bf16)v8[q];
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsB, voB[j] + ro * ldbB, 0, 2);
                         }
                     }
                 }
@@ -409,6 +468,9 @@ bool gemm_h2q_supported(const GemmArgs& a) {
     if (a.b32 != FMT_H2 && a.b32 != FMT_BF16) return false;
     const int ks = a.b32 == FMT_H2 ? 32 : 64, eb = a.b32 == FMT_H2 ? 4 : 2;
     if (!a.epi || a.K % ks != 0 || a.K < 2 * ks || a.act_col0 != 0) return false;
+    // the epilogue reaches a 256-row tile of every output / residual tensor through one buffer descriptor and 32-bit byte offsets
+    const long ldmax = std::max<long>({a.outF ? a.ldf : 0, a.outB ? a.ldb : 0, a.res ? a.ldr : 0});
+    if (BM * ldmax * 4 >= (1L << 30)) return false;
     if (!conv && !a.stats) {
         if (a.b32 != FMT_H2) return gemm_p44_supported(a);
         return a.out_hw == 0 && (a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_GELU) && (a.outF || a.outB) && (a.outF || !a.res);   // (bias optional)
