@@ -521,6 +521,60 @@ int uni_lncf_train_bwd_f64(const void* x, int x_dtype, int nchw, const double* w
                            int W, int C, void* grad_x, double* grad_weight, double* grad_bias, void* workspace, size_t workspace_bytes,
                            uni_stream_t stream);
 
+/* The four downsample layers of the ConvNeXt backbone for TRAINING (unicorn/models/backbone/convnext.py:77-87: the stem Conv2d(in_chans, C0,
+ * 4, stride=4) + channels-first LayerNorm, and three times channels-first LayerNorm + Conv2d(C, Co, 2, stride=2)).  A convolution whose kernel
+ * equals its stride is a GEMM over non-overlapping patches: the GEMMs are the caller's (the vendor library), everything around them is here.
+ * No host synchronisation, no read-back, no allocation, no atomics.  Operator only: the model-level engine stays inference only.
+ *
+ * LN to patches (uni_down_train_*)
+ *   x, grad_x   the (B, C, H, W) map in channels-last memory, dense [B][H][W][C].  x_dtype: 0 = the type of the form (fp32, fp64 in the _f64
+ *               form), 1 = fp16, 2 = bf16 (fp32 form only).  Conversion in registers, all arithmetic fp32 (fp64).
+ *   A, grad_A   the patch matrix [M][4 C] of the 2x2 / stride-2 convolution, M = B Ho Wo, Ho = H / 2, Wo = W / 2 (floor): pixel (n, h, w),
+ *               channel c is row (n Ho + h / 2) Wo + w / 2, column ((h & 1) 2 + (w & 1)) C + c, the column order of
+ *               weight.permute(0, 2, 3, 1).reshape(Co, 4 C).  a_dtype (0 / 1 / 2 as x_dtype) is its element type.  A pixel of a last row or
+ *               column that an odd H or W drops has no element in it.
+ *   weight, bias, grad_ln_weight, grad_ln_bias  [C] of the LayerNorm
+ *   stats       [B H W][2] = mean and 1 / sqrt(var + eps) of EVERY pixel
+ *   uni_down_train_fwd  rebuild == 0: mean, rstd (the variance is the mean of (x - mean)^2, a second pass over registers), z = weight *
+ *                       (x - mean) * rstd + bias rounded ONCE to the type of A.  Writes A and stats COMPLETELY.  rebuild != 0: the same
+ *                       kernel reads stats instead of computing it and writes A alone, COMPLETELY and with the bits of the forward (eps is
+ *                       then not read).  One launch.
+ *   uni_down_train_bwd  xhat = (x - mean) * rstd, t = grad_A * weight: grad_x = rstd * (t - mean_c t - xhat * mean_c (t * xhat)), written
+ *                       COMPLETELY with exact zeros at the dropped pixels, which are not read and take no part in the sums;
+ *                       grad_ln_weight[c] = sum of grad_A * xhat, grad_ln_bias[c] = sum of grad_A.  grad_x and the pair grad_ln_weight /
+ *                       grad_ln_bias may be NULL: that part is skipped (the reduce launch too when the pair is NULL; the workspace may then be
+ *                       NULL and is not touched), what is computed has the same bits as in the full call.  Both NULL: no launch, no error.  At
+ *                       most two launches.
+ *   Limits: B >= 1, H, W >= 2, C % 4 == 0, 4 <= C <= 2048, B H W < 2^31 (element offsets are 64-bit: A may pass 2^31 elements), pointers
+ *   16-byte aligned; other shapes are refused with an error string before any launch and uni_down_train_workspace_bytes returns 0 for them.
+ *   workspace (backward with the pair only): 16-byte aligned device scratch of >= uni_down_train_workspace_bytes(B, H, W, C) bytes (fp32; the
+ *   _f64 form needs twice that) = uni_lncf_train_workspace_bytes = 4 * 1024 * 2 C.  Nothing is kept in it between calls.
+ *
+ * Stem patches (uni_patch4_*), one launch each
+ *   x, grad_x   (B, Cin, H, W), NCHW-contiguous [B][Cin][H][W], element type x_dtype
+ *   A, grad_A   [M][Cin 16], M = B (H / 4) (W / 4), element type a_dtype: row as above with / 4, column (c 4 + kh) 4 + kw, the order of
+ *               weight.reshape(Co, Cin 16), so the weight needs no permutation
+ *   uni_patch4_gather   A = the patches of x, rounded once to a_dtype.  Writes A COMPLETELY.
+ *   uni_patch4_scatter  grad_x = grad_A at the same addresses, zeros in the margin that H % 4 or W % 4 drops.  Writes grad_x COMPLETELY.
+ *   Limits: B >= 1, 1 <= Cin <= 4, H, W >= 4, B H W < 2^31, pointers 16-byte aligned (W need not be a multiple of 4: x is accessed
+ *   element-wise); other shapes are refused with an error string before any launch.
+ * One writer per element, fixed summation orders (as uni_lncf_train_bwd): two calls give the same bits. */
+size_t uni_down_train_workspace_bytes(int B, int H, int W, int C);
+int uni_down_train_fwd(const void* x, int x_dtype, const float* weight, const float* bias, double eps, int B, int H, int W, int C, int rebuild,
+                       void* A, int a_dtype, float* stats, uni_stream_t stream);
+int uni_down_train_bwd(const void* x, int x_dtype, const float* weight, const float* stats, const void* grad_A, int a_dtype, int B, int H, int W,
+                       int C, void* grad_x, float* grad_ln_weight, float* grad_ln_bias, void* workspace, size_t workspace_bytes,
+                       uni_stream_t stream);
+int uni_down_train_fwd_f64(const void* x, int x_dtype, const double* weight, const double* bias, double eps, int B, int H, int W, int C,
+                           int rebuild, void* A, int a_dtype, double* stats, uni_stream_t stream);
+int uni_down_train_bwd_f64(const void* x, int x_dtype, const double* weight, const double* stats, const void* grad_A, int a_dtype, int B, int H,
+                           int W, int C, void* grad_x, double* grad_ln_weight, double* grad_ln_bias, void* workspace, size_t workspace_bytes,
+                           uni_stream_t stream);
+int uni_patch4_gather(const void* x, int x_dtype, int B, int Cin, int H, int W, void* A, int a_dtype, uni_stream_t stream);
+int uni_patch4_scatter(const void* grad_A, int a_dtype, int B, int Cin, int H, int W, void* grad_x, int x_dtype, uni_stream_t stream);
+int uni_patch4_gather_f64(const void* x, int x_dtype, int B, int Cin, int H, int W, void* A, int a_dtype, uni_stream_t stream);
+int uni_patch4_scatter_f64(const void* grad_A, int a_dtype, int B, int Cin, int H, int W, void* grad_x, int x_dtype, uni_stream_t stream);
+
 /* The point-wise middle of the ConvNeXt block's MLP for TRAINING (unicorn/models/backbone/convnext.py:46-48: x = pwconv1(x); x = act(x);
  * x = pwconv2(x) with act = nn.GELU(), the exact erf form): the GELU forward, and a backward that REBUILDS a = gelu(h) from h, so that the
  * caller keeps h (or only the input of pwconv1) instead of h and a.  The two GEMMs are the caller's (the vendor library).  One launch forward,

@@ -104,6 +104,12 @@ PROTOS = {
     "uni_lncf_train_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i, c_i]),
     "uni_lncf_train_fwd": (c_i, [C.c_void_p, c_i, c_i, c_f, c_f, C.c_double, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p]),
     "uni_lncf_train_bwd": (c_i, [C.c_void_p, c_i, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, C.c_void_p, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uni_down_train_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i, c_i]),
+    "uni_down_train_fwd": (c_i, [C.c_void_p, c_i, c_f, c_f, C.c_double, c_i, c_i, c_i, c_i, c_i, C.c_void_p, c_i, c_f, C.c_void_p]),
+    "uni_down_train_bwd": (c_i, [C.c_void_p, c_i, c_f, c_f, C.c_void_p, c_i, c_i, c_i, c_i, c_i, C.c_void_p, c_f, c_f, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    "uni_patch4_gather": (c_i, [C.c_void_p, c_i, c_i, c_i, c_i, c_i, C.c_void_p, c_i, C.c_void_p]),
+    "uni_patch4_scatter": (c_i, [C.c_void_p, c_i, c_i, c_i, c_i, c_i, C.c_void_p, c_i, C.c_void_p]),
     "uni_pw_mlp_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i]),
     "uni_pw_mlp_act_fwd": (c_i, [C.c_void_p, c_i, c_i, c_i, C.c_void_p, C.c_void_p]),
     "uni_pw_mlp_act_bwd": (c_i, [C.c_void_p, c_i, C.c_void_p, c_i, c_i, C.c_void_p, C.c_void_p, c_f, C.c_void_p, c_i, c_f, C.c_void_p, C.c_size_t,
@@ -156,7 +162,7 @@ F64_TWINS = ("uni_msda_fwd", "uni_msda_bwd", "uni_condinst_loss_fwd", "uni_condi
              "uni_head_mask_loss_fwd", "uni_head_mask_loss_bwd", "uni_mot_corr_loss_fwd", "uni_mot_corr_loss_bwd", "uni_prop_labels",
              "uni_prop_dice_pyramid_fwd", "uni_prop_dice_pyramid_bwd", "uni_dwln_train_fwd", "uni_dwln_train_bwd",
              "uni_block_tail_fwd", "uni_block_tail_bwd", "uni_lncf_train_fwd", "uni_lncf_train_bwd",
-             "uni_pw_mlp_act_fwd", "uni_pw_mlp_act_bwd", "uni_gn_act_train_fwd", "uni_gn_act_train_bwd")
+             "uni_down_train_fwd", "uni_down_train_bwd", "uni_patch4_gather", "uni_patch4_scatter", "uni_pw_mlp_act_fwd", "uni_pw_mlp_act_bwd", "uni_gn_act_train_fwd", "uni_gn_act_train_bwd")
 for _name in F64_TWINS:
     PROTOS[_name + "_f64"] = PROTOS[_name]
 

@@ -548,6 +548,30 @@ size_t uni_lncf_train_workspace_bytes(int B, int H, int W, int C) { return lncf_
         API(launch_lncf_train_bwd<T>(a, stats, grad_y, grad_x, grad_weight, grad_bias, workspace, workspace_bytes, S(stream)));                    \
     }
 UNI_PAIR(DEF_LNCF_TRAIN)
+size_t uni_down_train_workspace_bytes(int B, int H, int W, int C) { return down_train_workspace_bytes(B, H, W, C); }
+#define DEF_DOWN_TRAIN(SFX, T)                                                                                                                     \
+    int uni_down_train_fwd##SFX(const void* x, int x_dtype, const T* weight, const T* bias, double eps, int B, int H, int W, int C, int rebuild,   \
+                                void* A, int a_dtype, T* stats, uni_stream_t stream) {                                                             \
+        UNI_REQUIRE(x && weight && bias && A && stats, "down_train_fwd" #SFX ": NULL argument");                                                   \
+        const DownArgs<T> a{x, x_dtype, a_dtype, weight, bias, eps, B, H, W, C};                                                                   \
+        API(launch_down_train_fwd<T>(a, rebuild, A, stats, S(stream)));                                                                            \
+    }                                                                                                                                              \
+    int uni_down_train_bwd##SFX(const void* x, int x_dtype, const T* weight, const T* stats, const void* grad_A, int a_dtype, int B, int H, int W, \
+                                int C, void* grad_x, T* grad_ln_weight, T* grad_ln_bias, void* workspace, size_t workspace_bytes,                  \
+                                uni_stream_t stream) {                                                                                             \
+        UNI_REQUIRE(x && weight && stats && grad_A, "down_train_bwd" #SFX ": NULL argument");                                                      \
+        const DownArgs<T> a{x, x_dtype, a_dtype, weight, nullptr, 0.0, B, H, W, C};                                                                \
+        API(launch_down_train_bwd<T>(a, stats, grad_A, grad_x, grad_ln_weight, grad_ln_bias, workspace, workspace_bytes, S(stream)));              \
+    }                                                                                                                                              \
+    int uni_patch4_gather##SFX(const void* x, int x_dtype, int B, int Cin, int H, int W, void* A, int a_dtype, uni_stream_t stream) {              \
+        UNI_REQUIRE(x && A, "patch4_gather" #SFX ": NULL argument");                                                                               \
+        API(launch_patch4_gather<T>(x, x_dtype, B, Cin, H, W, A, a_dtype, S(stream)));                                                             \
+    }                                                                                                                                              \
+    int uni_patch4_scatter##SFX(const void* grad_A, int a_dtype, int B, int Cin, int H, int W, void* grad_x, int x_dtype, uni_stream_t stream) {   \
+        UNI_REQUIRE(grad_A && grad_x, "patch4_scatter" #SFX ": NULL argument");                                                                    \
+        API(launch_patch4_scatter<T>(grad_A, a_dtype, B, Cin, H, W, grad_x, x_dtype, S(stream)));                                                  \
+    }
+UNI_PAIR(DEF_DOWN_TRAIN)
 size_t uni_pw_mlp_workspace_bytes(int M, int Hd, int Co) { return pw_mlp_workspace_bytes(M, Hd, Co); }
 #define DEF_PW_MLP(SFX, T)                                                                                                                         \
     int uni_pw_mlp_act_fwd##SFX(const void* h, int h_dtype, int M, int Hd, void* a, uni_stream_t stream) {                                         \

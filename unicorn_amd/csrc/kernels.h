@@ -386,6 +386,32 @@ template <typename T>
 int launch_lncf_train_fwd(const LncfArgs<T>& a, T* y, T* stats, hipStream_t s);
 template <typename T>
 int launch_lncf_train_bwd(const LncfArgs<T>& a, const T* stats, const T* gy, void* gx, T* gw, T* gb, void* ws, size_t ws_bytes, hipStream_t s);
+// down_train.hip: the four downsample layers of the ConvNeXt backbone for TRAINING (convnext.py:77-87; the GEMMs stay with the vendor library).
+// LN to patches: the channels-first LayerNorm of x dense [B][H][W][C] (fp32, fp16 or bf16; fp64 in the fp64 form) written as the patch matrix
+// A [M][4 C] of the 2x2 / stride-2 convolution behind it (row (n Ho + h / 2) Wo + w / 2, column ((h & 1) 2 + (w & 1)) C + c; Ho = H / 2, Wo =
+// W / 2, M = B Ho Wo) in the element type a_dtype names, with stats [B H W][2]; `rebuild` reads stats and writes A alone, with the forward's
+// bits.  The backward reads gA at the same addresses and is lncf's: gx (the type of x; exact zeros at the pixels an odd H or W drops) and the
+// pair gw / gb, each may be NULL.  C % 4 == 0, 4 <= C <= 2048, H, W >= 2, B H W < 2^31.  Workspace (backward with gw / gb only):
+// down_train_workspace_bytes for fp32, twice that for fp64.
+// Stem patches: x [B][Cin][H][W] -> A [M][Cin 16] (row as above with / 4, column (c 4 + kh) 4 + kw) and back (gx written completely, zeros in
+// the margin H % 4 / W % 4 leave).  1 <= Cin <= 4, H, W >= 4, B H W < 2^31.
+size_t down_train_workspace_bytes(int B, int H, int W, int C);
+template <typename T>
+struct DownArgs {
+    const void* x;
+    int x_dtype, a_dtype;                       // 0: the type T, 1 fp16, 2 bf16 (fp32 form only)
+    const T *w, *bias;                          // bias: forward only
+    double eps;                                 // forward only (rebuild and backward read rstd)
+    int B, H, W, C;
+};
+template <typename T>
+int launch_down_train_fwd(const DownArgs<T>& a, int rebuild, void* A, T* stats, hipStream_t s);
+template <typename T>
+int launch_down_train_bwd(const DownArgs<T>& a, const T* stats, const void* gA, void* gx, T* gw, T* gb, void* ws, size_t ws_bytes, hipStream_t s);
+template <typename T>
+int launch_patch4_gather(const void* x, int x_dtype, int B, int Cin, int H, int W, void* A, int a_dtype, hipStream_t s);
+template <typename T>
+int launch_patch4_scatter(const void* gA, int a_dtype, int B, int Cin, int H, int W, void* gx, int x_dtype, hipStream_t s);
 // pw_mlp.hip: the point-wise middle of the ConvNeXt block's MLP for TRAINING (convnext.py:46-48; the GEMMs stay with the vendor library): the
 // exact GELU forward a = gelu(h) and a backward that rebuilds a from h: a and / or grad_h = grad_a * gelu'(h) and / or gb1[Hd] = the column sums of
 // the unrounded grad_h, plus gb2[Co] = the column sums of grad_y, fp32 (maps fp32, fp16 or bf16) and fp64, one launch forward and at most three

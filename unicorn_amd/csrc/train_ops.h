@@ -1,4 +1,4 @@
-// What the training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, pw_mlp.hip, gn_act_train.hip) share and that needs HIP: the refusal
+// What the training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, down_train.hip, pw_mlp.hip, gn_act_train.hip) share and that needs HIP: the refusal
 // of a shape, the host helpers of their launchers, the converting 16-byte vector access and the ordered reduce of per-block partial sums.  Plain
 // functions.  The shape limits and the launch plans are in train_plan.h, which compiles for the host alone.
 #pragma once
@@ -75,7 +75,7 @@ __device__ __forceinline__ void vec_store(E* p, const T (&v)[V]) {
     }
 }
 
-// The ordered reduce of per-block partial sums that dwln_train.hip and lncf_train.hip share: part [R][N] -> out, two jobs in one launch.
+// The ordered reduce of per-block partial sums that dwln_train.hip, lncf_train.hip and down_train.hip share: part [R][N] -> out, two jobs in one launch.
 // out[n] = sum over the R rows of part [R][N], rows in ascending order inside each of the four waves, then the waves in ascending order; double sums
 struct DwlnRJob {
     const void* part;

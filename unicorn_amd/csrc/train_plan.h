@@ -1,4 +1,4 @@
-// How a shape maps to a launch in the training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, pw_mlp.hip, gn_act_train.hip): the shape
+// How a shape maps to a launch in the training operators (dwln_train.hip, block_tail.hip, lncf_train.hip, down_train.hip, pw_mlp.hip, gn_act_train.hip): the shape
 // limits, the vector width, the lane mapping, grid, block, dynamic LDS, the rows of partial sums and the workspace that holds them -- stated
 // here and nowhere else.  Plain C++17, no HIP: the launchers read these plans, tools/train_plan_check.cpp checks them over the admitted
 // domain and prints them, tests/train_plans.py answers from that listing.  Retune a plan here; the check program says what it breaks.
@@ -80,6 +80,41 @@ static inline void lncf_plan_class(const LncfPlan& q, const char* en, char* buf,
     else std::snprintf(buf, n, "nchw<%s,%s>", en, nchw[q.family]);
 }
 static inline size_t lncf_plan_workspace_bytes(int B, int H, int W, int C) { return train_shape_ok(B, H, W, C) ? (size_t)4 * TRAIN_ROWS * 2 * C : 0; }
+
+// ---------------------------------------------------------------------------------------------------------------- down_train
+constexpr int P4_MAX_CIN = 4;                   // stem patches: most input channels
+constexpr int P4_BLOCKS = 1 << 16;              // stem patches: at most this many blocks walk the units
+// the LayerNorm in front of a 2x2 / stride-2 convolution walks its input map as lncf's channels-last plan says; H, W >= 2 on top of its limits
+static inline bool down_shape_ok(int B, int H, int W, int C) { return train_shape_ok(B, H, W, C) && H >= 2 && W >= 2; }
+// `cl<f16,V=8,NV=3> G=4 a=f16`: lncf's class (the element type of x) and the element type of the patch matrix
+static inline void down_plan_class(const LncfPlan& q, const char* en_x, const char* en_a, char* buf, size_t n) {
+    char cls[48];
+    lncf_plan_class(q, en_x, cls, sizeof(cls));
+    std::snprintf(buf, n, "%s a=%s", cls, en_a);
+}
+static inline size_t down_plan_workspace_bytes(int B, int H, int W, int C) { return down_shape_ok(B, H, W, C) ? lncf_plan_workspace_bytes(B, H, W, C) : 0; }
+// stem patches (kernel 4, stride 4) of an NCHW-contiguous map: a unit = the four elements (kw = 0 .. 3) of one (patch, channel, kh) in the
+// gather, of one (n, c, h, group of four columns) in the scatter, whose last group per row is the margin that W % 4 leaves
+struct Patch4Plan {
+    int Ho, Wo, wg;                             // output map; groups of four columns per row of x (scatter)
+    long long M, units;
+    int grid, block;
+};
+static inline bool patch4_shape_ok(int B, int Cin, int H, int W) {
+    return B >= 1 && Cin >= 1 && Cin <= P4_MAX_CIN && H >= 4 && W >= 4 && (long long)B * H * W < (1ll << 31);
+}
+static inline Patch4Plan patch4_plan(int B, int Cin, int H, int W, bool scatter) {
+    Patch4Plan q{};
+    q.Ho = H / 4, q.Wo = W / 4, q.wg = (int)plan_cdiv(W, 4);
+    q.M = (long long)B * q.Ho * q.Wo;
+    q.units = scatter ? (long long)B * Cin * H * q.wg : q.M * Cin * 4;      // < 2^33
+    q.block = 256;
+    const long long nb = plan_cdiv(q.units, q.block);
+    q.grid = (int)(nb < P4_BLOCKS ? nb : P4_BLOCKS);
+    return q;
+}
+// `<x=f32,a=f16>`
+static inline void patch4_plan_class(const char* en_x, const char* en_a, char* buf, size_t n) { std::snprintf(buf, n, "<x=%s,a=%s>", en_x, en_a); }
 
 // ---------------------------------------------------------------------------------------------------------------- block_tail
 struct BtPlan {

@@ -35,7 +35,17 @@ applies all four.
 
 fuse_groupnorm_act(model) routes the GroupNorm + SiLU / ReLU lines behind the backbone (BaseConv of the YOLOX-PAFPN and of the head after
 convert_bn_model_to_gn, network_blocks.py:29-51; the CondInst mask branch; unicorn.py:38) through unicorn_amd.ops.group_norm_act by the same
-technique: the norm runs the operator with the activation, the activation module hands its input on.  fuse_model applies all five."""
+technique: the norm runs the operator with the activation, the activation module hands its input on.  fuse_model applies all five.
+
+fuse_downsample(model) routes the four downsample layers (convnext.py:77-87)
+
+    nn.Sequential(nn.Conv2d(in_chans, dims[0], kernel_size=4, stride=4), LayerNorm(dims[0], data_format="channels_first"))
+    nn.Sequential(LayerNorm(dims[i], data_format="channels_first"), nn.Conv2d(dims[i], dims[i+1], kernel_size=2, stride=2))
+
+through unicorn_amd.ops.stem_conv and ops.downsample_ln: a convolution whose kernel equals its stride is a GEMM over patches, the GEMM stays
+with the vendor library, the LayerNorm is written straight into the patch matrix and rebuilt in the backward, and the result is channels-last
+memory, which the next block's dwconv7_ln reads in place.  The paired norm hands its input on unchanged and belongs to the pair:
+fuse_layernorm_cf skips it.  fuse_model_down applies all six."""
 import torch
 
 from . import ops
@@ -231,7 +241,7 @@ def fuse_layernorm_cf(model):
     modules fused (modules that are fused already are counted)."""
     n = 0
     for m in model.modules():
-        if not _lncf_fusable(m):
+        if not _lncf_fusable(m) or isinstance(m.__dict__.get("forward"), _FusedDown):       # fuse_downsample owns the norm of a fused pair
             continue
         if not isinstance(m.__dict__.get("forward"), _FusedLayerNormCF):
             m.forward = _FusedLayerNormCF(m)
@@ -246,6 +256,96 @@ def unfuse_layernorm_cf(model):
         if isinstance(m.__dict__.get("forward"), _FusedLayerNormCF):
             del m.__dict__["forward"]
             n += 1
+    return n
+
+
+class _FusedDown:
+    """instance-level `forward` of the channels-first LayerNorm (`role` 0: hands its input on unchanged) and of the 2x2 / stride-2 Conv2d behind it
+    (`role` 1: runs ops.downsample_ln with both modules' parameters) in a downsample layer"""
+    __slots__ = ("norm", "conv", "role")
+
+    def __init__(self, norm, conv, role):
+        self.norm, self.conv, self.role = norm, conv, role
+
+    def __call__(self, x):
+        n, c = self.norm, self.conv
+        if not (n.training and c.training and isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_cuda):
+            m = c if self.role else n
+            return type(m).forward(m, x)
+        if self.role == 0:
+            return x
+        return ops.downsample_ln(x, n.weight, n.bias, c.weight, c.bias, n.eps)
+
+
+class _FusedStem:
+    """instance-level `forward` of the stem's 4x4 / stride-4 Conv2d: ops.stem_conv; the norm behind it is fuse_layernorm_cf's"""
+    __slots__ = ("conv", "norm")
+
+    def __init__(self, conv, norm):
+        self.conv, self.norm = conv, norm
+
+    def __call__(self, x):
+        c = self.conv
+        if not (c.training and self.norm.training and isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_cuda):
+            return type(c).forward(c, x)
+        return ops.stem_conv(x, c.weight, c.bias)
+
+
+def _patch_conv_ok(conv, k):
+    return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (k, k) and conv.stride == (k, k) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None and conv.out_channels % 4 == 0
+            and 4 <= conv.out_channels <= ops.PW_MLP_MAX_H)
+
+
+def _down_kind(seq):
+    """1: (channels-first LayerNorm, Conv2d 2/2), 2: (Conv2d 4/4 of at most 4 channels, channels-first LayerNorm), 0: neither, or a module
+    carries an instance-level forward of somebody else's"""
+    if not isinstance(seq, torch.nn.Sequential) or len(seq) != 2:
+        return 0
+    a, b = seq[0], seq[1]
+    if _lncf_fusable(a) and _patch_conv_ok(b, 2) and b.in_channels == a.weight.shape[0]:
+        ok = (isinstance(a.__dict__.get("forward"), (_FusedDown, _FusedLayerNormCF, type(None)))
+              and isinstance(b.__dict__.get("forward"), (_FusedDown, type(None))))
+        return 1 if ok else 0
+    if _patch_conv_ok(a, 4) and a.in_channels <= ops.STEM_MAX_CIN and _lncf_fusable(b) and b.weight.shape[0] == a.out_channels:
+        return 2 if isinstance(a.__dict__.get("forward"), (_FusedStem, type(None))) else 0
+    return 0
+
+
+def fuse_downsample(model):
+    """Route the downsample layers of a ConvNeXt backbone (convnext.py:77-87) through unicorn_amd.ops.downsample_ln and ops.stem_conv, by the
+    technique of fuse_pw_mlp.  Two patterns, each an nn.Sequential of exactly two modules:
+      - a channels-first LayerNorm that fuse_layernorm_cf would accept, then Conv2d(C, Co, 2, stride=2) with padding 0, dilation 1, groups 1, a
+        bias, in_channels == C and Co % 4 == 0: the norm gets an instance-level `forward` that hands x on UNCHANGED, the convolution one that
+        runs ops.downsample_ln with both modules' parameters.  A `forward` that fuse_layernorm_cf set on that norm is replaced: the pair owns
+        its norm, and fuse_layernorm_cf skips (and does not count) a norm that carries the pair's forward;
+      - Conv2d(Cin, Co, 4, stride=4) with padding 0, groups 1, a bias, Cin <= 4 and Co % 4 == 0, then a channels-first LayerNorm over Co: the
+        convolution runs ops.stem_conv, whose channels-last result fuse_layernorm_cf's norm reads in place; the norm is left to it.
+    Both are active only when both modules are in training mode and x is a 4-D device tensor; otherwise each module runs its own forward.  So
+    a forward hook on the norm of a fused pair sees the un-normalised tensor as its output.  No site is skipped by shape.  Module tree,
+    parameter names and state_dict() stay as they were; copy.deepcopy(model) gives a copy that uses the copy's parameters.  Returns the
+    number of Sequentials fused (those fused already are counted)."""
+    n = 0
+    for seq in model.modules():
+        kind = _down_kind(seq)
+        if kind == 1:
+            seq[0].forward = _FusedDown(seq[0], seq[1], 0)
+            seq[1].forward = _FusedDown(seq[0], seq[1], 1)
+        elif kind == 2:
+            seq[0].forward = _FusedStem(seq[0], seq[1])
+        n += kind != 0
+    return n
+
+
+def unfuse_downsample(model):
+    """Remove what fuse_downsample set (and nothing else: a norm it took over from fuse_layernorm_cf runs its own forward until that is
+    called again); returns the number of Sequentials restored."""
+    n = 0
+    for m in model.modules():
+        f = m.__dict__.get("forward")
+        if isinstance(f, (_FusedDown, _FusedStem)):
+            del m.__dict__["forward"]
+            n += isinstance(f, _FusedStem) or f.role == 1
     return n
 
 
@@ -415,3 +515,10 @@ def unfuse_groupnorm_act(model):
 def fuse_model(model, keep="hidden"):
     """fuse_backbone_mlp + fuse_groupnorm_act -> the four counts of fuse_backbone_mlp and the number of GroupNorms fused"""
     return fuse_backbone_mlp(model, keep) + (fuse_groupnorm_act(model),)
+
+
+def fuse_model_down(model, keep="hidden"):
+    """fuse_model + fuse_downsample -> the five counts of fuse_model and the number of downsample layers fused (of which fuse_model's count of
+    channels-first norms still holds the paired ones: they were fused when it counted them): between the image and the stage outputs no eager
+    line, no vendor convolution and no layout conversion is left"""
+    return fuse_model(model, keep) + (fuse_downsample(model),)

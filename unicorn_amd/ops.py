@@ -1440,6 +1440,258 @@ def pw_mlp(t, w1, b1, w2, b2, keep="hidden"):
     return PwMlpFunction.apply(t, w1, b1, w2, b2, keep)
 
 
+def _patch_compute_dtype(x):
+    """the compute dtype of the two downsample operators, PwMlpFunction's rule"""
+    if torch.is_autocast_enabled("cuda"):
+        return torch.get_autocast_dtype("cuda")
+    return torch.float64 if x.dtype == torch.float64 else torch.float32
+
+
+def _col_sum(dev, cd, gy):
+    """the column sums of gy (M, Co) in the sum dtype of `cd`: the grad_y / grad_b2 path of uni_pw_mlp_act_bwd alone, which its header allows"""
+    M, Co = gy.shape
+    out = torch.empty(Co, device=dev, dtype=_pw_sum_dtype(cd))
+    _pw_act_bwd(dev, cd, M, Co, Co, None, None, None, None, None, gy, out)
+    return out
+
+
+WGRAD_ROWS = 1024
+
+
+def _wgrad_mm(gy, A):
+    """gy.t() @ A for gy (M, Co), A (M, K): the weight gradient of a patch convolution, a sum over the M output pixels.  One mm adds
+    the M terms of an element in fp32 in the order the vendor kernel takes them, and at training maps (M of 10^4 .. 10^5) its error is
+    several times that of the eager convolution's weight gradient.  So fp32 maps of at least 2 WGRAD_ROWS rows are multiplied in slices of
+    WGRAD_ROWS rows by ONE bmm, and the slices (and the mm of the rows left over) are added in ascending order in fp64: a fixed order, the
+    error of a 1024-term sum.  Half maps keep the single mm (fp32 accumulation, one rounding), fp64 maps too."""
+    M = gy.shape[0]
+    S = M // WGRAD_ROWS
+    if gy.dtype != torch.float32 or S < 2:
+        return torch.mm(gy.t(), A)
+    head = S * WGRAD_ROWS
+    part = torch.bmm(gy[:head].view(S, WGRAD_ROWS, -1).transpose(1, 2), A[:head].view(S, WGRAD_ROWS, -1))
+    out = part.sum(0, dtype=torch.float64)
+    if head < M:
+        out += torch.mm(gy[head:].t(), A[head:])
+    return out.to(torch.float32)
+
+
+class DownsampleLNFunction(torch.autograd.Function):
+    """A downsample layer of the ConvNeXt backbone (convnext.py:83-87: channels-first LayerNorm, then Conv2d(C, Co, 2, stride=2)):
+    apply(x (N,C,H,W), ln_weight (C,), ln_bias (C,), weight (Co,C,2,2), bias (Co,), eps) -> y (N,Co,H//2,W//2) in channels-last memory, in the
+    compute dtype; ops.downsample_ln checks the arguments.  The compute dtype is fp64 for fp64 tensors, else fp32, and under
+    torch.autocast("cuda") the autocast dtype; autocast is switched off for the Function's own lines, so forward and backward use the same
+    dtypes.  The HIP forward (uni_down_train_fwd) reads x in the dtype it has and writes the LayerNorm output straight into the patch matrix
+    A (M, 4C) of the convolution, which is then the addmm F.linear would make.  Saves x, the two LayerNorm vectors, weight and the (N H W, 2)
+    statistics: neither A nor the LayerNorm output.  The backward rebuilds A only when weight.grad is asked for (gy.t() @ A, in row slices:
+    _wgrad_mm) and computes only what autograd asks for.  No host synchronisation, one writer per element: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, ln_weight, ln_bias, weight, bias, eps):
+        N, Cc, H, W = x.shape
+        Co, Ho, Wo = weight.shape[0], H // 2, W // 2
+        cd = _patch_compute_dtype(x)
+        sd = _pw_sum_dtype(cd)
+        ctx.dims, ctx.cd, ctx.eps, ctx.x_dtype = (N, Cc, H, W, Co), cd, eps, x.dtype
+        if N == 0:
+            ctx.save_for_backward(x, ln_weight, ln_bias, weight)
+            ctx.b_dtype = bias.dtype
+            return torch.empty((N, Co, Ho, Wo), device=x.device, dtype=cd, memory_format=torch.channels_last)
+        M = N * Ho * Wo
+        with torch.autocast("cuda", enabled=False), torch.cuda.device(x.device):
+            xc = x.detach().contiguous(memory_format=torch.channels_last)
+            A = torch.empty((M, 4 * Cc), device=x.device, dtype=cd)
+            stats = torch.empty((N * H * W, 2), device=x.device, dtype=sd)
+            fn, name = _entry("uni_down_train_fwd", sd)
+            L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], L.ptr(ln_weight.detach().to(sd).contiguous()), L.ptr(ln_bias.detach().to(sd).contiguous()),
+                       eps, N, H, W, Cc, 0, L.ptr(A), _STORE_DTYPE[cd], L.ptr(stats), L.stream_ptr()), name)
+            W2 = weight.detach().permute(0, 2, 3, 1).reshape(Co, 4 * Cc).to(cd)
+            y = torch.addmm(bias.detach().to(cd), A, W2.t())
+        ctx.save_for_backward(xc, ln_weight, ln_bias, weight, stats)
+        ctx.b_dtype = bias.dtype
+        return y.view(N, Ho, Wo, Co).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        need = ctx.needs_input_grad
+        N, Cc, H, W, Co = ctx.dims
+        cd = ctx.cd
+        sd = _pw_sum_dtype(cd)
+        if N == 0:
+            x, ln_weight, ln_bias, weight = ctx.saved_tensors
+            z = torch.zeros_like
+            return (z(x) if need[0] else None, z(ln_weight) if need[1] else None, z(ln_bias) if need[2] else None, z(weight) if need[3] else None,
+                    torch.zeros(Co, device=x.device, dtype=ctx.b_dtype) if need[4] else None, None)
+        xc, ln_weight, ln_bias, weight, stats = ctx.saved_tensors
+        dev, Ho, Wo = xc.device, H // 2, W // 2
+        M = N * Ho * Wo
+        need_ln = need[1] or need[2]
+        g_x = g_lw = g_lb = g_w = g_b = None
+        with torch.autocast("cuda", enabled=False), torch.cuda.device(dev):
+            gy = grad_y.permute(0, 2, 3, 1).reshape(M, Co).to(cd).contiguous()
+            lw = ln_weight.detach().to(sd).contiguous()
+            if need[4]:
+                g_b = _col_sum(dev, cd, gy).to(ctx.b_dtype)
+            if need[3]:                                                      # A again, with the forward's bits
+                A = torch.empty((M, 4 * Cc), device=dev, dtype=cd)
+                fn, name = _entry("uni_down_train_fwd", sd)
+                L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], L.ptr(lw), L.ptr(ln_bias.detach().to(sd).contiguous()), ctx.eps, N, H, W, Cc, 1,
+                           L.ptr(A), _STORE_DTYPE[cd], L.ptr(stats), L.stream_ptr()), name)
+                g_w = _wgrad_mm(gy, A).view(Co, 2, 2, Cc).permute(0, 3, 1, 2).to(weight.dtype).contiguous()
+                del A
+            if need[0] or need_ln:
+                W2 = weight.detach().permute(0, 2, 3, 1).reshape(Co, 4 * Cc).to(cd)
+                gA = torch.mm(gy, W2)
+                g_x = torch.empty_like(xc) if need[0] else None              # channels-last like xc; the call writes it completely
+                g_lw = torch.empty(Cc, device=dev, dtype=sd) if need_ln else None
+                g_lb = torch.empty(Cc, device=dev, dtype=sd) if need_ln else None
+                ws = _train_ws("downsample_ln", "uni_down_train_workspace_bytes", dev, sd, N, H, W, Cc) if need_ln else None
+                fn, name = _entry("uni_down_train_bwd", sd)
+                L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], L.ptr(lw), L.ptr(stats), L.ptr(gA), _STORE_DTYPE[cd], N, H, W, Cc, L.ptr(g_x),
+                           L.ptr(g_lw), L.ptr(g_lb), L.ptr(ws), ws.numel() if need_ln else 0, L.stream_ptr()), name)
+        return (g_x, g_lw.to(ln_weight.dtype) if need[1] else None, g_lb.to(ln_bias.dtype) if need[2] else None, g_w, g_b, None)
+
+
+def _check_patch_conv(op, x, weight, bias, k):
+    """the checks the two downsample operators share on the map and the convolution's parameters -> N, C, H, W, Co"""
+    N, Cc, H, W = _check_map_dims(op, "x", x)
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (Cc, k, k):
+        raise L.UnicornHipError("%s: weight of shape %s is not (Co, %d, %d, %d): a %dx%d / stride-%d convolution of x's %d channels"
+                                % (op, tuple(weight.shape), Cc, k, k, k, k, k, Cc))
+    Co = weight.shape[0]
+    _check_channel_vecs(op, ("bias",), (bias,), Co)
+    if Co % 4 or not 4 <= Co <= PW_MLP_MAX_H:
+        raise L.UnicornHipError("%s: Co = %d is outside Co %% 4 == 0, 4 <= Co <= %d" % (op, Co, PW_MLP_MAX_H))
+    if H < k or W < k:
+        raise L.UnicornHipError("%s: map of H=%d W=%d is smaller than the %dx%d kernel" % (op, H, W, k, k))
+    if N * H * W >= 1 << 31:
+        raise L.UnicornHipError("%s: shape N=%d H=%d W=%d is outside N H W < 2^31" % (op, N, H, W))
+    return N, Cc, H, W, Co
+
+
+def _check_patch_dtypes(op, x, params, autocast):
+    ts = (x,) + tuple(params)
+    if x.dtype == torch.float64:
+        ok = not autocast and all(t.dtype == torch.float64 for t in params)
+    elif autocast:
+        ok = x.dtype in _STORE_DTYPE and all(t.is_floating_point() and t.dtype != torch.float64 for t in params)
+    else:
+        ok = x.dtype in _STORE_DTYPE and all(t.dtype == torch.float32 for t in params)
+    if not ok:
+        raise L.UnicornHipError("%s: dtypes %s unsupported (x fp32 / fp16 / bf16 with fp32 parameters, or all fp64; half parameters only under "
+                                "torch.autocast)" % (op, ", ".join(str(t.dtype) for t in ts)))
+
+
+def downsample_ln(x, ln_weight, ln_bias, weight, bias, eps=1e-6):
+    """A downsample layer of the ConvNeXt backbone (convnext.py:83-87) as one operator, equal in value and in all five gradients to
+    Conv2d(C, Co, 2, stride=2)(LayerNorm(C, data_format="channels_first")(x)):
+      x                  (N, C, H, W) fp32, fp16 or bf16, read in the dtype it has.  Channels-last memory (what ops.block_tail returns) is read
+                         in place; any other layout (NCHW-contiguous included) is converted ONCE with
+                         .contiguous(memory_format=torch.channels_last), and x.grad comes back channels-last
+      ln_weight, ln_bias (C,): the LayerNorm;  weight (Co, C, 2, 2), bias (Co,): the convolution.  fp32
+    All five fp64 is accepted for checks.  The compute dtype is fp64 for fp64 tensors, else fp32, and under torch.autocast("cuda") the
+    autocast dtype (the parameters are cast to it as F.conv2d casts them; the LayerNorm itself is computed in fp32 and rounded once).  Returns
+    y (N, Co, H // 2, W // 2) in the compute dtype with y.is_contiguous(memory_format=torch.channels_last): what the next block's
+    ops.dwconv7_ln reads in place.  A last row or column that an odd H or W leaves over is dropped, as the convolution drops it: its x.grad is
+    exact zeros.  The GEMMs are the vendor library's (addmm / mm); the LayerNorm, the patch layout and the LayerNorm backward are HIP
+    (uni_down_train_fwd / _bwd), the bias gradient is the column sum of uni_pw_mlp_act_bwd.  Autograd keeps x, ln_weight, ln_bias, weight and
+    two numbers per pixel: neither the LayerNorm output nor the patch matrix, which the backward rebuilds only for weight.grad.
+    C % 4 == 0, 4 <= C <= 2048, Co % 4 == 0, 4 <= Co <= 8192, H, W >= 2.  N == 0 returns an empty tensor without a library call."""
+    op = "downsample_ln"
+    names = ("x", "ln_weight", "ln_bias", "weight", "bias")
+    ts = (x, ln_weight, ln_bias, weight, bias)
+    _check_tensors(op, names, ts)
+    autocast = x.is_cuda and torch.is_autocast_enabled("cuda")
+    N, Cc, H, W, Co = _check_patch_conv(op, x, weight, bias, 2)
+    _check_channel_vecs(op, names[1:3], ts[1:3], Cc)
+    _check_train_shape(op, N, Cc, H, W)
+    _check_eps(op, eps)
+    _check_patch_dtypes(op, x, ts[1:], autocast)
+    _check_one_device(op, ts)
+    return DownsampleLNFunction.apply(x, ln_weight, ln_bias, weight, bias, float(eps))
+
+
+class StemConvFunction(torch.autograd.Function):
+    """The stem convolution of the ConvNeXt backbone (convnext.py:77-80: Conv2d(in_chans, C0, 4, stride=4)): apply(x (N,Cin,H,W), weight
+    (Co,Cin,4,4), bias (Co,)) -> y (N,Co,H//4,W//4) in channels-last memory, in the compute dtype of DownsampleLNFunction; ops.stem_conv checks
+    the arguments.  uni_patch4_gather writes the patch matrix A (M, 16 Cin), the GEMM is the addmm F.linear would make.  Saves x and weight; A
+    is gathered again for weight.grad, and x.grad (an image normally has none) is a mm and uni_patch4_scatter."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        N, Cin, H, W = x.shape
+        Co, Ho, Wo = weight.shape[0], H // 4, W // 4
+        cd = _patch_compute_dtype(x)
+        ctx.dims, ctx.cd, ctx.b_dtype = (N, Cin, H, W, Co), cd, bias.dtype
+        if N == 0:
+            ctx.save_for_backward(x, weight)
+            return torch.empty((N, Co, Ho, Wo), device=x.device, dtype=cd, memory_format=torch.channels_last)
+        M = N * Ho * Wo
+        with torch.autocast("cuda", enabled=False), torch.cuda.device(x.device):
+            xc = x.detach().contiguous()
+            A = torch.empty((M, 16 * Cin), device=x.device, dtype=cd)
+            fn, name = _entry("uni_patch4_gather", _pw_sum_dtype(cd))
+            L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], N, Cin, H, W, L.ptr(A), _STORE_DTYPE[cd], L.stream_ptr()), name)
+            y = torch.addmm(bias.detach().to(cd), A, weight.detach().reshape(Co, 16 * Cin).to(cd).t())
+        ctx.save_for_backward(xc, weight)
+        return y.view(N, Ho, Wo, Co).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        need = ctx.needs_input_grad
+        N, Cin, H, W, Co = ctx.dims
+        cd = ctx.cd
+        xc, weight = ctx.saved_tensors
+        if N == 0:
+            return (torch.zeros_like(xc) if need[0] else None, torch.zeros_like(weight) if need[1] else None,
+                    torch.zeros(Co, device=xc.device, dtype=ctx.b_dtype) if need[2] else None)
+        dev, Ho, Wo = xc.device, H // 4, W // 4
+        M = N * Ho * Wo
+        g_x = g_w = g_b = None
+        with torch.autocast("cuda", enabled=False), torch.cuda.device(dev):
+            gy = grad_y.permute(0, 2, 3, 1).reshape(M, Co).to(cd).contiguous()
+            if need[2]:
+                g_b = _col_sum(dev, cd, gy).to(ctx.b_dtype)
+            if need[1]:
+                A = torch.empty((M, 16 * Cin), device=dev, dtype=cd)
+                fn, name = _entry("uni_patch4_gather", _pw_sum_dtype(cd))
+                L.check(fn(L.ptr(xc), _STORE_DTYPE[xc.dtype], N, Cin, H, W, L.ptr(A), _STORE_DTYPE[cd], L.stream_ptr()), name)
+                g_w = _wgrad_mm(gy, A).view(Co, Cin, 4, 4).to(weight.dtype)
+                del A
+            if need[0]:
+                gA = torch.mm(gy, weight.detach().reshape(Co, 16 * Cin).to(cd))
+                g_x = torch.empty_like(xc)                                   # NCHW-contiguous like xc; the call writes it completely
+                fn, name = _entry("uni_patch4_scatter", _pw_sum_dtype(cd))
+                L.check(fn(L.ptr(gA), _STORE_DTYPE[cd], N, Cin, H, W, L.ptr(g_x), _STORE_DTYPE[xc.dtype], L.stream_ptr()), name)
+        return g_x, g_w, g_b
+
+
+STEM_MAX_CIN = 4
+
+
+def stem_conv(x, weight, bias):
+    """The stem convolution of the ConvNeXt backbone (convnext.py:77-80) as one operator, equal in value and in all three gradients to
+    Conv2d(Cin, Co, 4, stride=4)(x): x (N, Cin, H, W) fp32, fp16 or bf16 (any strides but NCHW-contiguous are converted once with
+    .contiguous()), weight (Co, Cin, 4, 4) and bias (Co,) fp32; or all fp64 for checks.  Compute dtype, autocast and the layout of the result are
+    those of ops.downsample_ln: y (N, Co, H // 4, W // 4) in channels-last memory, which ops.layernorm_cf reads in place.  The margin that
+    H % 4 or W % 4 leaves over is dropped, as the convolution drops it: its x.grad is zero.  The GEMMs are the vendor library's; the patch
+    gather and scatter are HIP (uni_patch4_gather / _scatter), the bias gradient is the column sum of uni_pw_mlp_act_bwd.  Autograd keeps x
+    and weight; x.grad is computed only when x requires a gradient.  1 <= Cin <= 4, Co % 4 == 0, 4 <= Co <= 8192, H, W >= 4.  N == 0 returns
+    an empty tensor without a library call."""
+    op = "stem_conv"
+    ts = (x, weight, bias)
+    _check_tensors(op, ("x", "weight", "bias"), ts)
+    autocast = x.is_cuda and torch.is_autocast_enabled("cuda")
+    N, Cin, H, W, Co = _check_patch_conv(op, x, weight, bias, 4)
+    if not 1 <= Cin <= STEM_MAX_CIN:
+        raise L.UnicornHipError("%s: Cin = %d is outside 1 <= Cin <= %d" % (op, Cin, STEM_MAX_CIN))
+    _check_patch_dtypes(op, x, ts[1:], autocast)
+    _check_one_device(op, ts)
+    return StemConvFunction.apply(x, weight, bias)
+
+
 def _prop_ws(dev, B, Kc, Q):
     need = L.lib().uni_prop_workspace_bytes(B, Kc, Q)
     if need == 0:
