@@ -335,6 +335,46 @@ int uni_head_loss_bwd_f64(const double* outputs, int ld_out, const double* origi
                           const int32_t* num_gt, const double* x_shifts, const double* y_shifts, const double* strides, const double* grad_out,
                           int B, int A, int C, double reg_weight, double* grad_outputs, int ld_grad, double* grad_origin, void* workspace,
                           size_t workspace_bytes, uni_stream_t stream);
+/* Head-output assembly for a whole BATCH: the lines that turn the head's prediction convolutions into what the loss operators above read
+ * (unicorn/models/unicorn_head_mask.py:339-366 of forward, get_output_and_grid :476-500 and the level cats :396-401 / :554-558; identically
+ * unicorn_head.py, yolo_head_det.py, yolo_head_det_mask.py; n_anchors == 1), forward and backward in ONE launch each whatever B, L, C, P and
+ * the layouts, without a host synchronisation, a workspace, a table upload or an atomic: one writer per element, two calls give the same bits.
+ *   reg, obj, cls, ctrl   HOST arrays of L DEVICE pointers: the maps (B,4,h_l,w_l), (B,1,h_l,w_l), (B,C,h_l,w_l), (B,P,h_l,w_l) of level l,
+ *                         all of the element type map_dtype names (0 = the type of the entry: fp32, fp64 in the _f64 form; 1 = fp16,
+ *                         2 = bf16, fp32 form only).  ctrl NULL (then P == 0): no controller maps.
+ *   hs, ws, strides       HOST arrays of L: the level sizes and the positive stride of the level
+ *   layouts               HOST array of L: bit 0 / 1 / 2 / 3 set = the reg / obj / cls / ctrl map of the level is NCHW-contiguous, clear =
+ *                         channels-last memory [B][h][w][channels]
+ * Anchor a = off_l + y w_l + x with off_l = sum_{k<l} h_k w_k, A = sum h_l w_l.  uni_head_assemble_fwd writes (a NULL result is skipped)
+ *   outputs [B][A] rows of pitch ld_out >= 5 + C: (reg0 + x) * s, (reg1 + y) * s, exp(reg2) * s, exp(reg3) * s, obj, cls[0 .. C-1]; the two
+ *                         leading columns as an add and then a multiply, never an fma; exp is the full-precision function
+ *   origin_preds [B][A][4] the raw reg channels;   x_shifts, y_shifts, expanded_strides [A]: x, y, s;
+ *   dynamic_params [B][A] rows of pitch ld_par >= P: ctrl[b][p][y][x];   fpn_levels [B][A] int32: l.   The pitch padding is never touched.
+ * Half maps are read as stored and decoded in fp32: the result has the bits of the fp32 call on the widened maps.
+ * uni_head_assemble_bwd reads grad_outputs (pitch ld_gout), grad_origin [B][A][4], grad_params (pitch ld_gpar) -- each may be NULL = zero --
+ * and writes, for every non-NULL entry of the HOST arrays grad_reg / grad_obj / grad_cls / grad_ctrl (an array may be NULL as a whole), the
+ * gradient of that map COMPLETELY in the element type and layout of the map, rounded once:
+ *   g_reg[0:2] = s g_out[0:2] + g_org[0:2];  g_reg[2:4] = s g_out[2:4] exp(reg[2:4]) + g_org[2:4];  g_obj = g_out[4];  g_cls = g_out[5:];
+ *   g_ctrl[b][p][y][x] = g_par[b][a][p].   reg is read only where grad_reg asks (it may be NULL otherwise).
+ * Limits: 1 <= L <= 4, 1 <= B <= 65535, 1 <= C <= 256, 1 <= P <= 1024 (0 without ctrl), h_l, w_l >= 1, A < 2^24, strides positive and finite;
+ * other shapes are refused with an error string before anything is launched.  A block assembles a tile of 64 anchors of one level through LDS.
+ * The _f64 forms are the same templated code in double precision for gradcheck and fixtures (maps and results fp64, map_dtype 0). */
+int uni_head_assemble_fwd(const void* const* reg, const void* const* obj, const void* const* cls, const void* const* ctrl, const int32_t* hs,
+                          const int32_t* ws, const double* strides, const int32_t* layouts, int L, int B, int C, int P, int map_dtype,
+                          float* outputs, int ld_out, float* origin_preds, float* x_shifts, float* y_shifts, float* expanded_strides,
+                          float* dynamic_params, int ld_par, int32_t* fpn_levels, uni_stream_t stream);
+int uni_head_assemble_bwd(const void* const* reg, const int32_t* hs, const int32_t* ws, const double* strides, const int32_t* layouts, int L, int B,
+                          int C, int P, int map_dtype, const float* grad_outputs, int ld_gout, const float* grad_origin,
+                          const float* grad_params, int ld_gpar, void* const* grad_reg, void* const* grad_obj, void* const* grad_cls,
+                          void* const* grad_ctrl, uni_stream_t stream);
+int uni_head_assemble_fwd_f64(const void* const* reg, const void* const* obj, const void* const* cls, const void* const* ctrl, const int32_t* hs,
+                              const int32_t* ws, const double* strides, const int32_t* layouts, int L, int B, int C, int P, int map_dtype,
+                              double* outputs, int ld_out, double* origin_preds, double* x_shifts, double* y_shifts, double* expanded_strides,
+                              double* dynamic_params, int ld_par, int32_t* fpn_levels, uni_stream_t stream);
+int uni_head_assemble_bwd_f64(const void* const* reg, const int32_t* hs, const int32_t* ws, const double* strides, const int32_t* layouts, int L,
+                              int B, int C, int P, int map_dtype, const double* grad_outputs, int ld_gout, const double* grad_origin,
+                              const double* grad_params, int ld_gpar, void* const* grad_reg, void* const* grad_obj, void* const* grad_cls,
+                              void* const* grad_ctrl, uni_stream_t stream);
 /* The CondInst mask loss of the head for a whole BATCH (unicorn/models/unicorn_head_mask.py:568-569, :675-694, :731-732 with
  * dynamic_mask_head.py:247-278), forward and backward, fed by the device-side results of uni_simota_assign: 5 launches forward and at most 22
  * backward whatever the data, B, A, M and capacity, without a host synchronisation, a read-back or an allocation.

@@ -7,6 +7,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libunicorn_hip.so")
 
 c_f = C.c_void_p   # device pointers travel as void*
 c_i = C.c_int
+c_pp = C.POINTER(C.c_void_p)   # a host array of device pointers
 
 
 class ModelCfg(C.Structure):
@@ -77,6 +78,10 @@ PROTOS = {
                                 C.c_size_t, C.c_void_p]),
     "uni_head_loss_bwd": (c_i, [c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, C.c_double, c_f, c_i, c_f,
                                 C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uni_head_assemble_fwd": (c_i, [c_pp, c_pp, c_pp, c_pp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                    c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_f, C.c_void_p]),
+    "uni_head_assemble_bwd": (c_i, [c_pp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), c_i, c_i, c_i, c_i,
+                                    c_i, c_f, c_i, c_f, c_f, c_i, c_pp, c_pp, c_pp, c_pp, C.c_void_p]),
     "uni_head_mask_loss_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "uni_head_mask_loss_fwd": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
@@ -159,7 +164,7 @@ PROTOS = {
 # fp32 / fp64 operator pairs whose two entries take the same arguments (device pointers travel as void*): the `_f64` prototype is the fp32 one.
 # The two correlation twins above are not: the fp64 form has no precision and no workspace.
 F64_TWINS = ("uni_msda_fwd", "uni_msda_bwd", "uni_condinst_loss_fwd", "uni_condinst_loss_bwd", "uni_head_loss_fwd", "uni_head_loss_bwd",
-             "uni_head_mask_loss_fwd", "uni_head_mask_loss_bwd", "uni_mot_corr_loss_fwd", "uni_mot_corr_loss_bwd", "uni_prop_labels",
+             "uni_head_assemble_fwd", "uni_head_assemble_bwd", "uni_head_mask_loss_fwd", "uni_head_mask_loss_bwd", "uni_mot_corr_loss_fwd", "uni_mot_corr_loss_bwd", "uni_prop_labels",
              "uni_prop_dice_pyramid_fwd", "uni_prop_dice_pyramid_bwd", "uni_dwln_train_fwd", "uni_dwln_train_bwd",
              "uni_block_tail_fwd", "uni_block_tail_bwd", "uni_lncf_train_fwd", "uni_lncf_train_bwd",
              "uni_down_train_fwd", "uni_down_train_bwd", "uni_patch4_gather", "uni_patch4_scatter", "uni_pw_mlp_act_fwd", "uni_pw_mlp_act_bwd", "uni_gn_act_train_fwd", "uni_gn_act_train_bwd")

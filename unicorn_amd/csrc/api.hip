@@ -500,6 +500,26 @@ size_t uni_head_loss_workspace_bytes(int B, int A, int C) { return head_loss_wor
         API(launch_head_loss_bwd<T>(a, grad_out, grad_outputs, ld_grad, grad_origin, S(stream)));                                                  \
     }
 UNI_PAIR(DEF_HEAD_LOSS)
+#define DEF_HEAD_ASSEMBLE(SFX, T)                                                                                                                  \
+    int uni_head_assemble_fwd##SFX(const void* const* reg, const void* const* obj, const void* const* cls, const void* const* ctrl,               \
+                                   const int32_t* hs, const int32_t* ws, const double* strides, const int32_t* layouts, int L, int B, int C,      \
+                                   int P, int map_dtype, T* outputs, int ld_out, T* origin_preds, T* x_shifts, T* y_shifts, T* expanded_strides,  \
+                                   T* dynamic_params, int ld_par, int32_t* fpn_levels, uni_stream_t stream) {                                     \
+        UNI_REQUIRE(reg && obj && cls && hs && ws && strides && layouts, "head_assemble_fwd" #SFX ": NULL argument");                             \
+        const HaShape sh{hs, ws, strides, layouts, L, B, C, P, map_dtype};                                                                         \
+        const HaOut<T> o{outputs, ld_out, origin_preds, x_shifts, y_shifts, expanded_strides, dynamic_params, ld_par, fpn_levels};                 \
+        API(launch_head_assemble_fwd<T>(sh, reg, obj, cls, ctrl, o, S(stream)));                                                                   \
+    }                                                                                                                                              \
+    int uni_head_assemble_bwd##SFX(const void* const* reg, const int32_t* hs, const int32_t* ws, const double* strides, const int32_t* layouts,   \
+                                   int L, int B, int C, int P, int map_dtype, const T* grad_outputs, int ld_gout, const T* grad_origin,           \
+                                   const T* grad_params, int ld_gpar, void* const* grad_reg, void* const* grad_obj, void* const* grad_cls,        \
+                                   void* const* grad_ctrl, uni_stream_t stream) {                                                                 \
+        UNI_REQUIRE(hs && ws && strides && layouts, "head_assemble_bwd" #SFX ": NULL argument");                                                  \
+        const HaShape sh{hs, ws, strides, layouts, L, B, C, P, map_dtype};                                                                         \
+        const HaGrad<T> g{grad_outputs, ld_gout, grad_origin, grad_params, ld_gpar};                                                               \
+        API(launch_head_assemble_bwd<T>(sh, reg, g, grad_reg, grad_obj, grad_cls, grad_ctrl, S(stream)));                                          \
+    }
+UNI_PAIR(DEF_HEAD_ASSEMBLE)
 size_t uni_dwln_train_workspace_bytes(int B, int H, int W, int C) { return dwln_train_workspace_bytes(B, H, W, C); }
 #define DEF_DWLN_TRAIN(SFX, T)                                                                                                                     \
     int uni_dwln_train_fwd##SFX(const T* x, const T* weight, const T* bias, const T* ln_weight, const T* ln_bias, double eps, int B, int H, int W, \

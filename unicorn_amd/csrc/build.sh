@@ -8,7 +8,7 @@ cd "$(dirname "$0")"
 OUT=../lib
 mkdir -p $OUT build
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result"
-UNITS="gemm gemm_h2 gemm_h2d gemm_h2q gemm_p44 mlp_fused norm msda corr corr_bwd misc condinst_loss simota head_loss head_mask_loss mot_corr prop_loss opt_step dwln_train block_tail lncf_train down_train pw_mlp gn_act_train post mask_post engine api"
+UNITS="gemm gemm_h2 gemm_h2d gemm_h2q gemm_p44 mlp_fused norm msda corr corr_bwd misc condinst_loss simota head_loss head_assemble head_mask_loss mot_corr prop_loss opt_step dwln_train block_tail lncf_train down_train pw_mlp gn_act_train post mask_post engine api"
 HDRS=$(ls *.h ../../include/*.h)
 pids=()
 objs=()

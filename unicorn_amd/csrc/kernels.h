@@ -306,6 +306,42 @@ template <typename T>
 int launch_head_loss_fwd(const HlArgs<T>& a, T* out, hipStream_t s);
 template <typename T>
 int launch_head_loss_bwd(const HlArgs<T>& a, const T* gout, T* g_out, int ldg, T* g_org, hipStream_t s);
+// head_assemble.hip: the lines between the head's prediction convolutions and get_losses (unicorn_head_mask.py:339-366, :476-500 and the level
+// cats :396-401, :554-558; n_anchors == 1) for a batch and up to HA_MAX_L levels, one launch forward and one backward, fp32 (maps fp32, fp16 or
+// bf16) and fp64, no host read-back, no workspace, one writer per element.  Per level l the maps reg (B,4,h,w), obj (B,1,h,w), cls (B,C,h,w)
+// and ctrl (B,P,h,w), each NCHW-contiguous (bit 0 .. 3 of layouts[l] set) or channels-last; anchor a = off_l + y w_l + x.
+//   forward   outputs [B][A][ld >= 5 + C], origin [B][A][4], xs / ys / st [A], params [B][A][ldp >= P], levels [B][A] (each may be NULL)
+//   backward  g_out [B][A][ldg], g_org [B][A][4], g_par [B][A][ldgp] (NULL = zero) -> per level g_reg / g_obj / g_cls / g_ctrl in the element type
+//             and layout of their map (an array or an entry may be NULL: not computed); reg is read for exp(reg[2:4]) when g_reg is asked for
+// 1 <= L <= 4, 1 <= B <= 65535, 1 <= C <= 256, 1 <= P <= 1024, h, w >= 1, A = sum h w < 2^24, strides > 0.
+constexpr int HA_MAX_L = 4;
+constexpr int HA_TILE = 64;                     // anchors of one level that a block assembles (and the channels of one pass through LDS)
+struct HaShape {
+    const int32_t *hs, *ws;                     // host arrays of L
+    const double* strides;
+    const int32_t* layouts;
+    int L, B, C, P, map_dtype;                  // P == 0: no controller maps; map_dtype 0 = T, 1 = fp16, 2 = bf16
+};
+template <typename T>
+struct HaOut {
+    T* outputs; int ld;
+    T* origin;
+    T *xs, *ys, *st;
+    T* params; int ldp;
+    int32_t* levels;
+};
+template <typename T>
+struct HaGrad {
+    const T* g_out; int ldg;
+    const T* g_org;
+    const T* g_par; int ldgp;
+};
+template <typename T>
+int launch_head_assemble_fwd(const HaShape& sh, const void* const* reg, const void* const* obj, const void* const* cls, const void* const* ctrl,
+                             const HaOut<T>& o, hipStream_t s);
+template <typename T>
+int launch_head_assemble_bwd(const HaShape& sh, const void* const* reg, const HaGrad<T>& g, void* const* g_reg, void* const* g_obj,
+                             void* const* g_cls, void* const* g_ctrl, hipStream_t s);
 // head_mask_loss.hip: the CondInst mask loss of get_losses (unicorn_head_mask.py:568-569, :675-694, :731-732) for a batch from the device-side
 // results of launch_simota_assign, forward + recomputing backward, fp32 and fp64, 5 launches forward and at most 22 backward, no host read-back.
 // mf [B][H][W][8], um [B][H][W][9 r r], params [B][A][ldp >= 169], lvl [B][A], masks [B][M][rH][rW] (read in place through mg), fg / mg [B][A],

@@ -666,6 +666,147 @@ def head_det_loss(outputs, origin_preds, labels, x_shifts, y_shifts, expanded_st
     return losses, assignment
 
 
+HEAD_ASSEMBLE_MAX_LEVELS = 4
+HEAD_ASSEMBLE_TILE = 64           # anchors of one level per block (HA_TILE of csrc/kernels.h): shapes around it are the ragged ones
+
+
+def _ha_arrays(hs, ws, strides, layouts):
+    n = len(hs)
+    return ((C.c_int32 * n)(*hs), (C.c_int32 * n)(*ws), (C.c_double * n)(*strides), (C.c_int32 * n)(*layouts))
+
+
+def _ha_ptrs(ts):
+    """host array of the device pointers of `ts` (an entry None: NULL), or None for no list at all"""
+    return None if ts is None else (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+class HeadAssembleFunction(torch.autograd.Function):
+    """The head-output assembly (unicorn_head_mask.py:339-366, :476-500, the cats :396-401 / :554-558) as one launch forward and one backward:
+    apply(strides (tuple of L floats), use_l1, has_ctrl, *maps) with maps = the L reg maps (B, 4, h, w), the L obj maps (B, 1, h, w), the L cls
+    maps (B, C, h, w) and, with has_ctrl, the L controller maps (B, P, h, w) -> (outputs (B, A, 5 + C), origin_preds (B, A, 4) or None,
+    x_shifts, y_shifts, expanded_strides (1, A), dynamic_params (B, A, P) or None, fpn_levels (B, A) int32 or None).  Maps fp32 / fp16 / bf16
+    -> results fp32, or all fp64 (ops.head_assemble checks).  NCHW-contiguous and channels-last memory are read in place per map, other
+    strides are converted once.  Saves the reg maps only.  Gradients in the dtype and layout of their map, only those autograd asks for; an
+    unused result costs no zero tensor.  The shifts, strides and levels are not differentiable.  No host synchronisation, no host-built
+    tensor, one writer per element: bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, strides, use_l1, has_ctrl, *maps):
+        ctx.set_materialize_grads(False)
+        Ln = len(strides)
+        laid = [_map_layout(m) for m in maps]
+        roles = [[t for t, _ in laid[r * Ln:(r + 1) * Ln]] for r in range(4 if has_ctrl else 3)]
+        reg, obj, cls = roles[:3]
+        ctrl = roles[3] if has_ctrl else None
+        layouts = [sum(laid[r * Ln + k][1] << r for r in range(len(roles))) for k in range(Ln)]
+        B, Cn, P = reg[0].shape[0], cls[0].shape[1], ctrl[0].shape[1] if has_ctrl else 0
+        hs, ws = [t.shape[2] for t in reg], [t.shape[3] for t in reg]
+        A, dev, mdt = sum(h * w for h, w in zip(hs, ws)), reg[0].device, reg[0].dtype
+        dt = torch.float64 if mdt == torch.float64 else torch.float32
+        outputs = torch.empty((B, A, 5 + Cn), device=dev, dtype=dt)
+        origin = torch.empty((B, A, 4), device=dev, dtype=dt) if use_l1 else None
+        xs, ys, st = (torch.empty((1, A), device=dev, dtype=dt) for _ in range(3))
+        params = torch.empty((B, A, P), device=dev, dtype=dt) if has_ctrl else None
+        levels = torch.empty((B, A), device=dev, dtype=torch.int32) if has_ctrl else None
+        ctx.geom = (hs, ws, tuple(strides), layouts, Ln, B, Cn, P, _STORE_DTYPE[mdt])
+        ctx.shapes = [(t.shape, t.dtype) for r in roles for t in r]
+        ctx.save_for_backward(*reg)
+        fn, name = _entry("uni_head_assemble_fwd", dt)
+        with torch.cuda.device(dev):
+            L.check(fn(_ha_ptrs(reg), _ha_ptrs(obj), _ha_ptrs(cls), _ha_ptrs(ctrl), *_ha_arrays(hs, ws, strides, layouts), Ln, B, Cn, P,
+                       _STORE_DTYPE[mdt], L.ptr(outputs), 5 + Cn, L.ptr(origin), L.ptr(xs), L.ptr(ys), L.ptr(st), L.ptr(params),
+                       P, L.ptr(levels), L.stream_ptr()), name)
+        ctx.mark_non_differentiable(*[t for t in (xs, ys, st, levels) if t is not None])
+        return outputs, origin, xs, ys, st, params, levels
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_org, _gx, _gy, _gs, g_par, _gl):
+        hs, ws, strides, layouts, Ln, B, Cn, P, code = ctx.geom
+        reg = ctx.saved_tensors
+        nroles = len(ctx.shapes) // Ln
+        need = ctx.needs_input_grad[3:]
+        # a gradient that nobody sent is a zero: its maps get none (autograd reads None as zero), the others read a NULL pointer as zero
+        live = (g_out is not None or g_org is not None, g_out is not None, g_out is not None, g_par is not None)
+        grads = [None] * len(need)
+        for r in range(nroles):
+            for k in range(Ln):
+                i = r * Ln + k
+                if need[i] and live[r]:
+                    shape, dtype = ctx.shapes[i]
+                    grads[i] = torch.empty(shape, device=reg[0].device, dtype=dtype,
+                                           memory_format=torch.contiguous_format if (layouts[k] >> r) & 1 else torch.channels_last)
+        if any(g is not None for g in grads):
+            dt = torch.float64 if reg[0].dtype == torch.float64 else torch.float32
+            g_out = None if g_out is None else _hl_rows(g_out, 5 + Cn)
+            g_org = None if g_org is None else g_org.contiguous()
+            g_par = None if g_par is None else _hl_rows(g_par, P)
+            fn, name = _entry("uni_head_assemble_bwd", dt)
+            per_role = [grads[r * Ln:(r + 1) * Ln] for r in range(nroles)] + [None] * (4 - nroles)
+            with torch.cuda.device(reg[0].device):
+                L.check(fn(_ha_ptrs(list(reg)), *_ha_arrays(hs, ws, strides, layouts), Ln, B, Cn, P, code, L.ptr(g_out),
+                           0 if g_out is None else g_out.stride(1), L.ptr(g_org), L.ptr(g_par), 0 if g_par is None else g_par.stride(1),
+                           *[_ha_ptrs(p) if p is not None and any(t is not None for t in p) else None for p in per_role], L.stream_ptr()), name)
+        return (None, None, None) + tuple(grads)
+
+
+def head_assemble(reg_outputs, obj_outputs, cls_outputs, strides, controller_outputs=None, use_l1=True):
+    """The training-time lines of the heads' forward between the prediction convolutions and get_losses (unicorn_head_mask.py:339-366 with
+    get_output_and_grid :476-500 and the level cats :396-401 / :554-558; identically unicorn_head.py, yolo_head_det.py, yolo_head_det_mask.py)
+    for all levels and the whole batch in one launch, differentiable in every map, n_anchors == 1.
+      reg_outputs, obj_outputs, cls_outputs   lists of L <= 4 maps (B, 4, h_l, w_l), (B, 1, h_l, w_l), (B, C, h_l, w_l)
+      controller_outputs                      None or a list of L maps (B, P, h_l, w_l) (P = 169 in the reference)
+      strides                                 L positive numbers
+    All maps of one call fp32, fp16 or bf16 (read as stored, decoded in fp32: wider than the reference's fp16 decode under autocast, whose
+    exp overflows above 11.09) with fp32 results, or all fp64 with fp64 results.  NCHW-contiguous and channels-last memory are read in place,
+    per map; other strides are converted once.  With anchor a = off_l + y w_l + x:
+    -> (outputs (B, A, 5 + C) = (reg0 + x) s, (reg1 + y) s, exp(reg2) s, exp(reg3) s, obj, cls -- the fp32 bits of the eager lines in columns
+        0, 1, 4 and up; origin_preds (B, A, 4) = reg, or None with use_l1 False; x_shifts, y_shifts, expanded_strides (1, A); dynamic_params
+        (B, A, P) and fpn_levels (B, A) int32, or None, None without controller maps)
+    as get_losses / ops.head_det_loss / ops.head_mask_loss take them.  Gradients reach every map that requires one, in its dtype and layout,
+    rounded once; the shifts, strides and levels carry none.  Autograd keeps the reg maps and nothing else.  No host synchronisation, no
+    host-to-device copy.  1 <= C <= 256, 1 <= P <= 1024, 1 <= B <= 65535, A < 2^24."""
+    op = "head_assemble"
+    names = ("reg_outputs", "obj_outputs", "cls_outputs") + (() if controller_outputs is None else ("controller_outputs",))
+    lists = (reg_outputs, obj_outputs, cls_outputs) + (() if controller_outputs is None else (controller_outputs,))
+    for n, ts in zip(names, lists):
+        if not isinstance(ts, (list, tuple)):
+            raise L.UnicornHipError("%s: %s is not a list of maps" % (op, n))
+        _check_tensors(op, ["%s[%d]" % (n, k) for k in range(len(ts))], ts)
+    Ln = len(reg_outputs)
+    if not 1 <= Ln <= HEAD_ASSEMBLE_MAX_LEVELS or any(len(ts) != Ln for ts in lists):
+        raise L.UnicornHipError("%s: %s maps per role do not fit 1 <= L <= %d levels, the same for every role"
+                                % (op, " / ".join(str(len(ts)) for ts in lists), HEAD_ASSEMBLE_MAX_LEVELS))
+    try:
+        strides = tuple(float(s) for s in strides)
+    except (TypeError, ValueError):
+        raise L.UnicornHipError("%s: strides %r are not %d numbers" % (op, strides, Ln))
+    if len(strides) != Ln or not all(0 < s < float("inf") for s in strides):
+        raise L.UnicornHipError("%s: strides %r are not %d positive numbers" % (op, strides, Ln))
+    for n, ts in zip(names, lists):
+        for k, t in enumerate(ts):
+            _check_map_dims(op, "%s[%d]" % (n, k), t)
+    B, Cn = reg_outputs[0].shape[0], cls_outputs[0].shape[1]
+    P = None if controller_outputs is None else controller_outputs[0].shape[1]
+    chans = (4, 1, Cn) + (() if P is None else (P,))
+    for n, ts, nc in zip(names, lists, chans):
+        for k, t in enumerate(ts):
+            if tuple(t.shape) != (B, nc) + tuple(reg_outputs[k].shape[2:]):
+                raise L.UnicornHipError("%s: %s[%d] of shape %s is not (%d, %d, %d, %d): the level's size with the role's channels"
+                                        % (op, n, k, tuple(t.shape), B, nc, reg_outputs[k].shape[2], reg_outputs[k].shape[3]))
+    A = sum(t.shape[2] * t.shape[3] for t in reg_outputs)
+    if not (1 <= B <= 65535 and 1 <= Cn <= 256 and (P is None or 1 <= P <= 1024) and all(t.shape[2] and t.shape[3] for t in reg_outputs)
+            and A < 1 << 24):
+        raise L.UnicornHipError("%s: shape B=%d C=%d P=%r levels %s is outside 1 <= B <= 65535, 1 <= C <= 256, 1 <= P <= 1024, non-empty levels "
+                                "with fewer than 2^24 anchors" % (op, B, Cn, P, [tuple(t.shape[2:]) for t in reg_outputs]))
+    every = [t for ts in lists for t in ts]
+    if reg_outputs[0].dtype not in _STORE_DTYPE or any(t.dtype != reg_outputs[0].dtype for t in every):
+        raise L.UnicornHipError("%s: dtypes %s unsupported (all maps fp32, fp16 or bf16, or all fp64)"
+                                % (op, ", ".join(sorted({str(t.dtype) for t in every}))))
+    _check_one_device(op, every)
+    return HeadAssembleFunction.apply(strides, bool(use_l1), controller_outputs is not None, *every)
+
+
 def _hm_ws(dev, dtype, B, A, H8, W8, r, cap):
     need = L.lib().uni_head_mask_loss_workspace_bytes(B, A, H8, W8, r, cap)
     if need == 0:
