@@ -9,7 +9,10 @@ against a reference (tests/train_plans.py holds the lists and says what a plan c
                          must both report the class under test -- against the operator's own restatement in fp64: 1e-12 for the fp64 twin,
                          4 x the restatement's own fp32 deviation on the same inputs for fp32, plus half an ulp of the half type on the
                          half-typed gradient for fp16 / bf16 x (lncf) or y (block_tail), the restatement then on the rounded tensor.  Two
-                         calls are bit-equal.  Failures are collected per class and reported once.
+                         calls are bit-equal.  Failures are collected per class and reported once.  ops.downsample_ln runs the
+                         channels-last kernel of lncf with another store address, so its kernels run alone (tests/down_calls.py, no
+                         GEMM) at both ends of every channels-last class too, against down_train_ref.patch_grads: the traced tags, a
+                         rebuilt A with the forward's bytes and exact zeros in g_x at the pixels an odd H or W drops.
   3. a block that loops at wide C: more groups / tiles / chunks than the 1024 blocks a launch may have (the existing many-pixel cases loop
      at C = 4 and 8 only), and dwln with four waves per strip on a map whose rows the weight pass splits.
 
@@ -24,6 +27,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import block_tail_ref as RB  # noqa: E402
+import down_calls as KD  # noqa: E402
+import down_train_ref as RDN  # noqa: E402
 import dwln_train_ref as RD  # noqa: E402
 import guard  # noqa: E402
 import lncf_ref as RL  # noqa: E402
@@ -51,7 +56,7 @@ def L():
     _lib.lib()
     assert torch.cuda.is_available(), "gpu tests need a HIP device"
     yield _lib
-    for cached in (lncf_case, bt_case, dwln_case):          # the wide cases hold their inputs and references on the device
+    for cached in (lncf_case, down_case, bt_case, dwln_case):          # the wide cases hold their inputs and references on the device
         cached.cache_clear()
 
 
@@ -167,11 +172,12 @@ def _report(bad):
     return "%d case(s) failed: %s\n%s" % (len(bad), ", ".join(bad), "\n".join("  %s: %s" % kv for kv in bad.items()))
 
 
-def _judge(bad, key, got, again, ref, dev, dt, half_result):
-    """collects into bad[key] every result outside its bound and every result that differs between the two calls"""
+def _judge(bad, key, got, again, ref, dev, dt, half_results):
+    """collects into bad[key] every result outside its bound (half_results: those a half dt rounds once more) and every result that differs
+    between the two calls"""
     for n in ref:
         err = RL.rel_err(got[n], ref[n])
-        bound = 1e-12 if dt == "f64" else 4 * dev[n] + (HALF_ULP[dt] if dt in HALF_ULP and n == half_result else 0.0)
+        bound = 1e-12 if dt == "f64" else 4 * dev[n] + (HALF_ULP[dt] if dt in HALF_ULP and n in half_results else 0.0)
         print("%-36s %-10s err %.3e  bound %.3e" % (key, n, err, bound))
         if not (got[n].shape == ref[n].shape and err <= bound):
             bad.setdefault(key, {})[n] = (err, bound)
@@ -214,7 +220,7 @@ def lncf_check(lib, bad, shape, dt, layout, cls, on_device=False):
     fwd, bwd = map_tags(tags, "lncf_train", "fwd"), map_tags(tags, "lncf_train", "bwd")
     if not (fwd == [cls] and bwd == [cls] and sum(tags.values()) == 3):         # forward, backward, reduce
         bad.setdefault(key, {})["trace"] = tags
-    _judge(bad, key, got, again, ref, dev, dt, "g_x")
+    _judge(bad, key, got, again, ref, dev, dt, ("g_x",))
 
 
 @pytest.mark.parametrize("layout,dt", LNCF_COMBOS, ids=["%s-%s" % c for c in LNCF_COMBOS])
@@ -225,6 +231,58 @@ def test_lncf_parity_at_both_ends_of_every_class(L, layout, dt):
     for cls, cs in classes.items():
         for C in P.ends(cs):
             lncf_check(L.lib(), bad, (P.MAP[0], C) + P.MAP[1:], dt, layout, cls)
+    assert not bad, _report(bad)
+
+
+# ---------------------------------------------------------------------------------------------------------------- down_train
+# ops.downsample_ln walks its input as lncf's channels-last plan says (csrc/ln_cl.h is the kernel of both), so its classes are those the
+# lncf sweep finds; its fixtures (tests/down_train_ref.py) reach NV <= 3 only.  The kernels alone through the C-ABI, no GEMM.
+@functools.lru_cache(maxsize=None)
+def down_case(C, half=None):
+    """x (MAP with C channels) and grad_A (M, 4 C), both rounded to `half` first (A has the element type of x here), the LayerNorm parameters,
+    the patch restatement in fp64 and its own fp32 deviation: computed once per case, shared, never modified"""
+    shape = (P.MAP[0], C) + P.MAP[1:]
+    x, w, b = RDN.draw("plain", sum(shape), shape, 4)[:3]
+    gA = torch.randn(P.MAP[0] * (P.MAP[1] // 2) * (P.MAP[2] // 2), 4 * C, generator=torch.Generator().manual_seed(C))
+    if half is not None:
+        x, gA = x.to(half).float(), gA.to(half).float()
+    ref = RDN.patch_grads(x, w, b, gA, dtype=torch.float64)
+    f32 = RDN.patch_grads(x, w, b, gA, dtype=torch.float32)
+    return (x, w, b, gA), ref, {n: RL.rel_err(f32[n], ref[n]) for n in ref}
+
+
+def down_run(L, ins, dt):
+    x, w, b, gA = ins
+    return KD.run_down(L, x.to(DEV, DT[dt]), w.to(DEV, _math(dt)), b.to(DEV, _math(dt)), gA.to(DEV, DT[dt]), DT[dt])
+
+
+def down_check(L, bad, C, dt, cls):
+    key = "%s C=%d" % (cls, C)
+    ins, ref, dev = down_case(C, _half_of(dt))
+    got, tags = traced(L.lib(), lambda: down_run(L, ins, dt))
+    again = down_run(L, ins, dt)
+    want = {"down_train fwd_%s a=%s" % (cls, dt): 1, "down_train rebuild_%s a=%s" % (cls, dt): 1,
+            "down_train bwd_%s a=%s gx=1 gwb=1" % (cls, dt): 1, "down_train reduce<%s>" % ("f64" if dt == "f64" else "f32"): 1}
+    if tags != want:
+        bad.setdefault(key, {})["trace"] = tags
+    if not torch.equal(got["A"].view(torch.uint8), got["A2"].view(torch.uint8)):
+        bad.setdefault(key, {})["A2"] = "the rebuilt A differs from the forward's"
+    Ho, Wo = P.MAP[1] // 2, P.MAP[2] // 2                   # H = 3 and W = 7 drop the last row and the last column
+    if got["g_x"][:, :, 2 * Ho:, :].any() or got["g_x"][:, :, :, 2 * Wo:].any():
+        bad.setdefault(key, {})["g_x"] = "not zero at a dropped pixel"
+    _judge(bad, key, got, again, ref, dev, dt, ("A", "g_x"))
+
+
+@pytest.mark.parametrize("dt", ["f32", "f16", "bf16", "f64"])
+def test_down_parity_at_both_ends_of_every_class(L, dt):
+    """bounds as for lncf above, from the restatement alone: 1e-12 for fp64, else 4 x the deviation of the fp32 patch_grads from its fp64 run
+    on the same inputs, plus half an ulp of the half type on A and on g_x, which are then rounded once more"""
+    classes = P.group(sweep("lncf", "cl", dt))
+    assert classes
+    bad = {}
+    for cls, cs in classes.items():
+        for C in P.ends(cs):
+            down_check(L, bad, C, dt, cls)
     assert not bad, _report(bad)
 
 
@@ -259,7 +317,7 @@ def dwln_check(lib, bad, shape, dt, cls):
     kernels = [map_tags(tags, "dwln_train", k) for k in ("fwd", "bwd_a", "bwd_dx")]
     if not (kernels == [[cls]] * 3 and sum(tags.values()) == 5):               # + the weight pass and the reduce
         bad.setdefault(key, {})["trace"] = tags
-    _judge(bad, key, got, again, ref, dev, dt, None)
+    _judge(bad, key, got, again, ref, dev, dt, ())
 
 
 @pytest.mark.parametrize("dt", DWLN_COMBOS)
@@ -310,7 +368,7 @@ def bt_check(lib, bad, shape, dt, layout, on_device=False):
     fwd, bwd = map_tags(tags, "block_tail", "fwd"), map_tags(tags, "block_tail", "bwd")
     if not (fwd == [cls] and bwd == [cls] and sum(tags.values()) == 3):         # forward, backward, reduce
         bad.setdefault(key, {})["trace"] = tags
-    _judge(bad, key, got, again, ref, dev, dt, "g_y")
+    _judge(bad, key, got, again, ref, dev, dt, ("g_y",))
 
 
 @pytest.mark.parametrize("layout,dt", BT_COMBOS, ids=["%s-%s" % c for c in BT_COMBOS])

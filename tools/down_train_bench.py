@@ -48,7 +48,7 @@ SITES = (("stem", (2, 3, 800, 1280), 192), ("downsample 1", (2, 192, 200, 320), 
 
 
 def variant_name(mangled):
-    """`_Z14down_cl_kernelIfDF16_Li8ELi3ELi0EEv...` -> `down_cl_kernel<f32,f16,8,3,0>` (the few Itanium codes these kernels use)"""
+    """`_Z12ln_cl_kernelIfDF16_Li8ELi3ELi0E6DownIOEv...` -> `ln_cl_kernel<f32,f16,8,3,0,DownIO>` (the few Itanium codes these kernels use)"""
     m = re.match(r"_Z(\d+)", mangled)
     if not m:
         return mangled
@@ -63,6 +63,12 @@ def variant_name(mangled):
         if lit:
             args.append(lit.group(1))
             rest = rest[lit.end():]
+            continue
+        named = re.match(r"(\d+)", rest)                           # a class that is no template: the policy of ln_cl_kernel
+        if named:
+            end = named.end() + int(named.group(1))
+            args.append(rest[named.end():end])
+            rest = rest[end:]
             continue
         for code, text in codes:
             if rest.startswith(code):
@@ -95,11 +101,11 @@ def resources(say, remarks):
             cur[m.group(1)] = m.group(2)
     names = [variant_name(k["name"]) for k in kernels]
     say("kernel variants of down_train.hip (gfx950, -O3): VGPRs / AGPRs / SGPRs, LDS bytes per block (static; the backward with partials adds")
-    say("16 C bytes of dynamic LDS), scratch bytes per lane, waves per SIMD.  Template arguments: <T, XT, V, NV, MODE> (MODE 0 forward and rebuild,")
-    say("1 backward) and <XT, AT, SCATTER>.")
+    say("16 C bytes of dynamic LDS), scratch bytes per lane, waves per SIMD.  Template arguments: <T, XT, V, NV, MODE, policy> (csrc/ln_cl.h; MODE 0")
+    say("forward and rebuild, 1 backward) and <XT, AT, SCATTER>.")
     for k, n in zip(kernels, names):
         short = n
-        say("  %-44s VGPR %3s AGPR %3s SGPR %3s  LDS %5s  scratch %s  occupancy %s"
+        say("  %-48s VGPR %3s AGPR %3s SGPR %3s  LDS %5s  scratch %s  occupancy %s"
             % (short, k.get("VGPRs"), k.get("AGPRs"), k.get("TotalSGPRs"), k.get("LDS Size"), k.get("ScratchSize"), k.get("Occupancy")))
     spill = [n for k, n in zip(kernels, names) if k.get("ScratchSize") != "0"]
     say("%d variants; variants that use scratch: %s" % (len(kernels), ", ".join(spill) or "none"))

@@ -1,11 +1,11 @@
-// What do the launchers of the four ConvNeXt training operators launch?  No GPU: the host code of a tree's units is compiled against a
+// What do the launchers of the five ConvNeXt training operators launch?  No GPU: the host code of a tree's units is compiled against a
 // recording stand-in for hipLaunchKernelGGL, so every launch prints (kernel instantiation, grid, block, dynamic LDS, the integral kernel
 // arguments) instead of running.  Two trees that print the same table launch the same kernels the same way.
 //
-//   for u in dwln_train block_tail lncf_train pw_mlp; do
+//   for u in dwln_train block_tail lncf_train down_train pw_mlp; do
 //     hipcc --cuda-host-only -O1 -std=c++17 -I TREE/unicorn_amd/csrc -DRECORD_UNIT="\"$u.hip\"" -c tools/train_launch_record.hip -o $u.o; done
 //   hipcc --cuda-host-only -O1 -std=c++17 -I TREE/unicorn_amd/csrc -c tools/train_launch_record.hip -o driver.o
-//   hipcc driver.o dwln_train.o block_tail.o lncf_train.o pw_mlp.o -o record && ./record > table.txt
+//   hipcc driver.o dwln_train.o block_tail.o lncf_train.o down_train.o pw_mlp.o -o record && ./record > table.txt
 //
 // With RECORD_UNIT this file is that unit with the launch macro replaced; without, the driver that walks the shapes.  Pointers are made up
 // (nothing is dereferenced on the host).  profiles/train_plan_shared.txt holds a comparison made this way.
@@ -19,7 +19,7 @@
 void record_launch(const char* mangled, dim3 grid, dim3 block, size_t lds, const std::string& args);
 
 #ifdef RECORD_UNIT
-#include "train_ops.h"
+struct DwlnRJob;                                // train_ops.h, which launches too: it is read below, after the launch macro is replaced
 template <auto K>
 struct KernelName {};                           // its mangled name holds that of the instantiation: the driver demangles it
 template <typename A, typename = void>
@@ -33,10 +33,7 @@ static void record_arg(std::string& s, const A& a) {
         s += " CG=" + std::to_string(a.CG) + " CGp=" + std::to_string(a.CGp) + " NS=" + std::to_string(a.NS) + " segs=" + std::to_string(a.segs) +
              " nstrips=" + std::to_string(a.nstrips);
 }
-static void record_arg(std::string& s, const DwlnRJob& j) {         // the partials a reduce job reads: byte offset in the workspace, rows, columns
-    s += " job(" + (j.blocks ? std::to_string(reinterpret_cast<uintptr_t>(j.part) - 0x10000) : std::string("-")) + " R=" + std::to_string(j.R) +
-         " N=" + std::to_string(j.N) + " n1=" + std::to_string(j.n1) + " blocks=" + std::to_string(j.blocks) + ")";
-}
+static void record_arg(std::string& s, const DwlnRJob& j);
 template <typename... A>
 static std::string record_args(const A&... a) {
     std::string s;
@@ -46,6 +43,11 @@ static std::string record_args(const A&... a) {
 #undef hipLaunchKernelGGL
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) \
     ((void)(stream), record_launch(typeid(KernelName<kernel>).name(), grid, block, lds, record_args(__VA_ARGS__)))
+#include "train_ops.h"
+static void record_arg(std::string& s, const DwlnRJob& j) {         // the partials a reduce job reads: byte offset in the workspace, rows, columns
+    s += " job(" + (j.blocks ? std::to_string(reinterpret_cast<uintptr_t>(j.part) - 0x10000) : std::string("-")) + " R=" + std::to_string(j.R) +
+         " N=" + std::to_string(j.N) + " n1=" + std::to_string(j.n1) + " blocks=" + std::to_string(j.blocks) + ")";
+}
 #include RECORD_UNIT
 
 #else
@@ -68,7 +70,7 @@ void uni_set_error(const char* fmt, ...) {
 }
 void record_launch(const char* mangled, dim3 grid, dim3 block, size_t lds, const std::string& args) {
     int status = 0;
-    char* plain = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);       // "KernelName<&lncf_cl_kernel<float, _Float16, 8, 3, 1>(LncfK<float>, ...)>"
+    char* plain = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);       // "KernelName<&ln_cl_kernel<float, _Float16, 8, 3, 1, DownIO>(LnClK<float>, DownIO, ...)>"
     std::string name = status == 0 ? plain : mangled;
     std::free(plain);
     if (name.rfind("KernelName<&", 0) == 0) name = name.substr(12, name.size() - 13);
@@ -99,6 +101,16 @@ static void run(const char* tn) {
                     const BtArgs<T> b{fake<void>(), dt, fake<T>(), nchw, fake<T>(), fake<T>(), m.B, m.H, m.W, C};
                     launch_block_tail_fwd<T>(b, fake<T>(), nullptr);
                     launch_block_tail_bwd<T>(b, fake<void>(), fake<T>(), fake<void>(), big, nullptr);
+                }
+            // downsample_ln: x and A of one element type, and fp32 x into a bf16 A
+            for (int dt = 0; dt < (sizeof(T) == 8 ? 1 : 3); ++dt)
+                for (int ad = dt; ad < (sizeof(T) == 8 ? 1 : 3); ad += 2) {
+                    std::printf("down<%s> x=%s a=%s B=%d H=%d W=%d C=%d\n", tn, DT[dt], DT[ad], m.B, m.H, m.W, C);
+                    const DownArgs<T> a{fake<void>(), dt, ad, fake<T>(), fake<T>(), 1e-6, m.B, m.H, m.W, C};
+                    launch_down_train_fwd<T>(a, 0, fake<void>(), fake<T>(), nullptr);
+                    launch_down_train_fwd<T>(a, 1, fake<void>(), fake<T>(), nullptr);
+                    launch_down_train_bwd<T>(a, fake<T>(), fake<void>(), fake<void>(), fake<T>(), fake<T>(), fake<void>(), big, nullptr);
+                    launch_down_train_bwd<T>(a, fake<T>(), fake<void>(), fake<void>(), nullptr, nullptr, nullptr, 0, nullptr);
                 }
             std::printf("dwln<%s> B=%d H=%d W=%d C=%d\n", tn, m.B, m.H, m.W, C);
             const DwlnArgs<T> d{fake<T>(), fake<T>(), fake<T>(), fake<T>(), fake<T>(), 1e-6, m.B, m.H, m.W, C};

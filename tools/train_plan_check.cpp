@@ -59,7 +59,7 @@ static void check_lncf(const LncfPlan& q, const Map& m, int C, const Etype& e, b
     const long long M = (long long)m.B * m.H * m.W;
     const size_t tsize = e.f64 ? 8 : 4;
     const bool cl = q.family == LNCF_CL;
-    // lncf_nchw_kernel: sm[2][2][LNCF_NW][64] of the math type, __launch_bounds__(512); lncf_cl_kernel: no static LDS, __launch_bounds__(256)
+    // lncf_nchw_kernel: sm[2][2][LNCF_NW][64] of the math type, __launch_bounds__(512); ln_cl_kernel (ln_cl.h): no static LDS, __launch_bounds__(256)
     check_launch(q.grid, 1, q.block, cl ? 256 : 512, cl ? 0 : 2 * 2 * LNCF_NW * 64 * tsize, q.lds);
     REQUIRE(q.units >= 1 && q.units <= M, "%u work units, %lld pixels", q.units, M);
     REQUIRE(q.grid <= (long long)q.units, "grid %d, %u work units", q.grid, q.units);

@@ -12,211 +12,53 @@
 //                   part[block][2][C] = the block's sums of grad_A * xhat and of grad_A -> dwln_reduce_kernel (train_ops.h)
 //   stem patches    x [B][Cin][H][W] (NCHW-contiguous) <-> A [M][Cin 16], column (c 4 + kh) 4 + kw: the order of weight.reshape(Co, Cin 16)
 //
-//   down_cl_kernel<V, NV, MODE>   the lane mapping of lncf_cl_kernel (lncf_train.hip; lncf_plan, channels-last): a pixel belongs to G lanes of ONE
-//                                 wave, a lane owns NV vectors of V consecutive channels, the row of a pixel is in registers, the variance is
-//                                 the second pass over registers, a sum over C is a butterfly over the G lanes.  MODE 0 = forward (stats_in
-//                                 NULL) and rebuild (stats_in given: the statistics are read instead of computed, stats_out is not written;
-//                                 every other instruction is shared, so A has the forward's bits), 1 = backward.  The element type of A is a
-//                                 run-time argument: one branch per vector, uniform in the launch.
+//   ln_cl_kernel<V, NV, MODE, DownIO>  the kernel of ln_cl.h, which lncf_train.hip runs too (lncf_plan, channels-last), with the policy below: the
+//                                 row of a pixel is its run of C elements in A / grad_A, and a dropped pixel has none.  MODE 0 = forward
+//                                 (stats_in NULL) and rebuild (stats_in given: A has the forward's bits), 1 = backward.
 //   patch4_kernel<SCATTER>        a lane takes the four elements kw = 0 .. 3 of a patch row: one 16-byte (8-byte) access on the side of A,
 //                                 four element accesses on the side of x (W need not be a multiple of 4)
 //
 // Every output element has one writer, no atomics, fixed summation orders: bitwise reproducible.  Element offsets are 64-bit (A can pass 2^31
 // elements); pixel and group indices fit 32 bits (B H W < 2^31 is required).
 #include "kernels.h"
-#include "train_ops.h"
+#include "ln_cl.h"
 
-template <typename T>
-struct DownK {                                  // kernel arguments (by value)
-    const void* x;
-    const T *w, *bias, *stats_in;
-    const void* ga;                             // the element type of A
+// the row of a pixel in the patch matrix A (MODE 0) / grad_A (MODE 1) for ln_cl_kernel (ln_cl.h).  The element type of A is a run-time
+// argument: one branch per vector, uniform in the launch (the fp64 form has one type)
+struct DownIO {
+    static constexpr bool REBUILD = true;
     void* a;
-    T* stats_out;
-    void* gx;                                   // the element type of x
-    T* part;
-    T eps;
+    const void* ga;
     int a_dtype;
-    int H, W, Ho, Wo, C;
-    long long M;                                // B H W
-};
-
-template <typename T>
-__device__ __forceinline__ T down_group_sum(T v, int G) {      // lncf_group_sum
-    for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// V elements of the patch matrix at element offset `off`, in the element type a_dtype names (the fp64 form has one)
-template <typename T, int V>
-__device__ __forceinline__ void down_a_store(void* a, size_t off, int a_dtype, const T (&r)[V]) {
-    if constexpr (sizeof(T) == 8) {
-        vec_store<double, V>(reinterpret_cast<double*>(a) + off, r);
-    } else {
-        if (a_dtype == 0) vec_store<float, V>(reinterpret_cast<float*>(a) + off, r);
-        else if (a_dtype == 1) vec_store<f16, V>(reinterpret_cast<f16*>(a) + off, r);
-        else vec_store<bf16, V>(reinterpret_cast<bf16*>(a) + off, r);
+    int H, W, Ho, Wo;
+    // kept = the pixel lies inside the 2 Ho x 2 Wo region the convolution reads
+    static __device__ __forceinline__ void place(DownIO io, long long pix, bool live, int C, bool& kept, size_t& ea) {
+        const int HW = io.H * io.W;
+        const int n = live ? (int)(pix / HW) : 0, r = live ? (int)(pix - (long long)n * HW) : 0, h = r / io.W, w = r - h * io.W;
+        kept = live && (h >> 1) < io.Ho && (w >> 1) < io.Wo;
+        ea = (((size_t)n * io.Ho + (h >> 1)) * io.Wo + (w >> 1)) * 4 * C + (size_t)((h & 1) * 2 + (w & 1)) * C;
     }
-}
-template <typename T, int V>
-__device__ __forceinline__ void down_a_load(const void* a, size_t off, int a_dtype, T (&r)[V]) {
-    if constexpr (sizeof(T) == 8) {
-        vec_load<double, V>(reinterpret_cast<const double*>(a) + off, r);
-    } else {
-        if (a_dtype == 0) vec_load<float, V>(reinterpret_cast<const float*>(a) + off, r);
-        else if (a_dtype == 1) vec_load<f16, V>(reinterpret_cast<const f16*>(a) + off, r);
-        else vec_load<bf16, V>(reinterpret_cast<const bf16*>(a) + off, r);
-    }
-}
-
-extern __shared__ double down_dyn_lds[];
-
-template <typename T, typename XT, int V, int NV, int MODE>
-__global__ __launch_bounds__(256) void down_cl_kernel(DownK<T> p, int G, int lgG, unsigned ngroups) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = tid & (G - 1), slot = tid >> lgG, PPB = 256 >> lgG;
-    const int C = p.C, nvec = C / V, HW = p.H * p.W;
-    const T cnt = T(C);
-    bool vok[NV];
-    int c[NV];
-    T wv[NV][V], bv[NV][V], dg[NV][V], db[NV][V];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int vec = k * G + g;
-        vok[k] = vec < nvec;
-        c[k] = vec * V;
-#pragma unroll
-        for (int j = 0; j < V; ++j) wv[k][j] = bv[k][j] = dg[k][j] = db[k][j] = T(0);
-        if (vok[k]) {
-            vec_load<T, V>(p.w + c[k], wv[k]);
-            if (MODE == 0) vec_load<T, V>(p.bias + c[k], bv[k]);
-        }
-    }
-    for (unsigned grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const long long pix = (long long)grp * PPB + slot;
-        const bool live = pix < p.M;            // the same in the G lanes of a pixel
-        // the patch element of the pixel: kept = it lies inside the 2 Ho x 2 Wo region the convolution reads
-        const int n = live ? (int)(pix / HW) : 0, r = live ? (int)(pix - (long long)n * HW) : 0, h = r / p.W, w = r - h * p.W;
-        const bool kept = live && (h >> 1) < p.Ho && (w >> 1) < p.Wo;
-        const size_t ea = (((size_t)n * p.Ho + (h >> 1)) * p.Wo + (w >> 1)) * 4 * C + (size_t)((h & 1) * 2 + (w & 1)) * C;
-        const size_t e = (size_t)pix * C;
-        const bool rd = MODE == 0 ? live : kept;        // the backward does not read a dropped pixel
-        T xv[NV][V];
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-#pragma unroll
-            for (int j = 0; j < V; ++j) xv[k][j] = T(0);
-            if (rd && vok[k]) vec_load<XT, V>(reinterpret_cast<const XT*>(p.x) + e + c[k], xv[k]);
-        }
-        if (MODE == 0) {
-            T mean, rstd;
-            if (p.stats_in) {                   // rebuild; uniform in the launch
-                mean = live ? p.stats_in[(size_t)pix * 2] : T(0);
-                rstd = live ? p.stats_in[(size_t)pix * 2 + 1] : T(0);
-#pragma unroll
-                for (int k = 0; k < NV; ++k)
-#pragma unroll
-                    for (int j = 0; j < V; ++j) xv[k][j] = vok[k] ? xv[k][j] - mean : T(0);
-            } else {
-                T s = 0;
-#pragma unroll
-                for (int k = 0; k < NV; ++k)
-#pragma unroll
-                    for (int j = 0; j < V; ++j) s += xv[k][j];
-                mean = down_group_sum(s, G) / cnt;
-                T q = 0;
-#pragma unroll
-                for (int k = 0; k < NV; ++k)
-#pragma unroll
-                    for (int j = 0; j < V; ++j) {
-                        xv[k][j] = vok[k] ? xv[k][j] - mean : T(0);
-                        q += xv[k][j] * xv[k][j];
-                    }
-                rstd = T(1) / sqrt(down_group_sum(q, G) / cnt + p.eps);
-                if (live && g == 0) {
-                    p.stats_out[(size_t)pix * 2] = mean;
-                    p.stats_out[(size_t)pix * 2 + 1] = rstd;
-                }
-            }
-            if (kept) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) {
-                    if (!vok[k]) continue;
-                    T o[V];
-#pragma unroll
-                    for (int j = 0; j < V; ++j) o[j] = (xv[k][j] * rstd) * wv[k][j] + bv[k][j];
-                    down_a_store<T, V>(p.a, ea + c[k], p.a_dtype, o);
-                }
-            }
+    template <int V, typename T>
+    static __device__ __forceinline__ void store(DownIO io, size_t off, const T (&r)[V]) {
+        if constexpr (sizeof(T) == 8) {
+            vec_store<double, V>(reinterpret_cast<double*>(io.a) + off, r);
         } else {
-            T gv[NV][V];
-            T mean = 0, rstd = 0;
-            if (kept) {
-                mean = p.stats_in[(size_t)pix * 2];
-                rstd = p.stats_in[(size_t)pix * 2 + 1];
-            }
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-#pragma unroll
-                for (int j = 0; j < V; ++j) gv[k][j] = T(0);
-                if (kept && vok[k]) down_a_load<T, V>(p.ga, ea + c[k], p.a_dtype, gv[k]);
-            }
-            T s1 = 0, s2 = 0;
-#pragma unroll
-            for (int k = 0; k < NV; ++k)
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const T xh = vok[k] ? (xv[k][j] - mean) * rstd : T(0);
-                    const T t = gv[k][j] * wv[k][j];
-                    if (p.part) {
-                        dg[k][j] += gv[k][j] * xh;
-                        db[k][j] += gv[k][j];
-                    }
-                    s1 += t;
-                    s2 += t * xh;
-                    xv[k][j] = xh;
-                    gv[k][j] = t;
-                }
-            if (p.gx) {
-                const T a = down_group_sum(s1, G) / cnt, b = down_group_sum(s2, G) / cnt;
-                if (live) {
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) {
-                        if (!vok[k]) continue;
-                        T o[V];
-#pragma unroll
-                        for (int j = 0; j < V; ++j) o[j] = kept ? rstd * (gv[k][j] - a - xv[k][j] * b) : T(0);
-                        vec_store<XT, V>(reinterpret_cast<XT*>(p.gx) + e + c[k], o);
-                    }
-                }
-            }
+            if (io.a_dtype == 0) vec_store<float, V>(reinterpret_cast<float*>(io.a) + off, r);
+            else if (io.a_dtype == 1) vec_store<f16, V>(reinterpret_cast<f16*>(io.a) + off, r);
+            else vec_store<bf16, V>(reinterpret_cast<bf16*>(io.a) + off, r);
         }
     }
-    if (MODE == 1 && p.part) {                  // as lncf_cl_kernel: the pixel slots of a wave by butterfly, then the four waves in ascending
-        double* sg = down_dyn_lds;              // order -> one row [2][C]; in double
-        for (int w = 0; w < 4; ++w) {
-            if (wave == w) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) {
-#pragma unroll
-                    for (int j = 0; j < V; ++j) {
-                        double a = (double)dg[k][j], b = (double)db[k][j];
-                        for (int o = G; o < 64; o <<= 1) {
-                            a += __shfl_xor(a, o, 64);
-                            b += __shfl_xor(b, o, 64);
-                        }
-                        if (lane < G && vok[k]) {
-                            sg[c[k] + j] = (w ? sg[c[k] + j] : 0.0) + a;
-                            sg[C + c[k] + j] = (w ? sg[C + c[k] + j] : 0.0) + b;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
+    template <int V, typename T>
+    static __device__ __forceinline__ void load(DownIO io, size_t off, T (&r)[V]) {
+        if constexpr (sizeof(T) == 8) {
+            vec_load<double, V>(reinterpret_cast<const double*>(io.ga) + off, r);
+        } else {
+            if (io.a_dtype == 0) vec_load<float, V>(reinterpret_cast<const float*>(io.ga) + off, r);
+            else if (io.a_dtype == 1) vec_load<f16, V>(reinterpret_cast<const f16*>(io.ga) + off, r);
+            else vec_load<bf16, V>(reinterpret_cast<const bf16*>(io.ga) + off, r);
         }
-        for (int i = tid; i < 2 * C; i += 256) p.part[(size_t)blockIdx.x * 2 * C + i] = (T)sg[i];
     }
-}
+};
 
 // stem patches.  gather: unit u = (m Cin + c) 4 + kh -> A[u 4 ..] = x[n][c][4 ho + kh][4 wo ..].  scatter: unit u = ((n Cin + c) H + h) wg + j
 // -> grad_x[n][c][h][4 j ..] = grad_A[...] inside the 4 Ho x 4 Wo region, zeros in the margin (the group j = Wo is the margin of a row).
@@ -283,7 +125,7 @@ static inline int down_shape_refused(const char* what, int B, int H, int W, int 
 
 // launches mode MODE with the element type XT of x as lncf_plan (train_plan.h, channels-last) says; *rows = the rows of partials it writes
 template <typename T, typename XT, int MODE>
-static void down_launch(const DownArgs<T>& a, const DownK<T>& k, int* rows, hipStream_t s) {
+static void down_launch(const DownArgs<T>& a, const LnClK<T>& k, const DownIO& io, int* rows, hipStream_t s) {
     const LncfPlan q = lncf_plan(a.B, a.H, a.W, a.C, sizeof(XT), sizeof(T) == 8, false, MODE == 1 && k.part);
     *rows = q.rows;
     char cls[64] = "";
@@ -291,29 +133,12 @@ static void down_launch(const DownArgs<T>& a, const DownK<T>& k, int* rows, hipS
     if (train_tracing()) down_plan_class(q, train_ename(a.x_dtype, f64), train_ename(a.a_dtype, f64), cls, sizeof(cls));
     if (MODE == 1) uni_variant_note("down_train bwd_%s gx=%d gwb=%d", cls, k.gx != nullptr, k.part != nullptr);
     else uni_variant_note("down_train %s_%s", k.stats_in ? "rebuild" : "fwd", cls);
-    train_with_vwidth<XT>(q.V, [&](auto vtag) {
-        constexpr int V = decltype(vtag)::value;
-        auto run = [&](auto ntag) {
-            constexpr int NV = decltype(ntag)::value;
-            hipLaunchKernelGGL((down_cl_kernel<T, XT, V, NV, MODE>), dim3(q.grid), dim3(q.block), q.lds, s, k, 1 << q.lg, q.lg, q.units);
-        };
-        switch (q.NV) {
-            case 1: run(std::integral_constant<int, 1>()); break;
-            case 2: run(std::integral_constant<int, 2>()); break;
-            case 3: run(std::integral_constant<int, 3>()); break;
-            case 4: run(std::integral_constant<int, 4>()); break;
-            default:                            // 6 or 8: more than 256 vectors, so V = 4
-                if constexpr (V == 4) {
-                    if (q.NV == 6) run(std::integral_constant<int, 6>());
-                    else run(std::integral_constant<int, 8>());
-                }
-        }
-    });
+    ln_cl_launch<T, XT, MODE>(q, k, io, s);
 }
 
 template <typename T, int MODE>
-static int down_dispatch(const char* what, const DownArgs<T>& a, const DownK<T>& k, int* rows, hipStream_t s) {
-    return train_with_etype<T>(what, "x_dtype", a.x_dtype, [&](auto e) { down_launch<T, typename decltype(e)::type, MODE>(a, k, rows, s); });
+static int down_dispatch(const char* what, const DownArgs<T>& a, const LnClK<T>& k, const DownIO& io, int* rows, hipStream_t s) {
+    return train_with_etype<T>(what, "x_dtype", a.x_dtype, [&](auto e) { down_launch<T, typename decltype(e)::type, MODE>(a, k, io, rows, s); });
 }
 
 template <typename T>
@@ -325,24 +150,24 @@ static int down_check(const char* what, const DownArgs<T>& a) {
 }
 
 template <typename T>
-static DownK<T> down_args(const DownArgs<T>& a) {
-    DownK<T> k{};
-    k.x = a.x, k.w = a.w, k.bias = a.bias, k.eps = (T)a.eps, k.a_dtype = a.a_dtype;
-    k.H = a.H, k.W = a.W, k.Ho = a.H / 2, k.Wo = a.W / 2, k.C = a.C, k.M = (long long)a.B * a.H * a.W;
+static LnClK<T> down_args(const DownArgs<T>& a) {
+    LnClK<T> k{};
+    k.x = a.x, k.w = a.w, k.bias = a.bias, k.eps = (T)a.eps, k.C = a.C, k.M = (long long)a.B * a.H * a.W;
     return k;
 }
+template <typename T>
+static DownIO down_io(const DownArgs<T>& a, void* A, const void* gA) { return DownIO{A, gA, a.a_dtype, a.H, a.W, a.H / 2, a.W / 2}; }
 
 template <typename T>
 int launch_down_train_fwd(const DownArgs<T>& a, int rebuild, void* A, T* stats, hipStream_t s) {
     if (int rc = down_check("down_train_fwd", a)) return rc;
     UNI_REQUIRE(aligned16(A) && aligned16(stats), "down_train_fwd: a pointer is not 16-byte aligned");
     UNI_REQUIRE(rebuild || a.eps > 0, "down_train_fwd: eps %g is not positive", a.eps);
-    DownK<T> k = down_args(a);
-    k.a = A;
+    LnClK<T> k = down_args(a);
     if (rebuild) k.stats_in = stats;
     else k.stats_out = stats;
     int rows;
-    if (int rc = down_dispatch<T, 0>("down_train_fwd", a, k, &rows, s)) return rc;
+    if (int rc = down_dispatch<T, 0>("down_train_fwd", a, k, down_io(a, A, nullptr), &rows, s)) return rc;
     UNI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -356,16 +181,11 @@ int launch_down_train_bwd(const DownArgs<T>& a, const T* stats, const void* gA, 
     if (!gx && !gw) return 0;
     T* part;
     if (int rc = train_partials("down_train_bwd", gw != nullptr, ws, ws_bytes, down_train_workspace_bytes(a.B, a.H, a.W, a.C), &part)) return rc;
-    DownK<T> k = down_args(a);
-    k.stats_in = stats, k.ga = gA, k.gx = gx, k.part = part;
+    LnClK<T> k = down_args(a);
+    k.stats_in = stats, k.gx = gx, k.part = part;
     int rows;
-    if (int rc = down_dispatch<T, 1>("down_train_bwd", a, k, &rows, s)) return rc;
-    if (gw) {
-        const DwlnRJob none{nullptr, nullptr, nullptr, 0, 0, 0, 0};
-        const DwlnRJob job{part, gw, gb, rows, 2 * a.C, a.C, cdiv(2 * a.C, 64)};
-        uni_variant_note("down_train reduce<%s>", train_ename(0, sizeof(T) == 8));
-        hipLaunchKernelGGL((dwln_reduce_kernel<T>), dim3(job.blocks), dim3(256), 0, s, none, job);
-    }
+    if (int rc = down_dispatch<T, 1>("down_train_bwd", a, k, down_io(a, nullptr, gA), &rows, s)) return rc;
+    if (gw) train_reduce_2c<T>(part, rows, a.C, gw, gb, "down_train", s);
     UNI_CHECK_HIP(hipGetLastError());
     return 0;
 }

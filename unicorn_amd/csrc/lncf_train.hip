@@ -5,11 +5,8 @@
 //   backward  xhat = (x - u) * rstd, t = grad_y * weight, grad_x = rstd * (t - mean_c t - xhat * mean_c (t * xhat)),
 //             part[block][2][C] = the block's sums of grad_y * xhat and of grad_y
 //
-//   lncf_cl_kernel<V, NV, MODE>    channels-last memory [B][H][W][C]: a pixel belongs to G lanes of ONE wave (G a power of two, 1 .. 64); a lane owns
-//                                  NV vectors of V consecutive channels (vector k of lane g = channels (k G + g) V ...; V = 4, or 8 for half x with
-//                                  C % 8 == 0: 16-byte loads of x either way), so the row of a pixel is in registers, x is read once, the variance
-//                                  is the second pass over registers and a sum over C is a butterfly over the G lanes: no LDS, no barrier.  A
-//                                  block of four waves takes 256 / G pixels at once (C = 96: G = 8, NV = 3, 32 pixels).
+//   ln_cl_kernel<V, NV, MODE, LncfIO>  channels-last memory [B][H][W][C]: the kernel of ln_cl.h, which down_train.hip runs too, with the policy below:
+//                                  y and grad_y are dense rows [B H W][C] of the math type, and every pixel has one.
 //   lncf_nchw_kernel<CH, KEEP, MODE>  NCHW-contiguous memory: a tile = 64 consecutive pixels of one image (lane = pixel: a wave reads 64 consecutive
 //                                  elements of a channel plane, whatever H W is: no alignment is assumed and a tile ends with its image), the eight
 //                                  waves of a block split the channels (wave w owns c = w, w + 8, ...).  KEEP: the slice of <= CH channels stays in
@@ -21,7 +18,7 @@
 // mode 0 = forward, 1 = backward.  Every output element has one writer, no atomics, fixed summation orders: bitwise reproducible.  Element
 // offsets are 64-bit; pixel, group and tile indices fit 32 bits (B H W < 2^31 is required).
 #include "kernels.h"
-#include "train_ops.h"
+#include "ln_cl.h"
 
 template <typename T>
 struct LncfK {                                  // kernel arguments (by value)
@@ -35,146 +32,23 @@ struct LncfK {                                  // kernel arguments (by value)
     long long M;                                // B H W
 };
 
-// sum over the G lanes of a pixel (G a power of two, the lanes are consecutive): xor butterfly, every lane gets the total
+// the output row / incoming gradient row of a pixel for ln_cl_kernel (ln_cl.h): dense [B H W][C] in the math type, every pixel has one
 template <typename T>
-__device__ __forceinline__ T lncf_group_sum(T v, int G) {
-    for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+struct LncfIO {
+    static constexpr bool REBUILD = false;
+    T* y;
+    const T* gy;
+    static __device__ __forceinline__ void place(LncfIO, long long pix, bool live, int C, bool& kept, size_t& ea) {
+        kept = live;
+        ea = (size_t)pix * C;
+    }
+    template <int V>
+    static __device__ __forceinline__ void store(LncfIO io, size_t off, const T (&r)[V]) { vec_store<T, V>(io.y + off, r); }
+    template <int V>
+    static __device__ __forceinline__ void load(LncfIO io, size_t off, T (&r)[V]) { vec_load<T, V>(io.gy + off, r); }
+};
 
 extern __shared__ double lncf_dyn_lds[];
-
-template <typename T, typename XT, int V, int NV, int MODE>
-__global__ __launch_bounds__(256) void lncf_cl_kernel(LncfK<T> p, int G, int lgG, unsigned ngroups) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = tid & (G - 1), slot = tid >> lgG, PPB = 256 >> lgG;
-    const int C = p.C, nvec = C / V;
-    const T cnt = T(C);
-    bool vok[NV];
-    int c[NV];
-    T wv[NV][V], bv[NV][V], dg[NV][V], db[NV][V];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int vec = k * G + g;
-        vok[k] = vec < nvec;
-        c[k] = vec * V;
-#pragma unroll
-        for (int j = 0; j < V; ++j) wv[k][j] = bv[k][j] = dg[k][j] = db[k][j] = T(0);
-        if (vok[k]) {
-            vec_load<T, V>(p.w + c[k], wv[k]);
-            if (MODE == 0) vec_load<T, V>(p.bias + c[k], bv[k]);
-        }
-    }
-    for (unsigned grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const long long pix = (long long)grp * PPB + slot;
-        const bool live = pix < p.M;            // the same in the G lanes of a pixel
-        const size_t e = (size_t)pix * C;
-        T xv[NV][V];
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-#pragma unroll
-            for (int j = 0; j < V; ++j) xv[k][j] = T(0);
-            if (live && vok[k]) vec_load<XT, V>(reinterpret_cast<const XT*>(p.x) + e + c[k], xv[k]);
-        }
-        if (MODE == 0) {
-            T s = 0;
-#pragma unroll
-            for (int k = 0; k < NV; ++k)
-#pragma unroll
-                for (int j = 0; j < V; ++j) s += xv[k][j];
-            const T mean = lncf_group_sum(s, G) / cnt;
-            T q = 0;
-#pragma unroll
-            for (int k = 0; k < NV; ++k)
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    xv[k][j] = vok[k] ? xv[k][j] - mean : T(0);
-                    q += xv[k][j] * xv[k][j];
-                }
-            const T rstd = T(1) / sqrt(lncf_group_sum(q, G) / cnt + p.eps);
-            if (live) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) {
-                    if (!vok[k]) continue;
-                    T r[V];
-#pragma unroll
-                    for (int j = 0; j < V; ++j) r[j] = (xv[k][j] * rstd) * wv[k][j] + bv[k][j];
-                    vec_store<T, V>(p.y + e + c[k], r);
-                }
-                if (g == 0) {
-                    p.stats_out[(size_t)pix * 2] = mean;
-                    p.stats_out[(size_t)pix * 2 + 1] = rstd;
-                }
-            }
-        } else {
-            T gv[NV][V];
-            T mean = 0, rstd = 0;
-            if (live) {
-                mean = p.stats_in[(size_t)pix * 2];
-                rstd = p.stats_in[(size_t)pix * 2 + 1];
-            }
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-#pragma unroll
-                for (int j = 0; j < V; ++j) gv[k][j] = T(0);
-                if (live && vok[k]) vec_load<T, V>(p.gy + e + c[k], gv[k]);
-            }
-            T s1 = 0, s2 = 0;
-#pragma unroll
-            for (int k = 0; k < NV; ++k)
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const T xh = vok[k] ? (xv[k][j] - mean) * rstd : T(0);
-                    const T t = gv[k][j] * wv[k][j];
-                    if (p.part) {
-                        dg[k][j] += gv[k][j] * xh;
-                        db[k][j] += gv[k][j];
-                    }
-                    s1 += t;
-                    s2 += t * xh;
-                    xv[k][j] = xh;
-                    gv[k][j] = t;
-                }
-            if (p.gx) {
-                const T a = lncf_group_sum(s1, G) / cnt, b = lncf_group_sum(s2, G) / cnt;
-                if (live) {
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) {
-                        if (!vok[k]) continue;
-                        T r[V];
-#pragma unroll
-                        for (int j = 0; j < V; ++j) r[j] = rstd * (gv[k][j] - a - xv[k][j] * b);
-                        vec_store<XT, V>(reinterpret_cast<XT*>(p.gx) + e + c[k], r);
-                    }
-                }
-            }
-        }
-    }
-    if (MODE == 1 && p.part) {                  // the pixel slots of a wave by butterfly, then the four waves in ascending order -> one row [2][C];
-        double* sg = lncf_dyn_lds;              // in double: a lane's own sum has few terms, the sum over the lanes has many
-        for (int w = 0; w < 4; ++w) {
-            if (wave == w) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) {
-#pragma unroll
-                    for (int j = 0; j < V; ++j) {
-                        double a = (double)dg[k][j], b = (double)db[k][j];
-                        for (int o = G; o < 64; o <<= 1) {
-                            a += __shfl_xor(a, o, 64);
-                            b += __shfl_xor(b, o, 64);
-                        }
-                        if (lane < G && vok[k]) {
-                            sg[c[k] + j] = (w ? sg[c[k] + j] : 0.0) + a;
-                            sg[C + c[k] + j] = (w ? sg[C + c[k] + j] : 0.0) + b;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        for (int i = tid; i < 2 * C; i += 256) p.part[(size_t)blockIdx.x * 2 * C + i] = (T)sg[i];
-    }
-}
 
 // channels of wave w of the NCHW path: c = w, w + LNCF_NW, ... < C
 __device__ __forceinline__ int lncf_slice(int C, int w) { return (C - w + LNCF_NW - 1) / LNCF_NW; }
@@ -376,24 +250,7 @@ static void lncf_launch(const LncfArgs<T>& a, const LncfK<T>& k, int* rows, hipS
             return;
         case LNCF_NCHW_STREAM8: return nchw(std::integral_constant<int, 8>(), std::false_type());
     }
-    train_with_vwidth<XT>(q.V, [&](auto vtag) {
-        constexpr int V = decltype(vtag)::value;
-        auto run = [&](auto ntag) {
-            constexpr int NV = decltype(ntag)::value;
-            hipLaunchKernelGGL((lncf_cl_kernel<T, XT, V, NV, MODE>), dim3(q.grid), dim3(q.block), q.lds, s, k, 1 << q.lg, q.lg, q.units);
-        };
-        switch (q.NV) {
-            case 1: run(std::integral_constant<int, 1>()); break;
-            case 2: run(std::integral_constant<int, 2>()); break;
-            case 3: run(std::integral_constant<int, 3>()); break;
-            case 4: run(std::integral_constant<int, 4>()); break;
-            default:                            // 6 or 8: more than 256 vectors, so V = 4
-                if constexpr (V == 4) {
-                    if (q.NV == 6) run(std::integral_constant<int, 6>());
-                    else run(std::integral_constant<int, 8>());
-                }
-        }
-    });
+    ln_cl_launch<T, XT, MODE>(q, LnClK<T>{k.x, k.w, k.bias, k.stats_in, k.stats_out, k.gx, k.part, k.eps, k.C, k.M}, LncfIO<T>{k.y, k.gy}, s);
 }
 
 template <typename T, int MODE>
@@ -432,12 +289,7 @@ int launch_lncf_train_bwd(const LncfArgs<T>& a, const T* stats, const T* gy, voi
     const LncfK<T> k{a.x, a.w, nullptr, gy, stats, nullptr, nullptr, gx, part, T(0), a.H * a.W, a.C, (long long)a.B * a.H * a.W};
     int rows;
     if (int rc = lncf_dispatch<T, 1>("lncf_train_bwd", a, k, &rows, s)) return rc;
-    if (gw) {
-        const DwlnRJob none{nullptr, nullptr, nullptr, 0, 0, 0, 0};
-        const DwlnRJob job{part, gw, gb, rows, 2 * a.C, a.C, cdiv(2 * a.C, 64)};
-        uni_variant_note("lncf_train reduce<%s>", train_ename(0, sizeof(T) == 8));
-        hipLaunchKernelGGL((dwln_reduce_kernel<T>), dim3(job.blocks), dim3(256), 0, s, none, job);
-    }
+    if (gw) train_reduce_2c<T>(part, rows, a.C, gw, gb, "lncf_train", s);
     UNI_CHECK_HIP(hipGetLastError());
     return 0;
 }

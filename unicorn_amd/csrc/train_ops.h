@@ -39,6 +39,22 @@ static void train_with_vwidth(int V, F&& f) {
     }
     f(std::integral_constant<int, 4>());
 }
+// a channels-last plan's vectors per lane NV (lncf_plan: 1, 2, 3, 4, 6 or 8) next to its V as a template argument: f(integral_constant<int, NV>).
+// 6 and 8 mean more than 256 vectors, which only V = 4 has
+template <int V, typename F>
+static void train_with_nv(int NV, F&& f) {
+    switch (NV) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+        default:
+            if constexpr (V == 4) {
+                if (NV == 6) f(std::integral_constant<int, 6>());
+                else f(std::integral_constant<int, 8>());
+            }
+    }
+}
 // the partials of a backward that has them `wanted`: *part = ws, which must hold f32_bytes (twice that for T = double); otherwise null
 template <typename T>
 static int train_partials(const char* what, bool wanted, void* ws, size_t ws_bytes, size_t f32_bytes, T** part) {
@@ -103,4 +119,12 @@ __global__ __launch_bounds__(256) void dwln_reduce_kernel(DwlnRJob j0, DwlnRJob 
         if (n < n1) out1[n] = (T)a;
         else out2[n - n1] = (T)a;
     }
+}
+// one job alone: the partials [rows][2][C] of a LayerNorm backward -> gw [C], gb [C]; `op` is the operator in the tag `<op> reduce<f32>`
+template <typename T>
+static void train_reduce_2c(const T* part, int rows, int C, T* gw, T* gb, const char* op, hipStream_t s) {
+    const DwlnRJob none{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    const DwlnRJob job{part, gw, gb, rows, 2 * C, C, cdiv(2 * C, 64)};
+    uni_variant_note("%s reduce<%s>", op, train_ename(0, sizeof(T) == 8));
+    hipLaunchKernelGGL((dwln_reduce_kernel<T>), dim3(job.blocks), dim3(256), 0, s, none, job);
 }
